@@ -13,6 +13,9 @@ re-uploaded outside the timed region only when it changes -- it does not).
 ``value`` = DOF/s of the forward part = ndof * K * N / (time spent in forward solves), the
 BASELINE.json metric "DOF/s (assembly+solve)"; ``adjoint_ms`` is the adjoint-gradient wall-clock
 per step, the second half of that metric.  ``ms_per_step`` covers the whole step.
+
+``--dump-outputs DIR`` writes what the last timed step computed (the state and d compliance / d thickness; for
+plate500k_dynamic the displacement history of the march) as DIR/<name>.npy, see ``dump_outputs``.
 """
 import argparse
 import json
@@ -117,6 +120,24 @@ def pmc_traffic(workload):
     # per-class figures of the rank-k updates (scripts/r4_pmc_levels.py): launches above / below the ridge of the chip
     by_class = {"mfma": pj.get("trailing_mfma_bound_hbm_bytes_per_launch"), "hbm": pj.get("trailing_hbm_bound_hbm_bytes_per_launch")}
     return pj.get("apply_hbm_bytes_per_launch"), pj.get("trailing_hbm_bytes_per_launch"), by_class
+
+
+DUMP_BYTES = 60_000_000          # array data of --dump-outputs: with the .npy headers well inside 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs DIR``: the arrays the timed path returned in its last step, one ``DIR/<name>.npy`` each in float64, so that two
+    builds run with the same arguments (the inputs are the same from run to run) can be compared output for output.  When the arrays
+    hold more than DUMP_BYTES together, every one of them is cut to the same share of its entries: the flattened array at the sorted
+    indices ``np.random.default_rng(0).choice(size, k, replace=False)`` -- the same sample for every build."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            k = a.size * DUMP_BYTES // total
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def make_workload(name, renumber=True, timings=None, tri=None):
@@ -435,6 +456,8 @@ def main_dynamic(args, torch):
     torch.cuda.synchronize()
     t_total = time.perf_counter() - t_start
     W = ctx.newmark_history(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"displacement_history": W})
     dist_parity = golden_distance_dynamic(W, mesh)
     tip = float(np.abs(W[-1, 2:mesh.ndof_u:3]).max())
     its = [i for i, _ in rows[-1][1]]
@@ -535,7 +558,7 @@ def main_distributed(args, rank, local_rank, world, torch, dist):
         dist.barrier()
         sync()
 
-    def run_case(scaling, steps, warmup):
+    def run_case(scaling, steps, warmup, dump=None):
         mult = world if scaling == "weak" else 1
         m = wing_skin_mesh(nc, ns * mult, span=6.0 * mult * ns / 580.0).renumbered()[0]
         leaf = m.recommended_leaf_size() if args.leaf is None else args.leaf
@@ -558,6 +581,7 @@ def main_distributed(args, rank, local_rank, world, torch, dist):
             g, it2, rr2 = ds.total_gradient("compliance", "thickness")
             sync()
             t2 = time.perf_counter()
+            step.gradient = g
             return (t1 - t0, t2 - t1, it, rr, it2, rr2)
 
         for _ in range(warmup):
@@ -570,6 +594,10 @@ def main_distributed(args, rank, local_rank, world, torch, dist):
         tt = torch.tensor([t_total, sum(r[0] for r in rows), sum(r[1] for r in rows)], device=dev, dtype=torch.float64)
         comm.allreduce_(tt, op="max")
         t_total, t_fwd, t_adj = tt.tolist()
+        if dump:
+            state = ds.gather_state()                            # collective: every rank takes part
+            if rank == 0:
+                dump_outputs(dump, {"state": state, "dcompliance_dthickness": step.gradient})
         return dict(ds=ds, m=m, rows=rows, t_total=t_total, t_fwd=t_fwd, t_adj=t_adj, steps=steps, scaling=scaling)
 
     def figures(r):
@@ -580,7 +608,7 @@ def main_distributed(args, rank, local_rank, world, torch, dist):
                 "replicated_separator_dofs": ds.info["n_top"], "pcg_iterations_forward": r["rows"][-1][2],
                 "pcg_iterations_adjoint": r["rows"][-1][4]}
 
-    main_run = run_case(args.scaling, args.steps, args.warmup)
+    main_run = run_case(args.scaling, args.steps, args.warmup, dump=args.dump_outputs)
     ds, m, rows = main_run["ds"], main_run["m"], main_run["rows"]
     prof = apply_ms = None
     if not rehearsal:
@@ -700,7 +728,11 @@ def main():
                          "line says REHEARSAL and is not a measurement)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal: allow --gpus N on a box with fewer cards (the ranks share them; collectives over gloo)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1 or args.warmup is not None and args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)
 
@@ -794,6 +826,7 @@ def main():
         step.timing = ctx.last_timing()
         g, it2, rr2 = ctx.total_gradient("compliance", "thickness")
         t2 = time.perf_counter()
+        step.gradient = g
         return (t1 - t0, t2 - t1, it, rr, it2, rr2)
 
     for _ in range(args.warmup):
@@ -803,6 +836,8 @@ def main():
     rows = [step() for _ in range(args.steps)]
     barrier()
     t_total = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"state": ctx.get_state(), "dcompliance_dthickness": step.gradient})
     t_fwd = sum(r[0] for r in rows)
     t_adj = sum(r[1] for r in rows)
     if dist is not None:

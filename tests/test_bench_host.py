@@ -60,6 +60,29 @@ def test_committed_counter_passes_belong_to_the_committed_sources():
     assert rec["source_digest"] == _build.source_digest(), "kernel sources changed after the counter passes: re-run scripts/r4_rocprof.sh"
 
 
+def test_dumped_outputs_are_float64_within_the_budget_and_the_same_sample_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    w, g = np.arange(1000.0), np.arange(10, dtype=np.float32).reshape(2, 5)
+    bench.dump_outputs(str(tmp_path / "all"), {"state": w, "grad": g})
+    assert np.array_equal(np.load(tmp_path / "all" / "state.npy"), w)
+    got = np.load(tmp_path / "all" / "grad.npy")
+    assert got.dtype == np.float64 and got.shape == (2, 5) and np.array_equal(got, g)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)                  # 8080 bytes in all: each array cut to half of its entries
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"state": w, "grad": g})
+    a, ga = np.load(tmp_path / "a" / "state.npy"), np.load(tmp_path / "a" / "grad.npy")
+    assert a.size + ga.size <= 500 and a.size == 4000 * 1000 // 8080 and ga.size == 4
+    assert np.all(np.diff(a) > 0) and np.isin(a, w).all()          # sorted entries of the array, no repeats
+    assert np.array_equal(a, np.load(tmp_path / "b" / "state.npy")) and np.array_equal(ga, np.load(tmp_path / "b" / "grad.npy"))
+
+
+def test_bench_refuses_a_timed_region_without_steps():
+    import subprocess
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
 def test_workload_table():
     m, fields, marker, desc = bench.make_workload("plate8k")
     assert m.ndof == 8046 and "8046 DOF" in desc

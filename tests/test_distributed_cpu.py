@@ -61,12 +61,13 @@ def test_rank_plans_partition_the_mesh(kind):
     assert owned.max() == 1
 
 
-def test_bench_launcher_with_two_ranks_on_the_cpu():
+def test_bench_launcher_with_two_ranks_on_the_cpu(tmp_path):
     """``python bench.py --gpus 2`` without a launcher and without a GPU: bench.py's own ``launch_ranks`` starts two ranks
     (torch.distributed.run --standalone), the ranks rendezvous over gloo, run the partitioned forward + adjoint step of
     ``main_distributed`` on a small skin with the numpy stand-in engine (``--rehearsal-engine``: a test hook, the line says
     REHEARSAL) and rank 0 prints the one JSON line of the contract -- with the element-partition label, and with the OTHER scaling
-    as a sub-object (``weak`` beside the default strong run)."""
+    as a sub-object (``weak`` beside the default strong run).  ``--dump-outputs``: rank 0 writes the gathered state and the
+    gradient of the last timed step, the single-domain oracle's solution of the same skin."""
     import json
     import subprocess
     import sys
@@ -74,8 +75,10 @@ def test_bench_launcher_with_two_ranks_on_the_cpu():
     env = dict(os.environ, FEMO_BENCH_NC="8", FEMO_BENCH_NS="24", OMP_NUM_THREADS="2",
                PYTHONPATH=os.pathsep.join([os.path.join(root, "tests"), root, os.environ.get("PYTHONPATH", "")]))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
+    out = tmp_path / "outputs"
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                          "--rehearsal-engine", "dist_helpers:NumpyEngine"], env=env, capture_output=True, text=True, timeout=600)
+                          "--rehearsal-engine", "dist_helpers:NumpyEngine", "--dump-outputs", str(out)],
+                         env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -88,3 +91,13 @@ def test_bench_launcher_with_two_ranks_on_the_cpu():
     w = j["weak"]
     assert w["scaling"] == "weak" and w["ndof"] > j["config"]["ndof"] and w["ndof_per_gpu"] >= 0.8 * j["config"]["ndof_per_gpu"]
     assert w["pcg_iterations_forward"] <= 4
+    from femo_alpha_amd.mesh import wing_skin_mesh
+    m = wing_skin_mesh(8, 24, span=6.0 * 24 / 580.0).renumbered()[0]          # main_distributed's skin at FEMO_BENCH_NC / NS
+    fields = dict(thickness=[1.27e-3], E=[73.1e9], nu=[0.33], density=[2780.0],
+                  F_solid=np.tile([0.0, 0.0, -2780.0 * 1.27e-3 * 9.81], (m.nn, 1)))
+    w0, _, dJ0, _ = H.reference_solution(m, lambda x: np.less(x[1], 1e-9), fields)
+    assert sorted(os.listdir(out)) == ["dcompliance_dthickness.npy", "state.npy"]
+    state, grad = np.load(out / "state.npy"), np.load(out / "dcompliance_dthickness.npy")
+    assert state.dtype == grad.dtype == np.float64 and state.shape == (j["config"]["ndof"],) == w0.shape
+    assert np.abs(state - w0).max() < 1e-8 * np.abs(w0).max()
+    assert np.abs(grad - dJ0).max() < 1e-7 * np.abs(dJ0).max()

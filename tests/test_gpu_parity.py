@@ -1225,3 +1225,26 @@ def test_cg2cr1_element(kind, uhat, bc, ewm):
     it3, rr3 = c.solve_state(zero_guess=True)
     assert rr3 <= 1e-12 and rel(c.get_state(), w_ref) < 1e-7
     c.close()
+
+
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """``bench.py --dump-outputs DIR`` on the single-GPU path: the state and d compliance / d thickness of the last timed step, float64,
+    against the oracle's solution of the same workload (BASELINE config 1, the bench's own numbering)."""
+    import os
+    import subprocess
+    import sys
+    import bench
+    from oracle.rm_shell_oracle import ShellOracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "plate8k", "--steps", "2", "--warmup", "1",
+                        "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    m, fields, marker, _ = bench.make_workload("plate8k")
+    o = ShellOracle(m, penalty_facets=m.penalty_facets(marker))
+    o.set_fields(h=fields["thickness"], E=fields["E"], nu=fields["nu"], rho=fields["density"], f=fields["F_solid"])
+    w_ref, _, dJ_ref = o.forward_adjoint()
+    assert sorted(os.listdir(out)) == ["dcompliance_dthickness.npy", "state.npy"]
+    w, dJ = np.load(out / "state.npy"), np.load(out / "dcompliance_dthickness.npy")
+    assert w.dtype == dJ.dtype == np.float64 and w.shape == w_ref.shape and dJ.shape == dJ_ref.shape
+    assert rel(w, w_ref) < 1e-8 and rel(dJ, dJ_ref) < 1e-8
