@@ -265,6 +265,15 @@ class Recorder:
                     derivs = {}
                     op.compute_derivatives(ivals, ovals, derivs)
                     for k, v in op._inputs.items():
+                        if (key, k) in derivs and bar.size > 1:
+                            # an output with several entries (a field): J has one row per entry, sparse or dense -> J^T bar
+                            J = derivs[(key, k)]
+                            if hasattr(J, "tocsr"):
+                                g = J.T @ bar
+                            else:
+                                g = np.asarray(J, dtype=np.float64).reshape(bar.size, -1).T @ bar
+                            self._push_to_source(v, np.asarray(g, dtype=np.float64).reshape(-1), sink)
+                            continue
                         if (key, k) in derivs:
                             J = np.asarray(derivs[(key, k)], dtype=np.float64).reshape(-1)
                             self._push_to_source(v, bar[0] * J, sink)

@@ -74,6 +74,12 @@ SIGNATURES = {
     "femo_set_cell_tags": (C.c_int, [C.c_void_p, _c_int32_p, C.c_int64, C.c_int32]),
     "femo_select_subdomain": (C.c_int, [C.c_void_p, C.c_int32]),
     "femo_field_output": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, C.c_int64]),
+    "femo_field_output_vjp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64]),
+    "femo_field_output_jacobian_nnz": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]),
+    "femo_field_output_jacobian": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), _c_int32_p, _c_double_p,
+                                             C.c_int64]),
+    "femo_field_total_gradients": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _c_double_p, C.c_char_p, _c_double_p, C.c_int64,
+                                             _c_int32_p, _c_double_p]),
     "femo_functional": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p]),
     "femo_dfunctional": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, _c_double_p, C.c_int64]),
     "femo_dRdarg_T": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, _c_double_p, C.c_int64]),

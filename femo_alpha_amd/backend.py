@@ -446,6 +446,43 @@ class ShellContext:
         self._chk(self.lib.femo_field_output(self._h, name.encode(), dptr(out), out.size))
         return out
 
+    def field_output_vjp(self, name, wrt, cbar):
+        """(d field / d wrt)^T cbar for the stored state and fields (femo_field_output_vjp); ``cbar``: one cotangent of nvc * nel
+        entries, or several as rows of a 2-D array (the result has the same number of rows).  Points of zero stress contribute
+        zero (a subgradient)."""
+        cb = np.ascontiguousarray(cbar, dtype=np.float64)
+        one = cb.ndim == 1
+        cb = cb.reshape(-1, self.mesh.nvc * self.mesh.nel) if cb.size else cb.reshape(0, self.mesh.nvc * self.mesh.nel)
+        out = np.empty((cb.shape[0], self.arg_size(wrt)))
+        self._chk(self.lib.femo_field_output_vjp(self._h, name.encode(), wrt.encode(), dptr(cb), cb.shape[0], dptr(out),
+                                                 out.shape[1]))
+        return out[0] if one else out
+
+    def field_output_jacobian(self, name, wrt):
+        """The partial Jacobian d field / d wrt as a ``scipy.sparse.csr_matrix`` of shape (nvc * nel, arg_size(wrt)): per cell a
+        dense block, the columns of a row in the cell's local order (femo_field_output_jacobian)."""
+        import scipy.sparse as sp
+        nnz = C.c_int64()
+        self._chk(self.lib.femo_field_output_jacobian_nnz(self._h, name.encode(), wrt.encode(), C.byref(nnz)))
+        nrow = self.mesh.nvc * self.mesh.nel
+        rowptr = np.empty(nrow + 1, dtype=np.int64)
+        colidx = np.empty(nnz.value, dtype=np.int32)
+        vals = np.empty(nnz.value)
+        self._chk(self.lib.femo_field_output_jacobian(self._h, name.encode(), wrt.encode(), rowptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      iptr(colidx), dptr(vals), nnz.value))
+        return sp.csr_matrix((vals, colidx, rowptr), shape=(nrow, self.arg_size(wrt)))
+
+    def field_total_gradients(self, name, cbars, arg):
+        """Total derivatives d (cbar_k . field) / d arg through the solved state for the rows cbar_k of ``cbars`` -- one grouped
+        adjoint solve (femo_field_total_gradients).  Returns (gradients (nbar, n), iterations, relative residuals)."""
+        cb = np.ascontiguousarray(np.atleast_2d(np.asarray(cbars, dtype=np.float64)))
+        nb = cb.shape[0]
+        out = np.empty((nb, self.field_size(arg)))
+        it = np.zeros(nb, dtype=np.int32); rr = np.zeros(nb)
+        self._chk(self.lib.femo_field_total_gradients(self._h, name.encode(), nb, dptr(cb), arg.encode(), dptr(out), out.shape[1],
+                                                      iptr(it), dptr(rr)))
+        return out, it, rr
+
     def arg_size(self, wrt):
         return self.ndof if wrt == "disp_solid" else self.field_size(wrt)
 

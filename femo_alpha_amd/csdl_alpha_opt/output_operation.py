@@ -43,7 +43,9 @@ class OutputOperation(csdl.CustomExplicitOperation):
 
 
 class OutputFieldOperation(csdl.CustomExplicitOperation):
-    """Field output; like the reference (:100-128) it defines ``compute`` only, no derivatives."""
+    """Field output (the reference's :72-128).  ``compute_derivatives`` returns, per declared argument, the sparse partial
+    Jacobian d field / d arg (nvc * nel rows, ``assemble(partial, dim=2)``) -- the reference declares these derivatives but
+    defines no ``compute_derivatives``."""
 
     def __init__(self, fea, args_name_list, output_name):
         super().__init__()
@@ -68,3 +70,9 @@ class OutputFieldOperation(csdl.CustomExplicitOperation):
         push_inputs(self, input_vals)
         self.fea.projectFieldOutput(self.fea_output["form"], self.fea_output["function"])
         output_vals[self.output_name] = getFuncArray(self.fea_output["function"])
+
+    def compute_derivatives(self, input_vals, output_vals, derivatives):
+        push_inputs(self, input_vals)
+        for arg in input_vals:
+            partial = computePartials(self.fea_output["form"], self.args_dict[arg]["function"])
+            derivatives[self.output_name, arg] = assemble(partial, dim=self.output_dim + 1)

@@ -6,6 +6,7 @@
 #include "sweeps_multi.h"
 #include "shape_sens.h"
 #include "stress.h"
+#include "stress_grad.h"
 #include "csr_map.h"
 
 #include <hip/hip_runtime.h>
@@ -70,6 +71,7 @@ struct femo_ctx {
     int* eorder = nullptr;      // elements along a Morton curve of their centroids (locality of gathers)
     int *n2e_off = nullptr, *n2e_ent = nullptr;   // inverted connectivity: P2 node -> (slot in Morton order) * npc + local node
     double* ybuf = nullptr;     // element results of the operator, YSTRIDE doubles per slot
+    int *v2e_off = nullptr, *v2e_ent = nullptr;   // vertex -> e * nvc + local vertex, cells in increasing order (stress-field derivatives)
     double* hK = nullptr;
     Tables* tab = nullptr;
     Tables* tab_s = nullptr;     // degree-4 rule of the p-norm stress measure (3x3 Gauss on quads)
@@ -2058,6 +2060,16 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
         HIPCHK(c, hipMalloc((void**)&c->n2e_ent, ent.size() * sizeof(int)));
         HIPCHK(c, hipMemcpy(c->n2e_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc((void**)&c->ybuf, (size_t)nel * YSTRIDE * sizeof(double)));
+        // vertex -> (cell, local vertex): the fixed-order sums of the per-cell results of the nodal-field derivatives
+        std::vector<int> voff(c->nn + 1, 0), vent((size_t)nel * nvc);
+        for (size_t i = 0; i < (size_t)nel * nvc; ++i) voff[cells[i] + 1]++;
+        for (int v = 0; v < c->nn; ++v) voff[v + 1] += voff[v];
+        std::vector<int> vcur(voff.begin(), voff.end() - 1);
+        for (size_t i = 0; i < (size_t)nel * nvc; ++i) vent[vcur[cells[i]]++] = (int)i;
+        HIPCHK(c, hipMalloc((void**)&c->v2e_off, voff.size() * sizeof(int)));
+        HIPCHK(c, hipMemcpy(c->v2e_off, voff.data(), voff.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMalloc((void**)&c->v2e_ent, vent.size() * sizeof(int)));
+        HIPCHK(c, hipMemcpy(c->v2e_ent, vent.data(), vent.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     HIPCHK(c, hipMalloc((void**)&c->hK, (size_t)nel * sizeof(double)));
     HIPCHK(c, hipMemcpy(c->hK, hK.data(), (size_t)nel * sizeof(double), hipMemcpyHostToDevice));
@@ -2176,7 +2188,7 @@ void femo_destroy(femo_ctx* c) {
     for (double* p : c->fp)
         if (p) hipFree(p);
     if (c->eq) hipFree(c->eq);
-    void* ptrs[] = {c->bi[0], c->bi[1], c->bi[2], c->bi[3], c->bi[4], c->ctag, c->gradbuf, c->csr_perm, c->csr_dest, c->csr_rowptr, c->csr_colidx, c->csr_vals, c->csr_ke, c->xyz, c->cells, c->cellp2, c->eorder, c->n2e_off, c->n2e_ent, c->ybuf, c->hK, c->tab, c->tab_s, c->tab_pre, c->h, c->E, c->nu, c->rho, c->f, c->uhat, c->fcell, c->fledge,
+    void* ptrs[] = {c->bi[0], c->bi[1], c->bi[2], c->bi[3], c->bi[4], c->ctag, c->gradbuf, c->csr_perm, c->csr_dest, c->csr_rowptr, c->csr_colidx, c->csr_vals, c->csr_ke, c->xyz, c->cells, c->cellp2, c->eorder, c->n2e_off, c->n2e_ent, c->ybuf, c->v2e_off, c->v2e_ent, c->hK, c->tab, c->tab_s, c->tab_pre, c->h, c->E, c->nu, c->rho, c->f, c->uhat, c->fcell, c->fledge,
                     c->funode, c->fvnode, c->fM2, c->fM1, c->frnode, c->fMR, c->mask, c->w, c->lam, c->r, c->z, c->p, c->Ap, c->dinv, c->b, c->tmp,
                     c->scal};
     for (void* p : ptrs)
@@ -4149,6 +4161,176 @@ int femo_field_output(femo_ctx* c, const char* name, double* out, int64_t n) {
     HIPCHK(c, e);
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------ derivatives of the stress fields
+// xi2 = zf h of the field output `name`; false for an unknown name
+static bool field_zf(const std::string& name, double* zf) {
+    if (name == "stress") *zf = 0.5;
+    else if (name == "stress_mid") *zf = 0.0;
+    else if (name == "stress_bot") *zf = -0.5;
+    else return false;
+    return true;
+}
+
+// entries per row of the partial Jacobian d field / d wrt (0: the field does not depend on wrt); -1: unknown argument
+static int field_jac_width(const femo_ctx* c, const std::string& wrt) {
+    if (wrt == "disp_solid") return c->ld;
+    if (wrt == "thickness" || wrt == "E" || wrt == "nu") return c->ewm ? 1 : c->nvc;
+    if (wrt == "uhat") return 3 * c->nvc;
+    if (wrt == "F_solid" || wrt == "density") return 0;
+    return -1;
+}
+
+static int field_arg_len(femo_ctx* c, const std::string& wrt, int64_t n) {
+    int64_t len;
+    if (wrt == "disp_solid") len = c->ndof;
+    else if (!field_ptr(c, wrt.c_str(), &len) || field_jac_width(c, wrt) < 0) return fail(c, "unknown argument '" + wrt + "'");
+    if (len != n) return fail(c, "buffer has the wrong length for '" + wrt + "'");
+    return 0;
+}
+
+#define FIELD_UHAT_LAUNCH(c, nthreads, ...)                                                                                            \
+    do {                                                                                                                               \
+        const int g_ = nblk(nthreads, 128);                                                                                            \
+        if ((c)->cg1) { if ((c)->quad) hipLaunchKernelGGL((k_field_uhat<4, 4, true>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); \
+                        else hipLaunchKernelGGL((k_field_uhat<3, 3, false>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); }      \
+        else { if ((c)->quad) hipLaunchKernelGGL((k_field_uhat<9, 4, true>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__);         \
+               else hipLaunchKernelGGL((k_field_uhat<6, 3, false>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); }                \
+    } while (0)
+
+// out (device, n) = (d field / d wrt)^T cbar for one device cotangent cbar (nvc * nel); every entry of out is written
+static int field_vjp_dev(femo_ctx* c, double zf, const std::string& wrt, const double* cbar, double* out, int64_t n) {
+    const MeshDev m = mesh_dev_all(c);
+    const FieldsDev f = fields_dev(c);
+    const int g = nblk(c->nel, EB);
+    const int mode = wrt == "disp_solid" ? 1 : wrt == "thickness" ? 2 : wrt == "E" ? 3 : wrt == "nu" ? 4 : 0;
+    if (mode) {
+        ELEM_LAUNCH(c, k_field_vjp, NOEXTRA, g, EB, m, f, c->tab, c->eorder, c->w, zf, mode, cbar, c->ybuf, out);
+        if (mode == 1) {
+            const int nthreads = c->nP2 + c->nghost;
+#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
+                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
+            if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
+            else if (c->quad) GATHER_SUM(9, 4);
+            else GATHER_SUM(6, 3);
+#undef GATHER_SUM
+        } else if (!c->ewm) {
+            hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(c->nn, 256)), dim3(256), 0, c->stream, c->nn, 1, c->v2e_off, c->v2e_ent, c->ybuf, out);
+        }
+    } else if (wrt == "uhat") {
+        FIELD_UHAT_LAUNCH(c, (int64_t)c->nel * 3 * c->nvc, m, f, c->tab, c->w, zf, cbar, c->ybuf, (double*)nullptr, (int*)nullptr);
+        hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(3 * (int64_t)c->nn, 256)), dim3(256), 0, c->stream, c->nn, 3, c->v2e_off, c->v2e_ent,
+                           c->ybuf, out);
+    } else {                                          // F_solid, density: the field does not depend on them
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const std::string fname(name ? name : ""), a(wrt ? wrt : "");
+    double zf;
+    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
+    if (field_arg_len(c, a, n)) return 1;
+    const size_t nc = (size_t)c->nvc * c->nel;
+    double* d = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d, ((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)) * sizeof(double)));
+    double* o = d + (size_t)nbar * nc;
+    int rc = 0;
+    if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
+    for (int64_t k = 0; k < nbar && !rc; ++k) rc = field_vjp_dev(c, zf, a, d + k * nc, o + k * n, n);
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
+    }
+    hipFree(d);
+    return rc;
+}
+
+int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wrt, int64_t* nnz) {
+    const std::string fname(name ? name : ""), a(wrt ? wrt : "");
+    double zf;
+    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    const int wd = field_jac_width(c, a);
+    if (wd < 0) return fail(c, "unknown argument '" + a + "'");
+    if (!nnz) return fail(c, "null nnz");
+    *nnz = (int64_t)wd * c->nvc * c->nel;
+    return 0;
+}
+
+int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, int64_t* rowptr, int32_t* colidx, double* vals, int64_t nnz) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const std::string fname(name ? name : ""), a(wrt ? wrt : "");
+    int64_t want;
+    if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
+    if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
+    if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
+    double zf;
+    field_zf(fname, &zf);
+    const int wd = field_jac_width(c, a);
+    const int64_t nrow = (int64_t)c->nvc * c->nel;
+    for (int64_t r = 0; r <= nrow; ++r) rowptr[r] = r * wd;
+    if (nnz == 0) return 0;
+    double* dv = nullptr;
+    int* dc = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dv, (size_t)nnz * sizeof(double)));
+    if (hipMalloc((void**)&dc, (size_t)nnz * sizeof(int)) != hipSuccess) { hipFree(dv); return fail(c, "out of device memory"); }
+    const MeshDev m = mesh_dev_all(c);
+    const FieldsDev f = fields_dev(c);
+    if (a == "uhat") {
+        FIELD_UHAT_LAUNCH(c, (int64_t)c->nel * 3 * c->nvc, m, f, c->tab, c->w, zf, (const double*)nullptr, (double*)nullptr, dv, dc);
+    } else {
+        const int mode = a == "disp_solid" ? 1 : a == "thickness" ? 2 : a == "E" ? 3 : 4;
+        ELEM_LAUNCH(c, k_field_jac, NOEXTRA, nblk(nrow, EB), EB, m, f, c->tab, c->w, zf, mode, dv, dc);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(vals, dv, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(colidx, dc, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost);
+    hipFree(dv);
+    hipFree(dc);
+    HIPCHK(c, e);
+    return 0;
+}
+
+// Total derivatives of nbar linear functionals g_k = cbar_k . field of the solved state:  lambda_k = K^-1 (d field / d w)^T cbar_k
+// (grouped sweeps, strong-BC masking of solve_multi_dev),  out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k.
+int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, const double* cbar, const char* arg, double* out, int64_t n,
+                               int32_t* iters, double* relres) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const std::string fname(name ? name : ""), a(arg ? arg : "");
+    double zf;
+    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
+    if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
+    if (field_arg_len(c, a, n)) return 1;
+    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nvc * c->nel;
+    double* Bd = mr_io_buffer(c, (size_t)nbar * (2 * nd + (size_t)std::max<int64_t>(n, 1) + nc));
+    if (!Bd) return 1;
+    double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * std::max<int64_t>(n, 1);
+    std::vector<double*> B(nbar), X(nbar);
+    for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    int rc = 0;
+    if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
+    for (int k = 0; k < nbar && !rc; ++k) rc = field_vjp_dev(c, zf, "disp_solid", Cd + k * nc, B[k], c->ndof);     // (d field / d w)^T cbar_k
+    if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                                    // lambda_k
+    for (int k = 0; k < nbar && !rc; ++k) {
+        double* g = Gd + (size_t)k * n;
+        rc = field_vjp_dev(c, zf, a, Cd + k * nc, g, n);                                                          // (d field / d arg)^T cbar_k
+        if (!rc) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                                       // - (dR/d arg)^T lambda_k
+    }
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, Gd, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
+    }
+    return rc;
+}
+#undef FIELD_UHAT_LAUNCH
 
 int femo_last_timing(const femo_ctx* c, double* out5) {
     for (int i = 0; i < 5; ++i) out5[i] = c->timing[i];

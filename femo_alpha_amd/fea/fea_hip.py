@@ -128,7 +128,8 @@ class Form:
 
 
 class FieldForm:
-    """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1)."""
+    """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1), 'stress_mid', 'stress_bot'.
+    ``assemble(computePartials(field_form, f), dim=2)`` is its sparse partial Jacobian."""
 
     def __init__(self, ctx, name):
         self.ctx, self.name = ctx, name
@@ -235,11 +236,20 @@ def assembleSystem(J, F, bcs=()):
     return JacobianOperator(J, bcs), F.ctx.residual()
 
 
+def assembleFieldPartial(v: PartialForm):
+    """d field / d argument of a field output as a scipy CSR matrix (nvc * nel rows): the reference's idiom for the partials of
+    an output of dimension 1, ``assemble(computePartials(form, f), dim=2)``."""
+    wrt = "disp_solid" if v.wrt.role == "state" else v.wrt.role
+    return v.form.ctx.field_output_jacobian(v.form.name, wrt)
+
+
 def assemble(f, dim=0, bcs=()):
     if dim == 0:
         return assembleScalar(f)
     if dim == 1:
         return assembleVector(f)
+    if dim == 2 and isinstance(f, PartialForm) and isinstance(f.form, FieldForm):
+        return assembleFieldPartial(f)
     raise TypeError("Invalid type for assembly.")
 
 

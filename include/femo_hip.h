@@ -269,6 +269,30 @@ int femo_select_subdomain(femo_ctx* ctx, int32_t sel);
  * (cell-major, the cell's vertices in connectivity order) -- replaces FEA.projectFieldOutput (fea/fea_dolfinx.py:205-206,
  * csdl_alpha_opt/output_operation.py:116-123). */
 int femo_field_output(femo_ctx* ctx, const char* name, double* out, int64_t n);
+/* Derivatives of the field outputs -- new: the reference's OutputFieldOperation declares them but defines no
+ * compute_derivatives (csdl_alpha_opt/output_operation.py:72-128).  name = "stress" | "stress_mid" | "stress_bot";
+ * wrt / arg = "disp_solid" (not for the totals), "thickness", "E", "nu", "uhat", "F_solid", "density" (the last two give
+ * zeros).  Per cell the field is c_e = M_e^-1 b_e with a mass matrix M_e of the reference geometry, so only the von Mises
+ * stress vm_q at the quadrature points is differentiated.  Zero-stress convention: a point with vm_q = 0 (w = 0, say)
+ * contributes zero -- a subgradient, as for "pnorm_stress"; every derivative is finite there.  Sums over the cells run in
+ * a fixed order without atomics: two identical calls return the same bits.
+ * femo_field_output_vjp: nbar cotangents cbar (nbar x nvc*nel, cell-major like femo_field_output) -> out (nbar x n,
+ *   n = the argument's length, femo_ndof for "disp_solid"): out_k = (d field / d wrt)^T cbar_k.
+ * femo_field_output_jacobian_nnz / femo_field_output_jacobian: the partial Jacobian d field / d wrt as CSR with nvc*nel
+ *   rows (row nvc*e + i: vertex i of cell e) and a fixed number of entries per row -- ld = 3 npc + 3 nvc for "disp_solid",
+ *   nvc for nodal (1 for per-cell) "thickness" / "E" / "nu", 3 nvc for "uhat", 0 for "F_solid" / "density"; rowptr has
+ *   nvc*nel + 1 entries, the columns of a row follow the cell's local order (not sorted).  nnz must be the count
+ *   femo_field_output_jacobian_nnz returns.
+ * femo_field_total_gradients: total derivatives of g_k = cbar_k . field through the solved state, for nbar cotangents:
+ *   lambda_k = K^-1 (d field / d w)^T cbar_k (one grouped multi-right-hand-side solve, strong-BC rows masked, as in
+ *   femo_total_gradients), out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k (nbar x n); iters, relres:
+ *   nbar entries or NULL. */
+int femo_field_output_vjp(femo_ctx* ctx, const char* name, const char* wrt, const double* cbar, int64_t nbar, double* out, int64_t n);
+int femo_field_output_jacobian_nnz(femo_ctx* ctx, const char* name, const char* wrt, int64_t* nnz);
+int femo_field_output_jacobian(femo_ctx* ctx, const char* name, const char* wrt, int64_t* rowptr, int32_t* colidx, double* vals,
+                               int64_t nnz);
+int femo_field_total_gradients(femo_ctx* ctx, const char* name, int32_t nbar, const double* cbar, const char* arg, double* out,
+                               int64_t n, int32_t* iters, double* relres);
 /* Scalar outputs for the stored state and fields: "compliance", "mass", "elastic_energy", "pnorm_stress", "volume",
  * "regularization" (the thickness term of the compliance, rm_shell_pde.py:64-83), and over the selected sub-domain
  * (femo_select_subdomain; the whole mesh if none) "tip_disp" = 0.5 int u.u J, "area" = int J (rm_shell_pde.py:95-105) and
