@@ -376,6 +376,35 @@ class ShellContext:
         self._chk(self.lib.femo_newmark_residual_T(self._h, int(levels), dptr(g), dptr(dF.ravel())))
         return g, dF
 
+    def newmark_adjoint_seeded(self, levels):
+        """The backward sweep of ``newmark_adjoint`` from the seed a device producer left behind (``newmark_stress_history_grad(..,
+        seed_adjoint=True)``); the adjoint history stays on the device."""
+        self._chk(self.lib.femo_newmark_adjoint_seeded(self._h, int(levels)))
+
+    def _stress_history_arg(self, levels, H):
+        if H is None:
+            return None, None
+        H = np.ascontiguousarray(np.asarray(H, dtype=np.float64).reshape(levels, self.ndof))
+        return H, dptr(H.ravel())
+
+    def newmark_stress_history(self, levels, H=None):
+        """(S, [P_i]) of the space-time p-norm stress aggregate: H (levels, ndof) level-major, or None for the history of the last march
+        (read in place).  m, rho, alpha and the regularisation are the settings of the static p-norm."""
+        keep, hp = self._stress_history_arg(levels, H)
+        per = np.empty(int(levels)); tot = C.c_double()
+        self._chk(self.lib.femo_newmark_stress_history(self._h, int(levels), hp, dptr(per), C.byref(tot)))
+        return tot.value, per
+
+    def newmark_stress_history_grad(self, levels, H=None, want_G=True, seed_adjoint=False):
+        """(dS/dt, dS/dW as (levels, ndof) or None).  ``seed_adjoint``: dS/dW is also left in the adjoint seed buffer for
+        ``newmark_adjoint_seeded``."""
+        keep, hp = self._stress_history_arg(levels, H)
+        g = np.empty(self.field_size("thickness"))
+        G = np.empty((int(levels), self.ndof)) if want_G else None
+        self._chk(self.lib.femo_newmark_stress_history_grad(self._h, int(levels), hp, dptr(g), None if G is None else dptr(G.ravel()),
+                                                            int(bool(seed_adjoint))))
+        return g, G
+
     def newmark_jvp(self, levels, dY=None, dthickness=None, dF=None):
         """[J dY + (dR/dt) dthickness + (dR/df) dF] as a (levels, ndof) array (forward mode of the whole-history residual)."""
         a = None if dY is None else np.ascontiguousarray(np.asarray(dY, dtype=np.float64).reshape(levels, self.ndof))

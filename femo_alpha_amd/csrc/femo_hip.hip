@@ -7,6 +7,7 @@
 #include "shape_sens.h"
 #include "stress.h"
 #include "stress_grad.h"
+#include "stress_history.h"
 #include "csr_map.h"
 
 #include <hip/hip_runtime.h>
@@ -99,6 +100,12 @@ struct femo_ctx {
         double *W = nullptr, *Fh = nullptr, *wdot = nullptr, *Fsw = nullptr, *mu0 = nullptr, *mu1 = nullptr, *Lam = nullptr, *Gh = nullptr;
         bool has_sw = false;
     } nm;
+    // space-time stress aggregate (femo_newmark_stress_history*): an uploaded history of its own (never nm.W) and the scratch of a
+    // level chunk, grown on demand and kept; capacities in doubles
+    struct StressHist {
+        double *H = nullptr, *ybuf = nullptr, *tbuf = nullptr, *acc = nullptr, *bsum = nullptr, *lev = nullptr, *stage = nullptr, *tout = nullptr;
+        size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    } sh;
     // CSR assembly
     long long csr_ncontrib = 0; int csr_nnz = 0;
     int *csr_perm = nullptr, *csr_dest = nullptr, *csr_rowptr = nullptr, *csr_colidx = nullptr;
@@ -217,6 +224,8 @@ struct femo_ctx {
         // 1e-4 / 1e-3 / 3e-3 / 1e-2 (L2: 0.58 of that) against 20.0 ms re-factorised -- the break-even sits at ~2.5e-3
         double stale_rel = 2e-3;
         int sweep_read_mode = 0;              // how a fused sweep reads what other workgroups of the launch wrote: 0 returning atomic, 1 agent-scope load, 2 plain (experiment)
+        int sh_levels_per_thread = 0;         // femo_newmark_stress_history*: levels one thread evaluates (0: enough level groups for ~2048 workgroups)
+        int sh_chunk = 0;                     // ... levels whose per-cell element vectors share the scratch at a time (0: as many as fit in 128 MB)
     } opt;
     // solver
     int precond = 0;
@@ -2175,7 +2184,8 @@ void femo_destroy(femo_ctx* c) {
     hipSetDevice(c->device);
     hipDeviceSynchronize();                   // stream2 / stream3 may still hold work that reads the buffers freed below
     if (c->gdir) hipFree(c->gdir);
-    void* nptrs[] = {c->nm.W, c->nm.Fh, c->nm.wdot, c->nm.Fsw, c->nm.mu0, c->nm.mu1, c->nm.Lam, c->nm.Gh};
+    void* nptrs[] = {c->nm.W, c->nm.Fh, c->nm.wdot, c->nm.Fsw, c->nm.mu0, c->nm.mu1, c->nm.Lam, c->nm.Gh,
+                     c->sh.H, c->sh.ybuf, c->sh.tbuf, c->sh.acc, c->sh.bsum, c->sh.lev, c->sh.stage, c->sh.tout};
     for (void* p : nptrs)
         if (p) hipFree(p);
     void* mptrs[] = {c->mr_v, c->mr_y, c->mr_work, c->mr_scal, c->mr_io};
@@ -2572,6 +2582,8 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "apply_lanes") { if (v != 0 && v != 4 && v != 5) return fail(c, "apply_lanes: 0 or 4 (a quad of lanes per element), or 5"); o.apply_lanes = v; }
     else if (k == "sweep_ahead") { if (v < 0) return fail(c, "sweep_ahead: number of top levels left to the solve (0: off)"); o.sweep_ahead = v; }
     else if (k == "stale_rel") { if (!(value >= 0)) return fail(c, "stale_rel: a relative change >= 0"); o.stale_rel = value; }
+    else if (k == "stress_history_levels_per_thread") { if (v < 0) return fail(c, "stress_history_levels_per_thread: >= 0 (0: automatic)"); o.sh_levels_per_thread = v; }
+    else if (k == "stress_history_chunk") { if (v < 0) return fail(c, "stress_history_chunk: >= 0 levels (0: automatic)"); o.sh_chunk = v; }
     else if (k == "stale_factor") { if (v < 0) return fail(c, "stale_factor: PCG iterations a kept factor is given before the factorisation is refreshed (0: never keep)"); o.stale_factor = v; }
     else if (k == "sweep_read_mode") { if (v < 0 || v > 2) return fail(c, "sweep_read_mode: 0 returning atomic, 1 agent-scope load, 2 plain load (experiment)"); o.sweep_read_mode = v; }
     else if (k == "swork_slots") { if (c->fr.ready || v < 1) return fail(c, "swork_slots >= 1, before femo_set_frontal_plan"); o.swork_slots = v; }
@@ -3818,19 +3830,16 @@ int femo_newmark_set_history(femo_ctx* c, int32_t which, const double* H) {     
 //   mu_i = b M lam_{i+1} - mu_{i+1},   A lam_i = G_i + b mu_i + (a M - K/2) lam_{i+1} - b mu_{i+1},   lam_0 = G_0 + (a M - K/2) lam_1 - b mu_1
 // (the O(T) form of state_operation_dynamic.py:619-691).  G: (levels x ndof) level-major, host; the result stays on the device
 // (femo_newmark_get_history(ctx, 2, ..)) for femo_newmark_residual_T.
-int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
-    HIPCHK(c, hipSetDevice(c->device));
+// the backward sweep from the seed G already in nm.Gh (levels x ndof, level-major) -- shared by femo_newmark_adjoint and
+// femo_newmark_adjoint_seeded, so that both give the same bits for the same G
+static int newmark_adjoint_sweep(femo_ctx* c, int32_t levels) {
     auto& nm = c->nm;
-    if (!nm.ready) return fail(c, "call femo_newmark_setup first");
-    if (levels < 1 || levels > nm.levels) return fail(c, "bad number of levels");
     const int64_t n = c->ndof;
     const int vg = vec_grid(n);
     const unsigned char* mask = c->has_mask ? c->mask : nullptr;
     const size_t hb = (size_t)nm.levels * n * sizeof(double);
     if (!nm.Lam) HIPCHK(c, hipMalloc((void**)&nm.Lam, hb));
-    if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, hb));
     HIPCHK(c, hipMemsetAsync(nm.Lam, 0, hb, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nm.Gh, G, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(nm.mu0, 0, (size_t)n * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->lam, 0, (size_t)n * sizeof(double), c->stream));
     double *mu_next = nm.mu0, *mu_i = nm.mu1;
@@ -3849,6 +3858,28 @@ int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& nm = c->nm;
+    if (!nm.ready) return fail(c, "call femo_newmark_setup first");
+    if (levels < 1 || levels > nm.levels) return fail(c, "bad number of levels");
+    const int64_t n = c->ndof;
+    const size_t hb = (size_t)nm.levels * n * sizeof(double);
+    if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, hb));
+    HIPCHK(c, hipMemcpyAsync(nm.Gh, G, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return newmark_adjoint_sweep(c, levels);
+}
+
+// the same sweep from the seed a device producer left in nm.Gh (femo_newmark_stress_history_grad(.., seed_adjoint = 1)): no host copy
+int femo_newmark_adjoint_seeded(femo_ctx* c, int32_t levels) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& nm = c->nm;
+    if (!nm.ready) return fail(c, "call femo_newmark_setup first");
+    if (levels < 1 || levels > nm.levels) return fail(c, "bad number of levels");
+    if (!nm.Gh) return fail(c, "femo_newmark_adjoint_seeded: no seed in the adjoint seed buffer");
+    return newmark_adjoint_sweep(c, levels);
 }
 
 // g_t (thickness length) = sum_i lam_i^T [ K'/2 (w_i + w_{i-1}) + M' (a (w_i - w_{i-1}) - b wdot_{i-1}) ],
@@ -4007,6 +4038,131 @@ int femo_newmark_tangent(femo_ctx* c, const double* dR, int32_t levels) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+
+// ---- space-time p-norm stress aggregate of the transient path (stress_history.h): S = sum_i P_i, P_i = PlateSim.pnorm_stress(level=i)
+// of femo_alpha/dynamic_rm_shell/plate_sim.py:427-449, the constraint the gust examples leave commented out
+// (ex_gust_response_opt.py:320,329,724; ex_lpc_gust_response_opt.py:49,55,445).  m, rho, alpha and the regularisation coefficient are
+// the static path's settings (femo_set_stress_params, femo_set_stress_alpha(sel = -1), option "stress_regularization").
+static int sh_grow(femo_ctx* c, int k, double** p, size_t n) {
+    size_t& cap = c->sh.cap[k];
+    if (cap >= n && *p) return 0;
+    if (*p) hipFree(*p);
+    *p = nullptr; cap = 0;
+    HIPCHK(c, hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(double)));
+    cap = n;
+    return 0;
+}
+
+// per_level (host, levels; may be null), total (host; may be null).  grad: g_t (host, thickness length; may be null) = dS/dt;
+// dS/dW level-major into nm.Gh (seed) and / or the host array G (may be null).  The level chunks of the gradient share one scratch.
+static int stress_history_run(femo_ctx* c, int32_t levels, const double* H, bool grad, double* per_level, double* total, double* g_t,
+                              double* G, bool seed) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& nm = c->nm;
+    auto& sh = c->sh;
+    if (levels < 1) return fail(c, "stress history: levels must be >= 1");
+    if ((!H || seed) && !nm.ready) return fail(c, "stress history: call femo_newmark_setup first");
+    if ((!H || seed) && levels > nm.levels) return fail(c, "stress history: more levels than femo_newmark_setup allocated");
+    const int64_t n = c->ndof;
+    const double* Hd = nm.W;
+    if (H) {               // the caller's history goes to a buffer of its own: nm.W stays the march's (femo_newmark_residual_T reads it)
+        if (sh_grow(c, 0, &sh.H, (size_t)levels * n)) return 1;
+        HIPCHK(c, hipMemcpyAsync(sh.H, H, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        Hd = sh.H;
+    }
+    if (stress_alpha_ref(c) < 0) { double v[2]; if (pnorm_dev(c, v)) return 1; }
+    const double alpha = stress_alpha_ref(c);
+    const int nel = c->nel, nvc = c->nvc;
+    const int nbx = nblk(nel, EB);
+    const int fill = std::max(1, (2048 + nbx - 1) / nbx);          // level groups that put ~2048 workgroups in flight
+    const size_t lev_doubles = (size_t)nel * YSTRIDE;
+    int chunk = levels;
+    if (grad) chunk = c->opt.sh_chunk > 0 ? c->opt.sh_chunk : (int)std::max<size_t>(1, ((size_t)128 << 20) / (lev_doubles * sizeof(double)));
+    chunk = std::min(chunk, (int)levels);
+    auto lpg_of = [&](int nlev) { return c->opt.sh_levels_per_thread > 0 ? c->opt.sh_levels_per_thread : std::max(1, (nlev + fill - 1) / fill); };
+    if (sh_grow(c, 4, &sh.bsum, (size_t)levels * nbx) || sh_grow(c, 5, &sh.lev, (size_t)levels)) return 1;
+    double* gdst = nullptr;
+    if (grad) {
+        if (sh_grow(c, 1, &sh.ybuf, (size_t)chunk * lev_doubles) || sh_grow(c, 2, &sh.tbuf, (size_t)chunk * nel * nvc) ||      // at most `chunk` level groups
+            sh_grow(c, 3, &sh.acc, (size_t)nel * nvc) || sh_grow(c, 7, &sh.tout, (size_t)std::max<int64_t>(c->nT, 1)))
+            return 1;
+        if (seed) {
+            if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, (size_t)nm.levels * n * sizeof(double)));
+            gdst = nm.Gh;
+        } else if (G) {
+            if (sh_grow(c, 6, &sh.stage, (size_t)chunk * n)) return 1;
+        }
+    }
+    const MeshDev m = mesh_dev(c);
+    const FieldsDev f = fields_dev(c);
+    const int gthreads = c->nP2 + c->nghost;
+    for (int l0 = 0; l0 < levels; l0 += chunk) {
+        const int nlev = std::min(chunk, (int)levels - l0);
+        const int lpg = lpg_of(nlev), ng = (nlev + lpg - 1) / lpg;
+        const dim3 grid(nbx, ng);
+        if (!grad) {
+            ELEM_LAUNCH(c, k_stress_history, COMMA_FALSE, grid, EB, m, f, c->tab_s, c->eorder, Hd, (int64_t)n, l0, nlev, lpg,
+                        c->stress_m, c->stress_rho, 1.0 / alpha, c->stress_reg, sh.bsum, sh.ybuf, sh.tbuf);
+            continue;
+        }
+        ELEM_LAUNCH(c, k_stress_history, COMMA_TRUE, grid, EB, m, f, c->tab_s, c->eorder, Hd, (int64_t)n, l0, nlev, lpg,
+                    c->stress_m, c->stress_rho, 1.0 / alpha, c->stress_reg, sh.bsum, sh.ybuf, sh.tbuf);
+        const int64_t tl = (int64_t)nel * nvc;
+        hipLaunchKernelGGL(k_hist_group_sum, dim3(nblk(tl, 256)), dim3(256), 0, c->stream, tl, ng, l0 == 0 ? 1 : 0, (const double*)sh.tbuf, sh.acc);
+        double* dst = seed ? gdst + (size_t)l0 * n : G ? sh.stage : nullptr;
+        if (dst) {
+            const dim3 gg(nblk(gthreads, 256), nlev);
+#define HIST_GATHER(NPC_, NVC_) hipLaunchKernelGGL((k_hist_gather<NPC_, NVC_>), gg, dim3(256), 0, c->stream, c->nP2, c->nn, nel, c->ndof_u, \
+                                                   c->ndof, c->n2e_off, c->n2e_ent, (const double*)sh.ybuf, dst, c->cr ? 1 : 0, c->nrot)
+            if (c->cg1) { if (c->quad) HIST_GATHER(4, 4); else HIST_GATHER(3, 3); }
+            else if (c->quad) HIST_GATHER(9, 4);
+            else HIST_GATHER(6, 3);
+#undef HIST_GATHER
+            HIPCHK(c, hipGetLastError());
+            if (G) HIPCHK(c, hipMemcpyAsync(G + (size_t)l0 * n, dst, (size_t)nlev * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    hipLaunchKernelGGL(k_hist_level_sums, dim3(nblk(levels, 256)), dim3(256), 0, c->stream, (int)levels, nbx, (const double*)sh.bsum, sh.lev);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> lv(levels);
+    HIPCHK(c, hipMemcpyAsync(lv.data(), sh.lev, (size_t)levels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (grad && g_t) {
+        if (c->ewm) hipLaunchKernelGGL(k_hist_cell_pick, dim3(nblk(nel, 256)), dim3(256), 0, c->stream, nel, nvc, (const double*)sh.acc, sh.tout);
+        else hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(c->nn, 256)), dim3(256), 0, c->stream, c->nn, 1, c->v2e_off, c->v2e_ent,
+                                (const double*)sh.acc, sh.tout);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(g_t, sh.tout, (size_t)c->nT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double s = 0.0;
+    for (int l = 0; l < levels; ++l) {
+        lv[l] /= alpha;
+        if (!std::isfinite(lv[l])) {
+            char buf[320];
+            snprintf(buf, sizeof buf, "stress history: the p-norm of level %d is not finite for m = %g, rho = %g -- (m vm)^rho overflows; "
+                     "lower m so that m vm stays near 1", l, c->stress_m, c->stress_rho);
+            return fail(c, buf);
+        }
+        s += lv[l];
+    }
+    if (!std::isfinite(s)) {
+        char buf[320];
+        snprintf(buf, sizeof buf, "stress history: the sum over %d levels is not finite for m = %g, rho = %g -- lower m", (int)levels,
+                 c->stress_m, c->stress_rho);
+        return fail(c, buf);
+    }
+    if (per_level) std::memcpy(per_level, lv.data(), (size_t)levels * sizeof(double));
+    if (total) *total = s;
+    return 0;
+}
+
+int femo_newmark_stress_history(femo_ctx* c, int32_t levels, const double* H, double* per_level, double* total) {
+    return stress_history_run(c, levels, H, false, per_level, total, nullptr, nullptr, false);
+}
+
+int femo_newmark_stress_history_grad(femo_ctx* c, int32_t levels, const double* H, double* g_thickness, double* G, int seed_adjoint) {
+    return stress_history_run(c, levels, H, true, nullptr, nullptr, g_thickness, G, seed_adjoint != 0);
 }
 
 // ---- CSR assembly of the elastic stiffness (what assembleMatrix(dR_du) returns in the reference,

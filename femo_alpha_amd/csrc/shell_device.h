@@ -666,10 +666,9 @@ constexpr int YSTRIDE = 40;     // doubles per element slot of the element-resul
 // second pass of the element operator: y(node) = sum of the contributions of the elements around the node,
 // read through the inverted connectivity (n2e_off / n2e_ent = slot * NPC + local node); also clears ghosts
 template <int NPC, int NVC>
-__global__ void __launch_bounds__(256)
-k_gather_sum(int nP2, int nV, int ndof_u, int ndof, const int* __restrict__ n2e_off, const int* __restrict__ n2e_ent,
-             const double* __restrict__ ybuf, double* __restrict__ y, int cr, int nrot) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void gather_sum_node(int p, int nP2, int nV, int ndof_u, int ndof, const int* __restrict__ n2e_off,
+                                                const int* __restrict__ n2e_ent, const double* __restrict__ ybuf, double* __restrict__ y,
+                                                int cr, int nrot) {
     if (p < nP2) {
         double s0 = 0, s1 = 0, s2 = 0, t0 = 0, t1 = 0, t2 = 0;
         const int b = n2e_off[p], e = n2e_off[p + 1];
@@ -694,6 +693,13 @@ k_gather_sum(int nP2, int nV, int ndof_u, int ndof, const int* __restrict__ n2e_
         const int g = ndof_u + 3 * nrot + (p - nP2);    // ghost entries: no element touches them
         if (g < ndof) y[g] = 0.0;
     }
+}
+
+template <int NPC, int NVC>
+__global__ void __launch_bounds__(256)
+k_gather_sum(int nP2, int nV, int ndof_u, int ndof, const int* __restrict__ n2e_off, const int* __restrict__ n2e_ent,
+             const double* __restrict__ ybuf, double* __restrict__ y, int cr, int nrot) {
+    gather_sum_node<NPC, NVC>(blockIdx.x * blockDim.x + threadIdx.x, nP2, nV, ndof_u, ndof, n2e_off, n2e_ent, ybuf, y, cr, nrot);
 }
 
 // blocks that share an XCD (blockIdx % 8, observed round-robin placement -- a speed hint only) work on a

@@ -121,11 +121,12 @@ k_pnorm(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int mode, double
                 t.k00 = -z * t.e00; t.k11 = -z * t.e11; t.k01 = -z * t.g01;
                 t.ga0 = t.ga1 = t.om = 0.0;
                 strains_T_q<NPC, NVC>(*tab, q, g, t, ye);
-                // -1/2 b (x) gradx(h): b0 = -theta.E1, b1 = theta.E0
+                // -1/2 b (x) gradx(h): b0 = -theta.E1, b1 = theta.E0, theta = sum_b NR_b theta_b (NR: the rotation's shape function,
+                // which differs from N1 for CG2CR1)
                 const double cb0 = -0.5 * (t.e00 * ts.gh0 + t.g01 * ts.gh1), cb1 = -0.5 * (t.e11 * ts.gh1 + t.g01 * ts.gh0);
                 for (int b = 0; b < NVC; ++b)
                     for (int c = 0; c < 3; ++c)
-                        ye[3 * NPC + 3 * b + c] += tab->N1[q][b] * (-cb0 * g.E1[c] + cb1 * g.E0[c]);
+                        ye[3 * NPC + 3 * b + c] += tab->NR[q][b] * (-cb0 * g.E1[c] + cb1 * g.E0[c]);
             } else if (mode == 2) {
                 double de[3];
                 dvm_deps(sig, vm, Eq, nuq, de);

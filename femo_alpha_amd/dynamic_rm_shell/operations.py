@@ -1,5 +1,5 @@
 """Dynamic operators: ``StateOperation`` (whole displacement history as one implicit state),
-``TotalStrainEnergyOperation`` and ``VolumeOperation`` -- interfaces of
+``TotalStrainEnergyOperation``, ``StressHistoryOperation`` and ``VolumeOperation`` -- interfaces of
 femo_alpha/dynamic_rm_shell/state_operation_dynamic.py:20-137,141-706, total_strain_energy_operation.py:20-138
 and volume_operation.py:20-70.  Histories cross the boundary as vectors flattened column-major from
 (fe_dofs, time_levels) (dynamic_rm_shell/utils.py:9-16)."""
@@ -129,6 +129,45 @@ class TotalStrainEnergyOperation(csdl.CustomExplicitOperation):
             dEdw[:, i] = gw
         derivatives[self.output_name, "thickness"] = dEdt
         derivatives[self.output_name, "disp_history"] = stack_array_into_vector(dEdw)
+
+
+class StressHistoryOperation(csdl.CustomExplicitOperation):
+    """Space-time p-norm stress aggregate S = sum_i PlateSim.pnorm_stress(level=i) (plate_sim.py:427-449) of a displacement
+    history: the stress constraint of ex_gust_response_opt.py:320,329 and ex_lpc_gust_response_opt.py:49,55,445.  The history is
+    uploaded once per call into a buffer of its own; the march's resident history is left as it is."""
+
+    def __init__(self, plate_sim, m=1e-6, rho=100, alpha=None, regularization=False):
+        super().__init__()
+        csdl.check_parameter(plate_sim, "plate_sim")
+        self.plate_sim = plate_sim
+        self.m, self.rho, self.alpha, self.regularization = m, rho, alpha, regularization
+        self.args_dict = ["thickness", "disp_history"]
+        self.output_name = "pnorm_stress_history"
+
+    def evaluate(self, inputs):
+        _declare(self, inputs)
+        out = self.create_output(self.output_name, (1,))
+        out.add_name(self.output_name)
+        self.declare_derivative_parameters(self.output_name, "*", dependent=True)
+        _finish(self)
+        return out
+
+    def _settings(self):
+        return dict(m=self.m, rho=self.rho, alpha=self.alpha, regularization=self.regularization)
+
+    def compute(self, input_vals, output_vals):
+        ps = self.plate_sim
+        W = reshape_vector_into_array(np.asarray(input_vals["disp_history"]), ps.time_levels)
+        ps.update_t(input_vals["thickness"])
+        output_vals[self.output_name] = np.array([ps.pnorm_stress_history(W=W, **self._settings())])
+
+    def compute_derivatives(self, input_vals, output_vals, derivatives):
+        ps = self.plate_sim
+        W = reshape_vector_into_array(np.asarray(input_vals["disp_history"]), ps.time_levels)
+        ps.update_t(input_vals["thickness"])
+        g_t, g_w = ps.pnorm_stress_history_partials(W=W, **self._settings())
+        derivatives[self.output_name, "thickness"] = g_t
+        derivatives[self.output_name, "disp_history"] = stack_array_into_vector(g_w)
 
 
 class VolumeOperation(csdl.CustomExplicitOperation):

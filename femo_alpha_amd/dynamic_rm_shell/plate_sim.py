@@ -159,14 +159,61 @@ class PlateSim:
         if level is not None:
             self.ctx.set_state(self.W[level].cpu().numpy())
 
-    def pnorm_stress(self, m=1e-6, rho=100, alpha=None, regularization=False, level=None):
-        """1/alpha int (m vm_top)^rho dx over the degree-4 measure (plate_sim.py:427-444) for the state of time level
-        ``level`` (default: the state the context holds, i.e. the last level solved -- the reference's ``self.w``)."""
-        if regularization or alpha is not None:
-            raise NotImplementedError("only the reference's default call pattern (alpha=None, regularization=False) is provided")
-        self._level_state(level)
+    def _stress_settings(self, m, rho, alpha, regularization):
+        """m, rho, alpha (None: the area of the degree-4 measure) and the regularisation 0.5e3 int t^rho dx (plate_sim.py:438-441)
+        into the context; alpha and the coefficient are sent only when they change."""
         self.ctx.set_stress_params(m, rho)
+        alpha = None if alpha is None else float(alpha)
+        if alpha != getattr(self, "_stress_alpha", None):
+            self.ctx.set_stress_alpha(alpha)
+            self._stress_alpha = alpha
+        reg = 0.5e3 if regularization else 0.0
+        if reg != getattr(self, "_stress_reg", 0.0):
+            self.ctx.set_option("stress_regularization", reg)
+            self._stress_reg = reg
+
+    def pnorm_stress(self, m=1e-6, rho=100, alpha=None, regularization=False, level=None):
+        """1/alpha [int (m vm_top)^rho dx (+ 0.5e3 int t^rho dx)] over the degree-4 measure (plate_sim.py:427-444) for the state of
+        time level ``level`` (default: the state the context holds, i.e. the last level solved -- the reference's ``self.w``)."""
+        self._level_state(level)
+        self._stress_settings(m, rho, alpha, regularization)
         return self.ctx.functional("pnorm_stress")
+
+    # ------------------------------------------------------------------ space-time stress aggregate (femo_newmark_stress_history*)
+    def _history_arg(self, W):
+        """None (the history of the last march, read in place on the device) or a (fe_dofs, time_levels) history as level-major rows."""
+        if W is None:
+            self._newmark()
+            return None
+        W = np.asarray(W, dtype=np.float64).reshape(self.fe_dofs, self.time_levels)
+        return np.ascontiguousarray(W.T)
+
+    def pnorm_stress_history(self, m=1e-6, rho=100, alpha=None, regularization=False, per_level=False, W=None):
+        """S = sum over the time levels of pnorm_stress(level=i) (plate_sim.py:427-449), in one pass over the history; the max-stress
+        estimate follows as AggregatedStressModel(m, rho).evaluate(S).  ``per_level``: the T values P_i instead.  ``W``: a
+        (fe_dofs, time_levels) history (None: the last march's).  A P_i or S that overflows is an error (lower m)."""
+        self._stress_settings(m, rho, alpha, regularization)
+        S, P = self.ctx.newmark_stress_history(self.time_levels, self._history_arg(W))
+        return P if per_level else S
+
+    def pnorm_stress_history_partials(self, m=1e-6, rho=100, alpha=None, regularization=False, W=None):
+        """(dS/dt, dS/dW) of ``pnorm_stress_history``; dS/dW in the boundary layout (fe_dofs, time_levels)."""
+        self._stress_settings(m, rho, alpha, regularization)
+        g, G = self.ctx.newmark_stress_history_grad(self.time_levels, self._history_arg(W))
+        return g, G.T.copy(order="F")
+
+    def pnorm_stress_history_total_gradient(self, m=1e-6, rho=100, alpha=None, regularization=False):
+        """(dS/dt, dS/dF_history) through the transient adjoint, for the history of the last march.  The history gradient seeds the
+        adjoint on the device (femo_newmark_adjoint_seeded), the residual products follow (self weight as residual_T_products
+        treats it): dS/dt = dS/dt|_W - sum_i (dR_i/dt)^T lam_i, dS/dF = -[(dR_i/df)^T lam_i]_i, (time_levels, 3 nn)."""
+        self._newmark()
+        self._stress_settings(m, rho, alpha, regularization)
+        T = self.time_levels
+        g_part, _ = self.ctx.newmark_stress_history_grad(T, None, want_G=False, seed_adjoint=True)
+        self.ctx.newmark_adjoint_seeded(T)
+        self.Lam = self.ctx.newmark_tensor(2)
+        g_t, dF = self.residual_T_products()
+        return g_part - g_t, -dF
 
     def von_Mises_stress(self, level=None):
         """Top-surface von Mises stress of one time level as a DG1 field, nvc values per cell (plate_sim.py:446-450)."""

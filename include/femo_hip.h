@@ -399,6 +399,22 @@ int femo_newmark_get_history(femo_ctx* ctx, int32_t which, double* out);        
 int femo_newmark_set_history(femo_ctx* ctx, int32_t which, const double* H);   /* which: 0 displacements, 2 adjoint */
 int femo_newmark_adjoint(femo_ctx* ctx, const double* G, int32_t levels);       /* (dR/dy)^T Lambda = G, O(T) recursion */
 int femo_newmark_residual_T(femo_ctx* ctx, int32_t levels, double* g_thickness, double* dF);
+/* The O(T) recursion of femo_newmark_adjoint run from the seed already in the adjoint seed buffer (left there by
+ * femo_newmark_stress_history_grad(.., seed_adjoint = 1)), with no host copy.  The same seed gives the same bits as
+ * femo_newmark_adjoint. */
+int femo_newmark_adjoint_seeded(femo_ctx* ctx, int32_t levels);
+/* Space-time p-norm stress aggregate of the transient path: S = sum_{i < levels} P_i, P_i = 1/alpha [int (m vm_top(w_i))^rho dx_4
+ * + regc int t^rho dx_4], i.e. the sum over the time levels of the reference's PlateSim.pnorm_stress(level=i)
+ * (dynamic_rm_shell/plate_sim.py:427-449) -- the stress constraint ex_gust_response_opt.py:320,329,724 and
+ * ex_lpc_gust_response_opt.py:49,55,445 leave commented out.  m, rho: femo_set_stress_params; alpha: femo_set_stress_alpha(sel = -1)
+ * (default the area of the degree-4 measure); regc: option "stress_regularization".  H: the history, (levels x ndof) level-major, or
+ * NULL for the one of the last march, read in place.  A given H goes to a buffer of its own: the resident displacement history is
+ * never written.  per_level (levels entries) and total may be NULL.  A P_i or S that is not finite is an error naming m and rho.
+ * femo_newmark_stress_history_grad: g_thickness = dS/dt (thickness length; may be NULL), G = dS/dW (levels x ndof, level-major; may be
+ * NULL); seed_adjoint != 0 leaves dS/dW in the adjoint seed buffer for femo_newmark_adjoint_seeded.  No float atomics: the results
+ * repeat bit for bit. */
+int femo_newmark_stress_history(femo_ctx* ctx, int32_t levels, const double* H, double* per_level, double* total);
+int femo_newmark_stress_history_grad(femo_ctx* ctx, int32_t levels, const double* H, double* g_thickness, double* G, int seed_adjoint);
 /* Forward mode (state_operation_dynamic.py:228-329: compute_jacvec_product fwd; :534-605: apply_inverse_jacobian fwd, the
  * "tangent linear model").  Results land in the adjoint-history buffer (femo_newmark_get_history(ctx, 2, ..)). */
 int femo_newmark_jvp(femo_ctx* ctx, int32_t levels, const double* dY, const double* dthickness, const double* dF);
