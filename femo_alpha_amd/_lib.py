@@ -124,6 +124,10 @@ SIGNATURES = {
     "femo_newmark_adjoint_seeded": (C.c_int, [C.c_void_p, C.c_int32]),
     "femo_newmark_stress_history": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "femo_newmark_stress_history_grad": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p, C.c_int]),
+    "femo_newmark_disp_aggregate": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, C.c_int32, C.c_double, C.c_double, _c_double_p,
+                                              _c_double_p]),
+    "femo_newmark_disp_aggregate_grad": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, C.c_int32, C.c_double, C.c_double, _c_double_p,
+                                                   _c_double_p, C.c_int]),
     "femo_newmark_jvp": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "femo_newmark_tangent": (C.c_int, [C.c_void_p, _c_double_p, C.c_int32]),
     "femo_newmark_ptr": (C.c_void_p, [C.c_void_p, C.c_int32]),

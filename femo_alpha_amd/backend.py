@@ -378,7 +378,7 @@ class ShellContext:
 
     def newmark_adjoint_seeded(self, levels):
         """The backward sweep of ``newmark_adjoint`` from the seed a device producer left behind (``newmark_stress_history_grad(..,
-        seed_adjoint=True)``); the adjoint history stays on the device."""
+        seed_adjoint=True)``, ``newmark_disp_aggregate_grad(.., seed_adjoint=True)``); the adjoint history stays on the device."""
         self._chk(self.lib.femo_newmark_adjoint_seeded(self._h, int(levels)))
 
     def _stress_history_arg(self, levels, H):
@@ -404,6 +404,33 @@ class ShellContext:
         self._chk(self.lib.femo_newmark_stress_history_grad(self._h, int(levels), hp, dptr(g), None if G is None else dptr(G.ravel()),
                                                             int(bool(seed_adjoint))))
         return g, G
+
+    @staticmethod
+    def _disp_components(components):
+        try:
+            return {"all": 0, "translations": 1}[components]
+        except (KeyError, TypeError):
+            raise ValueError(f'components must be "all" or "translations", got {components!r}') from None
+
+    def newmark_disp_aggregate(self, levels, rho, scaler=1.0, components="all", H=None):
+        """(M, [M_i]) of the max-displacement KS aggregate M = KS_rho(|s| |W|) / s (include/femo_hip.h): H (levels, ndof) level-major,
+        or None for the history of the last march (read in place).  components: "all" or "translations"."""
+        keep, hp = self._stress_history_arg(levels, H)
+        per = np.empty(int(levels)); tot = C.c_double()
+        self._chk(self.lib.femo_newmark_disp_aggregate(self._h, int(levels), hp, self._disp_components(components), float(rho),
+                                                       float(scaler), dptr(per), C.byref(tot)))
+        return tot.value, per
+
+    def newmark_disp_aggregate_grad(self, levels, rho, scaler=1.0, components="all", H=None, want_G=True, seed_adjoint=False):
+        """(M, dM/dW as (levels, ndof) or None).  ``seed_adjoint``: dM/dW is also left in the adjoint seed buffer for
+        ``newmark_adjoint_seeded``."""
+        keep, hp = self._stress_history_arg(levels, H)
+        tot = C.c_double()
+        G = np.empty((int(levels), self.ndof)) if want_G else None
+        self._chk(self.lib.femo_newmark_disp_aggregate_grad(self._h, int(levels), hp, self._disp_components(components), float(rho),
+                                                            float(scaler), C.byref(tot), None if G is None else dptr(G.ravel()),
+                                                            int(bool(seed_adjoint))))
+        return tot.value, G
 
     def newmark_jvp(self, levels, dY=None, dthickness=None, dF=None):
         """[J dY + (dR/dt) dthickness + (dR/df) dF] as a (levels, ndof) array (forward mode of the whole-history residual)."""

@@ -8,6 +8,7 @@
 #include "stress.h"
 #include "stress_grad.h"
 #include "stress_history.h"
+#include "disp_history.h"
 #include "csr_map.h"
 
 #include <hip/hip_runtime.h>
@@ -100,11 +101,12 @@ struct femo_ctx {
         double *W = nullptr, *Fh = nullptr, *wdot = nullptr, *Fsw = nullptr, *mu0 = nullptr, *mu1 = nullptr, *Lam = nullptr, *Gh = nullptr;
         bool has_sw = false;
     } nm;
-    // space-time stress aggregate (femo_newmark_stress_history*): an uploaded history of its own (never nm.W) and the scratch of a
-    // level chunk, grown on demand and kept; capacities in doubles
+    // space-time stress aggregate (femo_newmark_stress_history*) and max-displacement aggregate (femo_newmark_disp_aggregate*): an
+    // uploaded history of their own (never nm.W) and the scratch of a level chunk, grown on demand and kept; capacities in doubles
     struct StressHist {
         double *H = nullptr, *ybuf = nullptr, *tbuf = nullptr, *acc = nullptr, *bsum = nullptr, *lev = nullptr, *stage = nullptr, *tout = nullptr;
-        size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        double *kpart = nullptr, *kres = nullptr;       // KS block pairs and per-level / total results of the displacement aggregate
+        size_t cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     } sh;
     // CSR assembly
     long long csr_ncontrib = 0; int csr_nnz = 0;
@@ -226,6 +228,7 @@ struct femo_ctx {
         int sweep_read_mode = 0;              // how a fused sweep reads what other workgroups of the launch wrote: 0 returning atomic, 1 agent-scope load, 2 plain (experiment)
         int sh_levels_per_thread = 0;         // femo_newmark_stress_history*: levels one thread evaluates (0: enough level groups for ~2048 workgroups)
         int sh_chunk = 0;                     // ... levels whose per-cell element vectors share the scratch at a time (0: as many as fit in 128 MB)
+        int dh_chunk = 0;                     // femo_newmark_disp_aggregate_grad: levels staged at a time for a host G (0: as many as fit in 128 MB)
     } opt;
     // solver
     int precond = 0;
@@ -2185,7 +2188,8 @@ void femo_destroy(femo_ctx* c) {
     hipDeviceSynchronize();                   // stream2 / stream3 may still hold work that reads the buffers freed below
     if (c->gdir) hipFree(c->gdir);
     void* nptrs[] = {c->nm.W, c->nm.Fh, c->nm.wdot, c->nm.Fsw, c->nm.mu0, c->nm.mu1, c->nm.Lam, c->nm.Gh,
-                     c->sh.H, c->sh.ybuf, c->sh.tbuf, c->sh.acc, c->sh.bsum, c->sh.lev, c->sh.stage, c->sh.tout};
+                     c->sh.H, c->sh.ybuf, c->sh.tbuf, c->sh.acc, c->sh.bsum, c->sh.lev, c->sh.stage, c->sh.tout,
+                     c->sh.kpart, c->sh.kres};
     for (void* p : nptrs)
         if (p) hipFree(p);
     void* mptrs[] = {c->mr_v, c->mr_y, c->mr_work, c->mr_scal, c->mr_io};
@@ -2584,6 +2588,7 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "stale_rel") { if (!(value >= 0)) return fail(c, "stale_rel: a relative change >= 0"); o.stale_rel = value; }
     else if (k == "stress_history_levels_per_thread") { if (v < 0) return fail(c, "stress_history_levels_per_thread: >= 0 (0: automatic)"); o.sh_levels_per_thread = v; }
     else if (k == "stress_history_chunk") { if (v < 0) return fail(c, "stress_history_chunk: >= 0 levels (0: automatic)"); o.sh_chunk = v; }
+    else if (k == "disp_history_chunk") { if (v < 0) return fail(c, "disp_history_chunk: >= 0 levels (0: automatic)"); o.dh_chunk = v; }
     else if (k == "stale_factor") { if (v < 0) return fail(c, "stale_factor: PCG iterations a kept factor is given before the factorisation is refreshed (0: never keep)"); o.stale_factor = v; }
     else if (k == "sweep_read_mode") { if (v < 0 || v > 2) return fail(c, "sweep_read_mode: 0 returning atomic, 1 agent-scope load, 2 plain load (experiment)"); o.sweep_read_mode = v; }
     else if (k == "swork_slots") { if (c->fr.ready || v < 1) return fail(c, "swork_slots >= 1, before femo_set_frontal_plan"); o.swork_slots = v; }
@@ -4163,6 +4168,101 @@ int femo_newmark_stress_history(femo_ctx* c, int32_t levels, const double* H, do
 
 int femo_newmark_stress_history_grad(femo_ctx* c, int32_t levels, const double* H, double* g_thickness, double* G, int seed_adjoint) {
     return stress_history_run(c, levels, H, true, nullptr, nullptr, g_thickness, G, seed_adjoint != 0);
+}
+
+// ---- max-displacement aggregate of the transient path (disp_history.h): M = KS_rho(|s| |W|) / s over the whole history, the lpc
+// example's max_disp = csdl.maximum(csdl.absolute(s W), rho) / s (ex_lpc_gust_response_opt.py:457-459, 770-772).
+// per_level (host, levels; may be null): M_l over level l alone; total (host; may be null).  grad: dM/dW level-major into nm.Gh (seed)
+// and / or the host array G (may be null), staged one chunk of levels at a time.
+static int disp_history_run(femo_ctx* c, int32_t levels, const double* H, int32_t components, double rho, double scaler, bool grad,
+                            double* per_level, double* total, double* G, bool seed) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& nm = c->nm;
+    auto& sh = c->sh;
+    if (levels < 1) return fail(c, "disp aggregate: levels must be >= 1");
+    char msg[256];
+    if (!(rho > 0.0) || !std::isfinite(rho)) {
+        snprintf(msg, sizeof msg, "disp aggregate: rho must be finite and > 0, got rho = %g", rho);
+        return fail(c, msg);
+    }
+    if (scaler == 0.0 || !std::isfinite(scaler)) {
+        snprintf(msg, sizeof msg, "disp aggregate: scaler must be finite and non-zero, got scaler = %g", scaler);
+        return fail(c, msg);
+    }
+    if (components != 0 && components != 1) return fail(c, "disp aggregate: components must be 0 (all entries) or 1 (translations)");
+    if ((!H || seed) && !nm.ready) return fail(c, "disp aggregate: call femo_newmark_setup first");
+    if ((!H || seed) && levels > nm.levels) return fail(c, "disp aggregate: more levels than femo_newmark_setup allocated");
+    const int64_t n = c->ndof, ncols = components == 1 ? (int64_t)c->ndof_u : n;
+    const double* Hd = nm.W;
+    if (H) {               // the caller's history goes to the buffer of its own: nm.W stays the march's
+        if (sh_grow(c, 0, &sh.H, (size_t)levels * n)) return 1;
+        HIPCHK(c, hipMemcpyAsync(sh.H, H, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        Hd = sh.H;
+    }
+    const bool vec = (n & 1) == 0;                 // rows of an even length start 16-byte aligned: pairs of entries per load
+    const int64_t items = vec ? ncols / 2 : ncols;
+    // ~4096 workgroups over all levels, none with fewer than 256 items
+    const int nbx = (int)std::max<int64_t>(1, std::min<int64_t>((4096 + levels - 1) / levels, (items + 255) / 256));
+    if (sh_grow(c, 8, &sh.kpart, (size_t)levels * nbx * 3) || sh_grow(c, 9, &sh.kres, (size_t)4 * levels + 2)) return 1;
+    const double cu = rho * std::fabs(scaler);
+    if (vec) hipLaunchKernelGGL(k_disp_ks_partial<true>, dim3(nbx, levels), dim3(256), 0, c->stream, Hd, n, ncols, cu, sh.kpart);
+    else hipLaunchKernelGGL(k_disp_ks_partial<false>, dim3(nbx, levels), dim3(256), 0, c->stream, Hd, n, ncols, cu, sh.kpart);
+    hipLaunchKernelGGL(k_disp_ks_combine, dim3(1), dim3(256), 0, c->stream, (int)levels, nbx, (const double*)sh.kpart, sh.kres);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> res((size_t)4 * levels + 2);
+    HIPCHK(c, hipMemcpyAsync(res.data(), sh.kres, res.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int l = 0; l < levels; ++l)
+        if (res[levels + l] != 0.0) {
+            snprintf(msg, sizeof msg, "disp aggregate: the history holds %.0f non-finite entries at level %d", res[levels + l], l);
+            return fail(c, msg);
+        }
+    const double inv = 1.0 / (rho * scaler);
+    const double tot = res[4 * levels] * inv;
+    if (!std::isfinite(tot)) {
+        snprintf(msg, sizeof msg, "disp aggregate: rho |scaler| |w| overflows for rho = %g, scaler = %g -- lower rho or scaler", rho, scaler);
+        return fail(c, msg);
+    }
+    if (grad) {
+        const int chunk = seed ? (int)levels : std::min<int>(levels, c->opt.dh_chunk > 0 ? c->opt.dh_chunk
+                                                                  : (int)std::max<int64_t>(1, ((int64_t)128 << 20) / (n * (int64_t)sizeof(double))));
+        double* dst = nullptr;
+        if (seed) {
+            if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, (size_t)nm.levels * n * sizeof(double)));
+            dst = nm.Gh;
+        } else if (G) {
+            if (sh_grow(c, 6, &sh.stage, (size_t)chunk * n)) return 1;
+            dst = sh.stage;
+        }
+        const int64_t gitems = vec ? n / 2 : n;
+        for (int l0 = 0; dst && l0 < levels; l0 += chunk) {
+            const int nlev = std::min(chunk, (int)levels - l0);
+            const int nbg = (int)std::max<int64_t>(1, std::min<int64_t>((4096 + nlev - 1) / nlev, (gitems + 255) / 256));
+            const double sgn = scaler > 0 ? 1.0 : -1.0;
+            if (vec) hipLaunchKernelGGL(k_disp_ks_grad<true>, dim3(nbg, nlev), dim3(256), 0, c->stream, Hd, n, ncols, l0, cu, sgn,
+                                        (const double*)(sh.kres + 4 * levels), dst);
+            else hipLaunchKernelGGL(k_disp_ks_grad<false>, dim3(nbg, nlev), dim3(256), 0, c->stream, Hd, n, ncols, l0, cu, sgn,
+                                    (const double*)(sh.kres + 4 * levels), dst);
+            HIPCHK(c, hipGetLastError());
+            if (G) HIPCHK(c, hipMemcpyAsync(G + (size_t)l0 * n, dst, (size_t)nlev * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            if (seed) dst += (size_t)nlev * n;
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (per_level)
+        for (int l = 0; l < levels; ++l) per_level[l] = res[l] * inv;
+    if (total) *total = tot;
+    return 0;
+}
+
+int femo_newmark_disp_aggregate(femo_ctx* c, int32_t levels, const double* H, int32_t components, double rho, double scaler,
+                                double* per_level, double* total) {
+    return disp_history_run(c, levels, H, components, rho, scaler, false, per_level, total, nullptr, false);
+}
+
+int femo_newmark_disp_aggregate_grad(femo_ctx* c, int32_t levels, const double* H, int32_t components, double rho, double scaler,
+                                     double* total, double* G, int seed_adjoint) {
+    return disp_history_run(c, levels, H, components, rho, scaler, true, nullptr, total, G, seed_adjoint != 0);
 }
 
 // ---- CSR assembly of the elastic stiffness (what assembleMatrix(dR_du) returns in the reference,

@@ -1,5 +1,5 @@
 """Dynamic operators: ``StateOperation`` (whole displacement history as one implicit state),
-``TotalStrainEnergyOperation``, ``StressHistoryOperation`` and ``VolumeOperation`` -- interfaces of
+``TotalStrainEnergyOperation``, ``StressHistoryOperation``, ``MaxDisplacementHistoryOperation`` and ``VolumeOperation`` -- interfaces of
 femo_alpha/dynamic_rm_shell/state_operation_dynamic.py:20-137,141-706, total_strain_energy_operation.py:20-138
 and volume_operation.py:20-70.  Histories cross the boundary as vectors flattened column-major from
 (fe_dofs, time_levels) (dynamic_rm_shell/utils.py:9-16)."""
@@ -168,6 +168,39 @@ class StressHistoryOperation(csdl.CustomExplicitOperation):
         g_t, g_w = ps.pnorm_stress_history_partials(W=W, **self._settings())
         derivatives[self.output_name, "thickness"] = g_t
         derivatives[self.output_name, "disp_history"] = stack_array_into_vector(g_w)
+
+
+class MaxDisplacementHistoryOperation(csdl.CustomExplicitOperation):
+    """max_disp = csdl.maximum(csdl.absolute(scaler * disp_history), rho) / scaler of ex_lpc_gust_response_opt.py:457-459, 770-772:
+    the KS aggregate of PlateSim.max_displacement_history over the whole space-time history.  The history is uploaded once per call
+    into a buffer of its own; the march's resident history is left as it is."""
+
+    def __init__(self, plate_sim, rho, scaler=1.0, components="all"):
+        super().__init__()
+        csdl.check_parameter(plate_sim, "plate_sim")
+        self.plate_sim = plate_sim
+        self.rho, self.scaler, self.components = rho, scaler, components
+        self.args_dict = ["disp_history"]
+        self.output_name = "max_disp"
+
+    def evaluate(self, inputs):
+        _declare(self, inputs)
+        out = self.create_output(self.output_name, (1,))
+        out.add_name(self.output_name)
+        self.declare_derivative_parameters(self.output_name, "*", dependent=True)
+        _finish(self)
+        return out
+
+    def _history(self, input_vals):
+        return reshape_vector_into_array(np.asarray(input_vals["disp_history"]), self.plate_sim.time_levels)
+
+    def compute(self, input_vals, output_vals):
+        M = self.plate_sim.max_displacement_history(self.rho, self.scaler, self.components, W=self._history(input_vals))
+        output_vals[self.output_name] = np.array([M])
+
+    def compute_derivatives(self, input_vals, output_vals, derivatives):
+        G = self.plate_sim.max_displacement_history_partials(self.rho, self.scaler, self.components, W=self._history(input_vals))
+        derivatives[self.output_name, "disp_history"] = stack_array_into_vector(G)
 
 
 class VolumeOperation(csdl.CustomExplicitOperation):

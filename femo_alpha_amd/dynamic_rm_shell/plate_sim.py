@@ -66,6 +66,10 @@ class PlateSim:
         self.t = np.full(self.num_var, 1e-3)
         self.opt_iter = 0
         self.W = None                      # device history, (time_levels, fe_dofs)
+        # tip displacement history (plate_sim.py:22-23, 107, 116-117, 154-156, 323-328): uz at x_tip, refreshed by every march
+        self.x_tip, self.cell_tip = None, None
+        self._tip = None                   # (dofs, weights) of the probe, False where the default point lies in no cell
+        self.tip_disp_history = np.zeros(self.time_levels)
         self.solve_info = []
         self._v = {n: ctx.vec_tensor(n) for n in ("state", "adjoint", "r", "z", "p", "Ap", "b")}
 
@@ -83,6 +87,7 @@ class PlateSim:
         # the next set-up re-allocates the resident histories: the zero-copy views of the old ones must not outlive them
         self.W = None
         self.Lam = None
+        self.tip_disp_history = np.zeros(self.time_levels)
 
     def _gravity(self):
         return (-1.0 if self.g_factor is None else self.g_factor) * 9.81
@@ -128,6 +133,7 @@ class PlateSim:
         ctx.newmark_set_constant_load(self._self_weight_load() if self._sw_weights is not None else None)
         self.solve_info = ctx.newmark_march(self.Nsteps, reassemble_every_step)
         self.W = ctx.newmark_tensor(0)                 # device history, (time_levels, fe_dofs), zero-copy
+        self.tip_disp_history = self.tip_displacement_history()
         return ctx.newmark_history(0).T.copy(order="F")
 
     def energy_audit(self):
@@ -214,6 +220,66 @@ class PlateSim:
         self.Lam = self.ctx.newmark_tensor(2)
         g_t, dF = self.residual_T_products()
         return g_part - g_t, -dF
+
+    # ------------------------------------------------------------------ tip displacement history
+    DEFAULT_X_TIP = (10.0, 0.0, 0.0)       # extractTipDispDolfinx's default point (plate_sim.py:22)
+
+    def set_up_tip_dofs(self, x_tip, cell_tip=None):
+        """The point whose z displacement ``tip_disp_history`` records (plate_sim.py:154-156).  ``cell_tip`` is a cell index of the
+        ShellMesh given to this PlateSim -- NOT the reference's dolfinx-internal index, which no other mesh shares; None locates the
+        cell holding x_tip (ShellMesh.point_evaluation; an error if there is none)."""
+        self._tip = self.mesh.point_evaluation(x_tip, cell=cell_tip, component=2)
+        self.x_tip, self.cell_tip = x_tip, cell_tip
+
+    def _tip_probe(self):
+        if self._tip is None:
+            if self.x_tip is not None:
+                self._tip = self.mesh.point_evaluation(self.x_tip, cell=self.cell_tip, component=2)
+            else:                         # the reference's default point, located; a mesh without it records zeros
+                cell = self.mesh.locate(self.DEFAULT_X_TIP)
+                self._tip = False if cell is None else self.mesh.point_evaluation(self.DEFAULT_X_TIP, cell=cell, component=2)
+        return self._tip
+
+    def tip_displacement_history(self, W=None):
+        """uz at the tip point for every time level (time_levels,): a gather of the cell's npc uz columns of the history and a dot with
+        the basis weights at the point -- on the device for the history of the last march (W = None), on the host for a given
+        (fe_dofs, time_levels) W.  Zeros if no tip was set up and the default point lies in no cell."""
+        probe = self._tip_probe()
+        if probe is False:
+            return np.zeros(self.time_levels)
+        dofs, weights = probe
+        if W is not None:
+            return weights @ np.asarray(W, dtype=np.float64).reshape(self.fe_dofs, self.time_levels)[dofs, :]
+        torch = self.torch
+        dev = self.W.device
+        idx = torch.as_tensor(dofs, dtype=torch.long, device=dev)
+        return (self.W[:, idx] @ torch.as_tensor(weights, dtype=torch.float64, device=dev)).cpu().numpy()
+
+    # ------------------------------------------------------------------ max-displacement aggregate (femo_newmark_disp_aggregate*)
+    def max_displacement_history(self, rho, scaler=1.0, components="all", per_level=False, W=None):
+        """M = csdl.maximum(csdl.absolute(scaler * W), rho) / scaler over the whole space-time history (ex_lpc_gust_response_opt.py:
+        457-459, 770-772), as the KS aggregate of include/femo_hip.h, in one pass over the history.  components: "all" (every entry,
+        rotations included) or "translations" (the mid-surface displacement).  ``per_level``: the T values M_i of each level alone.
+        ``W``: a (fe_dofs, time_levels) history (None: the last march's, read in place)."""
+        M, P = self.ctx.newmark_disp_aggregate(self.time_levels, rho, scaler, components, self._history_arg(W))
+        return P if per_level else M
+
+    def max_displacement_history_partials(self, rho, scaler=1.0, components="all", W=None):
+        """dM/dW of ``max_displacement_history`` in the boundary layout (fe_dofs, time_levels); the thickness does not enter M."""
+        _, G = self.ctx.newmark_disp_aggregate_grad(self.time_levels, rho, scaler, components, self._history_arg(W))
+        return G.T.copy(order="F")
+
+    def max_displacement_history_total_gradient(self, rho, scaler=1.0, components="all"):
+        """(dM/dt, dM/dF_history) through the transient adjoint, for the history of the last march: dM/dW seeds the adjoint on the
+        device (femo_newmark_adjoint_seeded), the residual products follow: dM/dt = -sum_i (dR_i/dt)^T lam_i,
+        dM/dF = -[(dR_i/df)^T lam_i]_i, (time_levels, 3 nn)."""
+        self._newmark()
+        T = self.time_levels
+        self.ctx.newmark_disp_aggregate_grad(T, rho, scaler, components, None, want_G=False, seed_adjoint=True)
+        self.ctx.newmark_adjoint_seeded(T)
+        self.Lam = self.ctx.newmark_tensor(2)
+        g_t, dF = self.residual_T_products()
+        return -g_t, -dF
 
     def von_Mises_stress(self, level=None):
         """Top-surface von Mises stress of one time level as a DG1 field, nvc values per cell (plate_sim.py:446-450)."""

@@ -172,6 +172,119 @@ class ShellMesh:
         det = np.linalg.norm(np.cross(J[..., 0], J[..., 1]), axis=-1)
         return np.einsum("q,eq,qa->ea", wq, det, N2)
 
+    # ------------------------------------------------------------------ point evaluation
+    def _ref_nodes(self):
+        """Reference coordinates of the local P2 nodes in ``cell_p2`` / build_tables order (Q2I; triangle edges ED = (0 1, 1 2, 2 0)):
+        quadrilaterals on [-1, 1]^2, triangles on the unit simplex."""
+        if self.is_quad:
+            return np.array([[-1, -1], [1, -1], [1, 1], [-1, 1], [0, -1], [1, 0], [0, 1], [-1, 0], [0, 0]], dtype=np.float64)
+        return np.array([[0, 0], [1, 0], [0, 1], [0.5, 0], [0.5, 0.5], [0, 0.5]], dtype=np.float64)
+
+    def _geometry(self, ref):
+        """(N, dN) of the (bi)linear geometry at reference points ref (..., 2): (..., nvc), (..., nvc, 2)."""
+        xi, eta = ref[..., 0], ref[..., 1]
+        if self.is_quad:
+            sx, sy = np.array([-1, 1, 1, -1.0]), np.array([-1, -1, 1, 1.0])
+            N = 0.25 * (1 + sx * xi[..., None]) * (1 + sy * eta[..., None])
+            dN = np.stack([0.25 * sx * (1 + sy * eta[..., None]), 0.25 * sy * (1 + sx * xi[..., None])], axis=-1)
+            return N, dN
+        N = np.stack([1 - xi - eta, xi, eta], axis=-1)
+        dN = np.broadcast_to(np.array([[-1, -1], [1, 0], [0, 1.0]]), N.shape + (2,))
+        return N, dN
+
+    def displacement_basis(self, ref):
+        """Values of the displacement basis at reference points ref (..., 2), in ``cell_p2`` order: Q2 (9) / P2 (6), or Q1 / P1 for
+        CG1CG1 -- the functions of build_tables (csrc/femo_hip.hip)."""
+        ref = np.asarray(ref, dtype=np.float64)
+        xi, eta = ref[..., 0], ref[..., 1]
+        if self.element == "CG1CG1":
+            return self._geometry(ref)[0]
+        if self.is_quad:
+            lag2 = lambda t: np.stack([0.5 * t * (t - 1.0), 1.0 - t * t, 0.5 * t * (t + 1.0)], axis=-1)       # nodes -1, 0, 1
+            a, b = lag2(xi), lag2(eta)
+            q2 = [(0, 0), (2, 0), (2, 2), (0, 2), (1, 0), (2, 1), (1, 2), (0, 1), (1, 1)]
+            return np.stack([a[..., i] * b[..., j] for i, j in q2], axis=-1)
+        L = np.stack([1 - xi - eta, xi, eta], axis=-1)
+        ed = [(0, 1), (1, 2), (2, 0)]
+        return np.concatenate([L * (2 * L - 1), np.stack([4 * L[..., i] * L[..., j] for i, j in ed], axis=-1)], axis=-1)
+
+    def pull_back(self, x, cells, tol=1e-14, maxit=100):
+        """Reference coordinates of the point x (3,) in each of ``cells`` under the (bi)linear geometry: Gauss-Newton least squares on
+        the cell embedded in R^3, from the local P2 node nearest x, to a correction below ``tol``.  Returns (ref (n, 2), distance from x
+        to the cell's surface (n,), converged (n,) bool)."""
+        cells = np.atleast_1d(np.asarray(cells, dtype=np.int64))
+        x = np.asarray(x, dtype=np.float64)
+        X = self.nodes[self.cells[cells]]                                     # (n, nvc, 3)
+        X0 = X[:, :1, :]
+        Xr, xr = X - X0, x[None, :] - X0[:, 0, :]                             # relative to vertex 0: corrections at the rounding of h
+        rn = self._ref_nodes()
+        Nn, _ = self._geometry(rn)
+        start = np.argmin(np.linalg.norm(np.einsum("ab,nbk->nak", Nn, Xr) - xr[:, None, :], axis=2), axis=1)
+        ref = rn[start].copy()
+        done = np.zeros(len(cells), dtype=bool)
+        for _ in range(maxit):
+            N, dN = self._geometry(ref)
+            r = xr - np.einsum("nb,nbk->nk", N, Xr)
+            J = np.einsum("nbk,nbj->nkj", Xr, dN)                             # (n, 3, 2)
+            JtJ = np.einsum("nki,nkj->nij", J, J)
+            d = np.linalg.solve(JtJ, np.einsum("nki,nk->ni", J, r)[..., None])[..., 0]
+            ref = np.where(done[:, None], ref, ref + d)
+            done |= np.abs(d).max(axis=1) < tol
+            if done.all():
+                break
+        N, _ = self._geometry(ref)
+        dist = np.linalg.norm(xr - np.einsum("nb,nbk->nk", N, Xr), axis=1)
+        return ref, dist, done
+
+    def _inside(self, ref, tol):
+        if self.is_quad:
+            return np.abs(ref).max(axis=1) <= 1 + tol
+        return (ref[:, 0] >= -tol) & (ref[:, 1] >= -tol) & (ref.sum(axis=1) <= 1 + tol)
+
+    def locate(self, x, tol=1e-10):
+        """The cell holding the point x: among the cells whose pull-back of x lands inside the reference cell (to ``tol``), the one
+        nearest to x (the lowest index among equals).  None if there is none."""
+        x = np.asarray(x, dtype=np.float64)
+        X = self.nodes[self.cells]
+        lo, hi = X.min(axis=1), X.max(axis=1)
+        pad = 0.5 * (hi - lo).max(axis=1, keepdims=True)
+        cand = np.nonzero(np.all((x >= lo - pad) & (x <= hi + pad), axis=1))[0]
+        if cand.size == 0:
+            return None
+        ref, dist, ok = self.pull_back(x, cand)
+        ok &= self._inside(ref, tol)
+        if not ok.any():
+            return None
+        return int(cand[ok][np.argmin(dist[ok])])
+
+    def point_evaluation(self, x, cell=None, component=2):
+        """(dofs, weights) such that ``weights @ w[dofs]`` is component ``component`` of the mid-surface displacement of the state w
+        at the point x -- the reference's ``w.sub(0).eval(x, cell)[component]`` (plate_sim.py:22-23; its tip history takes the z
+        component).  ``cell``: an index into THIS mesh's cells (the reference's are dolfinx-internal, which no other mesh shares); None
+        locates the cell (``locate``) and raises if no cell holds x.  x is pulled back to the reference coordinates of the cell's
+        (bi)linear geometry (Gauss-Newton on a cell embedded in R^3, to a correction below 1e-14; an error if it does not converge)
+        and the displacement basis of the element is evaluated there."""
+        x = np.asarray(x, dtype=np.float64).ravel()
+        if x.size == 2:
+            x = np.append(x, 0.0)
+        if x.size != 3 or not np.all(np.isfinite(x)):
+            raise ValueError(f"x must be a finite point in R^3, got {x}")
+        if component not in (0, 1, 2):
+            raise ValueError(f"component must be 0, 1 or 2, got {component}")
+        if cell is None:
+            cell = self.locate(x)
+            if cell is None:
+                raise ValueError(f"the point {x.tolist()} lies in no cell of the mesh")
+        cell = int(cell)
+        if not 0 <= cell < self.nel:
+            raise ValueError(f"cell {cell} is not a cell of this mesh ({self.nel} cells)")
+        ref, _, ok = self.pull_back(x, [cell])
+        if not ok[0]:
+            raise ValueError(f"the pull-back of {x.tolist()} into cell {cell} did not converge")
+        weights = self.displacement_basis(ref[0])
+        dofs = 3 * self.cell_p2[cell].astype(np.int64) + component
+        return dofs, weights
+
     def cell_diameters(self):
         """UFL ``CellDiameter``: largest distance between two vertices of the cell
         (used at linear_shell_model.py:285,325,339)."""

@@ -415,6 +415,22 @@ int femo_newmark_adjoint_seeded(femo_ctx* ctx, int32_t levels);
  * repeat bit for bit. */
 int femo_newmark_stress_history(femo_ctx* ctx, int32_t levels, const double* H, double* per_level, double* total);
 int femo_newmark_stress_history_grad(femo_ctx* ctx, int32_t levels, const double* H, double* g_thickness, double* G, int seed_adjoint);
+/* Max-displacement aggregate of the transient path: the lpc example's max_disp = csdl.maximum(csdl.absolute(s*disp_history),
+ * rho=rho_max)/s (ex_lpc_gust_response_opt.py:457-459, 770-772; rho_max = 300 at :77, s = 1/max(tip_disp_history)), a KS aggregate
+ * over every entry of the space-time history.  Our contract (csdl_alpha's maximum / absolute are not checked against it): for
+ * rho > 0 and a finite s != 0, x_k = |s| |w_k| over the selected entries k,
+ *     M = ( x_max + 1/rho log sum_k exp(rho (x_k - x_max)) ) / s,      dM/dw_k = sign(s) sign(w_k) exp(rho (x_k - s M))
+ * (0 where w_k = 0 and on entries not selected; every exponent <= 0).  components: 0 every entry (rotations included, as the example
+ * aggregates), 1 the first ndof_u entries of every level (the mid-surface displacement).  H: (levels x ndof) level-major, or NULL for
+ * the history of the last march, read in place; a given H goes to the buffer of femo_newmark_stress_history, never into the resident
+ * history.  per_level (levels entries: M_l over level l alone) and total may be NULL.  rho <= 0, s zero or not finite, and a
+ * non-finite history entry (the level is named) are errors.  femo_newmark_disp_aggregate_grad: total = M (the same bits as
+ * femo_newmark_disp_aggregate), G = dM/dW (levels x ndof, level-major; may be NULL); seed_adjoint != 0 leaves dM/dW in the adjoint
+ * seed buffer for femo_newmark_adjoint_seeded.  No float atomics: the results repeat bit for bit. */
+int femo_newmark_disp_aggregate(femo_ctx* ctx, int32_t levels, const double* H, int32_t components, double rho, double scaler,
+                                double* per_level, double* total);
+int femo_newmark_disp_aggregate_grad(femo_ctx* ctx, int32_t levels, const double* H, int32_t components, double rho, double scaler,
+                                     double* total, double* G, int seed_adjoint);
 /* Forward mode (state_operation_dynamic.py:228-329: compute_jacvec_product fwd; :534-605: apply_inverse_jacobian fwd, the
  * "tangent linear model").  Results land in the adjoint-history buffer (femo_newmark_get_history(ctx, 2, ..)). */
 int femo_newmark_jvp(femo_ctx* ctx, int32_t levels, const double* dY, const double* dthickness, const double* dF);
