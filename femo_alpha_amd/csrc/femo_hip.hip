@@ -10,6 +10,7 @@
 #include "stress_history.h"
 #include "disp_history.h"
 #include "csr_map.h"
+#include "hip_handles.h"
 
 #include <hip/hip_runtime.h>
 
@@ -36,101 +37,103 @@ static std::string g_create_error;
 
 struct femo_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     int krylov = 0;                          // 0: conjugate gradients, 1: BiCGStab (femo_set_krylov)
-    double* bi[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // BiCGStab work vectors (allocated on first use)
+    DevBuf<double> bi[5];                    // BiCGStab work vectors (allocated on first use)
     int tab_nq = 0;                          // quadrature points of the operator's tables (c->tab)
     double hK_mean = 0;                      // mean cell diameter (the yardstick of a change of uhat, option "stale_factor")
     // multi-right-hand-side solves (femo_solve_linear_multi): two interleaved buffers of 4 ndof doubles for the sweeps, 5 work vectors
     // per right-hand side (x, r, z, p, Ap), 8 device scalars per right-hand side; allocated on first use
-    double *mr_v = nullptr, *mr_y = nullptr, *mr_work = nullptr, *mr_scal = nullptr, *mr_scal_host = nullptr;
-    double* mr_io = nullptr;                 // right-hand sides, solutions and gradients of the multi entry points (grown on demand, kept)
-    size_t mr_io_cap = 0;
+    DevBuf<double> mr_v, mr_y, mr_work, mr_scal;
+    PinnedBuf<double> mr_scal_host;
+    DevBuf<double> mr_io;                    // right-hand sides, solutions and gradients of the multi entry points (grown on demand, kept)
     long long opt_version = 0;               // bumped by every femo_set_option
-    hipStream_t stream2 = nullptr;           // look-ahead: the bulk of a trailing update runs beside the next panel
-    hipEvent_t ev_la[2] = {nullptr, nullptr};
-    hipEvent_t ev_sp[2] = {nullptr, nullptr};
-    hipStream_t stream_g = nullptr;          // second stream of the levels whose fronts are dealt to two streams (option "split_cnt")
-    hipEvent_t ev_g[2] = {nullptr, nullptr};
-    hipStream_t stream_m = nullptr;          // diagonal look-ahead: a stream that may not use the CUs reserved for the diagonal blocks
-    hipEvent_t ev_da[2] = {nullptr, nullptr};
-    hipStream_t stream3 = nullptr;           // L11^-1 of a finished level is formed beside the factorisation of the next ones
-    hipStream_t stream_a = nullptr;          // option "sweep_ahead": the forward sweep of the lower levels beside the factorisation of the top
-    hipEvent_t ev_a[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_x[2] = {nullptr, nullptr};
+    Stream stream2;                          // look-ahead: the bulk of a trailing update runs beside the next panel
+    Event ev_la[2];
+    Event ev_sp[2];
+    Stream stream_g;                         // second stream of the levels whose fronts are dealt to two streams (option "split_cnt")
+    Event ev_g[2];
+    Stream stream_m;                         // diagonal look-ahead: a stream that may not use the CUs reserved for the diagonal blocks
+    Event ev_da[2];
+    Stream stream3;                          // L11^-1 of a finished level is formed beside the factorisation of the next ones
+    Stream stream_a;                         // option "sweep_ahead": the forward sweep of the lower levels beside the factorisation of the top
+    Event ev_a[3];
+    Event ev_x[2];
     int nn = 0, nel = 0, nvc = 0, npc = 0, nP2 = 0, ndof_u = 0, ndof = 0, ld = 0;   // ndof = vector length = mesh DOFs + nghost
     int nghost = 0;
     bool quad = true, ewm = false, ewp = false, has_uhat = false;
     bool cr = false;                         // element CG2CR1 (linear_shell_model.py:68-73, triangles): rotation on the edge midpoints (Crouzeix-Raviart)
     int nrot = 0;                            // rotation nodes: nn, or the number of edges for CG2CR1
-    int* frnode = nullptr; double* fMR = nullptr;   // CG2CR1: rotation nodes and 3 x 3 rotation blocks of the penalty facets
     bool cg1 = false;                        // element CG1CG1 (linear_shell_model.py:74-79): displacement on the vertices too (nP2 == nn)
     int64_t nT = 0, nF = 0;
     // mesh
-    double* xyz = nullptr;
-    int* cells = nullptr;
-    int* cellp2 = nullptr;
-    int* eorder = nullptr;      // elements along a Morton curve of their centroids (locality of gathers)
-    int *n2e_off = nullptr, *n2e_ent = nullptr;   // inverted connectivity: P2 node -> (slot in Morton order) * npc + local node
-    double* ybuf = nullptr;     // element results of the operator, YSTRIDE doubles per slot
-    int *v2e_off = nullptr, *v2e_ent = nullptr;   // vertex -> e * nvc + local vertex, cells in increasing order (stress-field derivatives)
-    double* hK = nullptr;
-    Tables* tab = nullptr;
-    Tables* tab_s = nullptr;     // degree-4 rule of the p-norm stress measure (3x3 Gauss on quads)
-    Tables* tab_pre = nullptr;   // rule of the front assembly when the operator's has more than 4 x 4 points (option "precond_nquad"); null: c->tab
+    DevBuf<double> xyz;
+    DevBuf<int> cells;
+    DevBuf<int> cellp2;
+    DevBuf<int> eorder;         // elements along a Morton curve of their centroids (locality of gathers)
+    DevBuf<int> n2e_off, n2e_ent;                 // inverted connectivity: P2 node -> (slot in Morton order) * npc + local node
+    DevBuf<double> ybuf;        // element results of the operator, YSTRIDE doubles per slot
+    DevBuf<int> v2e_off, v2e_ent;                 // vertex -> e * nvc + local vertex, cells in increasing order (stress-field derivatives)
+    DevBuf<double> hK;
+    DevBuf<Tables> tab;
+    DevBuf<Tables> tab_s;        // degree-4 rule of the p-norm stress measure (3x3 Gauss on quads)
+    DevBuf<Tables> tab_pre;      // rule of the front assembly when the operator's has more than 4 x 4 points (option "precond_nquad"); null: c->tab
     int tab_pre_nq = 0;
     double stress_m = 1e-6, stress_rho = 100.0, stress_alpha = -1.0, stress_reg = 0.0;
-    int* ctag = nullptr;                     // sub-domain index per cell
+    DevBuf<int> ctag;                        // sub-domain index per cell
     int csel = -1, ntags = 0;
     std::vector<double> alpha_tag;           // reference area of every sub-domain (frozen at first use, like stress_alpha)
-    double* gradbuf = nullptr;
-    double* eq = nullptr;                    // option "equilibrate": the factorisation is that of D K D, D = diag(eq) (allocated on first use)
-    double* fp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // force -> pressure solve: x, r, z, p, Ap, diag (3 nn each, on first use)
+    DevBuf<double> gradbuf;
+    DevBuf<double> eq;                       // option "equilibrate": the factorisation is that of D K D, D = diag(eq) (allocated on first use)
+    DevBuf<double> fp[6];                    // force -> pressure solve: x, r, z, p, Ap, diag (3 nn each, on first use)
     // element-partitioned driver (femo_dist_*): replicated separator entries, dot weights, gradient scatter map
     struct Dist {
         bool ready = false;
         int ntop = 0, nranks = 1, nl = 0, nsel = 0;
-        int *top_idx = nullptr, *sel = nullptr;
-        double *wdot = nullptr, *topbuf = nullptr, *topsave = nullptr, *gloc = nullptr;
+        DevBuf<int> top_idx, sel;
+        DevBuf<double> wdot, topbuf, topsave, gloc;
     } di;
     // transient march (femo_newmark_*): history, force history and work vectors resident in HBM
     struct Newmark {
         bool ready = false;
         int levels = 0, flevels = 0;
         double dt = 0, a = 0, b = 0;
-        double *W = nullptr, *Fh = nullptr, *wdot = nullptr, *Fsw = nullptr, *mu0 = nullptr, *mu1 = nullptr, *Lam = nullptr, *Gh = nullptr;
+        DevBuf<double> W, Fh, wdot, Fsw, mu0, mu1, Lam, Gh;
         bool has_sw = false;
     } nm;
     // space-time stress aggregate (femo_newmark_stress_history*) and max-displacement aggregate (femo_newmark_disp_aggregate*): an
-    // uploaded history of their own (never nm.W) and the scratch of a level chunk, grown on demand and kept; capacities in doubles
+    // uploaded history of their own (never nm.W) and the scratch of a level chunk, grown on demand and kept
     struct StressHist {
-        double *H = nullptr, *ybuf = nullptr, *tbuf = nullptr, *acc = nullptr, *bsum = nullptr, *lev = nullptr, *stage = nullptr, *tout = nullptr;
-        double *kpart = nullptr, *kres = nullptr;       // KS block pairs and per-level / total results of the displacement aggregate
-        size_t cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        DevBuf<double> H, ybuf, tbuf, acc, bsum, lev, stage, tout;
+        DevBuf<double> kpart, kres;                     // KS block pairs and per-level / total results of the displacement aggregate
     } sh;
     // CSR assembly
-    long long csr_ncontrib = 0; int csr_nnz = 0;
-    int *csr_perm = nullptr, *csr_dest = nullptr, *csr_rowptr = nullptr, *csr_colidx = nullptr;
-    double *csr_vals = nullptr, *csr_ke = nullptr;
+    struct Csr {
+        long long ncontrib = 0; int nnz = 0;
+        DevBuf<int> perm, dest, rowptr, colidx;
+        DevBuf<double> vals, ke;
+    } csr;
     double op_aK = 1.0, op_aM = 0.0;      // the operator every solve / factorisation uses: aK * K + aM * M
     int nquad = 4, nred = 0;
     // fields
-    double *h = nullptr, *E = nullptr, *nu = nullptr, *rho = nullptr, *f = nullptr, *uhat = nullptr;
+    DevBuf<double> h, E, nu, rho, f, uhat;
     // dirichlet
     int nf = 0;
-    int *fcell = nullptr, *fledge = nullptr, *funode = nullptr, *fvnode = nullptr;
-    double *fM2 = nullptr, *fM1 = nullptr;
+    struct Facets {
+        DevBuf<int> cell, ledge, unode, vnode;
+        DevBuf<double> M2, M1;
+        DevBuf<int> rnode; DevBuf<double> MR;    // CG2CR1: rotation nodes and 3 x 3 rotation blocks of the penalty facets
+    } fa;
     double beta = 1e15;
     bool penalty_dirty = true;
-    double* gdir = nullptr;       // prescribed values g of the penalty term beta/h_E |..| (w - g).v (linear_shell_model.py:323-333); null = zero
+    DevBuf<double> gdir;          // prescribed values g of the penalty term beta/h_E |..| (w - g).v (linear_shell_model.py:323-333); null = zero
     bool has_g = false;
-    unsigned char* mask = nullptr;
+    DevBuf<unsigned char> mask;
     bool has_mask = false;
     // vectors
-    double *w = nullptr, *lam = nullptr, *r = nullptr, *z = nullptr, *p = nullptr, *Ap = nullptr, *dinv = nullptr,
-           *b = nullptr, *tmp = nullptr;
-    double* scal = nullptr;        // device, 8 slots
-    double* scal_host = nullptr;   // pinned, 8 slots
+    DevBuf<double> w, lam, r, z, p, Ap, dinv, b, tmp;
+    DevBuf<double> scal;           // device, 8 slots
+    PinnedBuf<double> scal_host;   // pinned, 8 slots
     bool jacobi_dirty = true;      // the Jacobi diagonal is stale (fields / Dirichlet data / operator changed)
     // schedule switches and failure policy (femo_set_option); never read from the environment
     struct Options {
@@ -234,14 +237,14 @@ struct femo_ctx {
     int precond = 0;
     double rtol = 1e-10;
     int maxit = 200000, check_every = 50;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     double timing[5] = {0, 0, 0, 0, 0};
     std::string err;
     // multifrontal preconditioner (precond == 2)
     struct Frontal {
         bool ready = false, factored = false;
         bool have_factor = false;             // a complete factorisation of SOME earlier operator sits in the panel store (option "stale_factor")
-        double* snap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // thickness, E, nu, density, uhat as they were when that factor was made
+        DevBuf<double> snap[5];               // thickness, E, nu, density, uhat as they were when that factor was made
         bool snap_valid = false;
         bool w_mode = false;                  // the wide levels of the stored factor hold W = L21 X where L21 was (option "sweep_w" at the time of the factorisation)
         double* ahead_vec = nullptr;          // option "sweep_ahead": the vector whose forward sweep the running factorisation starts (null: none)
@@ -250,20 +253,18 @@ struct femo_ctx {
         int ntree = 0, nlevels = 0;
         std::vector<int> h_nf, h_npiv, h_level_off, h_level_nodes, h_level_maxnp, h_level_maxnb;
         std::vector<char> h_level_wide;              // level takes the wide solve kernels (and keeps S in Sinv)
-        int *nf = nullptr, *npiv = nullptr, *dofs = nullptr, *upmap = nullptr, *parent = nullptr, *left = nullptr,
-            *right = nullptr, *level_nodes = nullptr, *elem_front = nullptr, *elem_map = nullptr, *info = nullptr,
-            *cinv0 = nullptr, *cinv1 = nullptr;
-        long long *poff = nullptr, *soff = nullptr, *doff = nullptr, *linvoff = nullptr, *xoff = nullptr;
-        double *P = nullptr, *S = nullptr, *Linv = nullptr, *X = nullptr, *Xtmp = nullptr, *Swork = nullptr;
+        DevBuf<int> nf, npiv, dofs, upmap, parent, left, right, level_nodes, elem_front, elem_map, info, cinv0, cinv1;
+        DevBuf<long long> poff, soff, doff, linvoff, xoff;
+        DevBuf<double> P, S, Linv, X, Xtmp, Swork;
         // fused sweeps of the wide levels (option "sweep_fuse"): tiles as tasks of one launch per run of consecutive wide levels
-        int* slot_of = nullptr;               // position of every front in level_nodes
-        int *fel_off = nullptr, *fel = nullptr;      // elements of every level-0 front, by position in the level (front-centric assembly)
+        DevBuf<int> slot_of;                  // position of every front in level_nodes
+        DevBuf<int> fel_off, fel;                    // elements of every level-0 front, by position in the level (front-centric assembly)
         bool fc_ok = false;                   // every element belongs to a level-0 front
-        int* sweep_cnt = nullptr;             // two counters per position (k_sweep_wide_fwd / _bwd)
-        SweepTask *ftasks = nullptr, *btasks = nullptr;
+        DevBuf<int> sweep_cnt;                // two counters per position (k_sweep_wide_fwd / _bwd)
+        DevBuf<SweepTask> ftasks, btasks;
         std::vector<long long> h_ft_off;      // forward table (levels ascending): tasks of level L at [h_ft_off[L], h_ft_off[L + 1])
         std::vector<long long> h_bt_begin, h_bt_end;   // backward table (levels descending): tasks of level L at [begin, end)
-        hipGraphExec_t sweep_graph = nullptr; // one preconditioner application on c->z, captured (option "sweep_graph")
+        GraphExec sweep_graph;                // one preconditioner application on c->z, captured (option "sweep_graph")
         long long sweep_graph_key = -1;       // options version the graph was captured under
         std::vector<long long> h_soff;        // host copy of the Schur offsets (femo_front_schur_get / block_set)
         long long p_doubles = 0, s_doubles = 0, linv_doubles = 0, x_doubles = 0;
@@ -278,8 +279,8 @@ struct femo_ctx {
         long long prof_calls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         double prof_flops[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // algorithmic flops of what the launches of a class execute (lower triangles only)
         double prof_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // compulsory HBM bytes of those launches (every operand entry once, results read + written)
-        std::vector<hipEvent_t> pev;
-        std::vector<double> pmeta;            // per profiled launch group: algorithmic flops, compulsory bytes (rank-k updates only)
+        struct ProfRecord { Event a, b; int cls, level; double flops, bytes; };   // flops / bytes: rank-k updates only
+        std::vector<ProfRecord> prof;         // one per profiled launch group
         double last_fl = 0, last_by = 0;
         int cur_level = 0;
     } fr;
@@ -304,7 +305,7 @@ static int fail(femo_ctx* c, const std::string& msg) {
 // whatever the operator A = aK K + aM M (+ Dirichlet treatment) depends on has changed: both preconditioners are stale
 static void operator_changed(femo_ctx* c, bool fields_only = false);
 static int snapshot_fields(femo_ctx* c);
-static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<hipEvent_t>* marks = nullptr);
+static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<Event>* marks = nullptr);
 
 // ------------------------------------------------------------------------------------------ tables
 static void gauss_legendre(int n, double* x, double* w) {
@@ -538,8 +539,8 @@ static FieldsDev fields_dev(const femo_ctx* c) {
 }
 static FacetDev facet_dev(const femo_ctx* c) {
     FacetDev fd;
-    fd.nf = c->nf; fd.cell = c->fcell; fd.ledge = c->fledge; fd.unode = c->funode; fd.vnode = c->fvnode;
-    fd.M2 = c->fM2; fd.M1 = c->fM1; fd.rnode = c->frnode; fd.MR = c->fMR;
+    fd.nf = c->nf; fd.cell = c->fa.cell; fd.ledge = c->fa.ledge; fd.unode = c->fa.unode; fd.vnode = c->fa.vnode;
+    fd.M2 = c->fa.M2; fd.M1 = c->fa.M1; fd.rnode = c->fa.rnode; fd.MR = c->fa.MR;
     return fd;
 }
 
@@ -769,17 +770,16 @@ static FrontDev front_dev(const femo_ctx* c) {
 
 // event pair around one launch group when profiling
 struct ProfScope {
-    femo_ctx* c; int cls; hipStream_t s; hipEvent_t a = nullptr, b = nullptr;
-    ProfScope(femo_ctx* c_, int cls_, hipStream_t s_ = nullptr) : c(c_), cls(cls_), s(s_ ? s_ : c_->stream) {
+    femo_ctx* c; int cls; hipStream_t s; Event a, b;
+    ProfScope(femo_ctx* c_, int cls_, hipStream_t s_ = nullptr) : c(c_), cls(cls_), s(s_ ? s_ : c_->stream.get()) {
         if (!c->fr.profile) return;
-        hipEventCreate(&a); hipEventCreate(&b);
+        hipEventCreate(a.out()); hipEventCreate(b.out());
         hipEventRecord(a, s);
     }
     ~ProfScope() {
         if (!c->fr.profile) return;
         hipEventRecord(b, s);
-        c->fr.pev.push_back(a); c->fr.pev.push_back(b); c->fr.pev.push_back((hipEvent_t)(intptr_t)(cls + 16 * c->fr.cur_level));
-        c->fr.pmeta.push_back(cls == 2 ? c->fr.last_fl : 0.0); c->fr.pmeta.push_back(cls == 2 ? c->fr.last_by : 0.0);
+        c->fr.prof.push_back({std::move(a), std::move(b), cls, c->fr.cur_level, cls == 2 ? c->fr.last_fl : 0.0, cls == 2 ? c->fr.last_by : 0.0});
         c->fr.last_fl = c->fr.last_by = 0;
     }
 };
@@ -834,7 +834,7 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
         if (c->opt.equilibrate) {
             if (c->op_aM != 0.0 || c->op_aK != 1.0 || l1 != fr.nlevels || l0 != 0)
                 return fail(c, "option equilibrate: static operator and whole factorisations only (an experiment)");
-            if (!c->eq) HIPCHK(c, hipMalloc((void**)&c->eq, (size_t)c->ndof * sizeof(double)));
+            if (!c->eq) HIPCHK(c, c->eq.alloc((size_t)c->ndof));
             c->jacobi_dirty = true;
             if (refresh_diag(c)) return 1;
             hipLaunchKernelGGL(k_eq_scale, dim3(vec_grid(c->ndof)), dim3(256), 0, c->stream, c->eq, (const double*)c->dinv, mask, c->opt.equilibrate, (int64_t)c->ndof);
@@ -848,7 +848,7 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             if (!c->tab_pre || c->tab_pre_nq != c->opt.precond_nquad * c->opt.precond_nquad) {
                 Tables TP;                                           // 8 KB on this thread's stack (contexts of several threads factorise at once)
                 build_tables(true, c->opt.precond_nquad, TP, 0, c->cg1, c->cr);
-                if (!c->tab_pre) HIPCHK(c, hipMalloc((void**)&c->tab_pre, sizeof(Tables)));
+                if (!c->tab_pre) HIPCHK(c, c->tab_pre.alloc(1));
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 HIPCHK(c, hipMemcpy(c->tab_pre, &TP, sizeof(Tables), hipMemcpyHostToDevice));
                 c->tab_pre_nq = TP.nq;
@@ -1298,11 +1298,10 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             HIPCHK(c, hipStreamWaitEvent(c->stream_a, c->ev_a[0], 0));
             HIPCHK(c, hipEventRecord(c->ev_a[1], c->stream3));
             HIPCHK(c, hipStreamWaitEvent(c->stream_a, c->ev_a[1], 0));
-            hipStream_t main_stream = c->stream;
             const bool keep_inflight = fr.x_inflight;
-            c->stream = c->stream_a; fr.x_inflight = false;            // (the sweep's own join has nothing to wait for: done above)
+            std::swap(c->stream, c->stream_a); fr.x_inflight = false;  // (the sweep's own join has nothing to wait for: done above)
             const int rc_a = frontal_fwd(c, fr.ahead_vec, 0, L + 1, nullptr);
-            c->stream = main_stream; fr.x_inflight = keep_inflight;
+            std::swap(c->stream, c->stream_a); fr.x_inflight = keep_inflight;
             if (rc_a) return rc_a;
             HIPCHK(c, hipEventRecord(c->ev_a[2], c->stream_a));
             fr.ahead_levels = L + 1;
@@ -1340,27 +1339,25 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
         fr.factored = false; fr.have_factor = false; fr.snap_valid = false;
         pivot_rc = 5;
     }
-    for (size_t i = 0; i + 2 < fr.pev.size() + 0 && fr.profile; i += 3) {
+    for (const auto& pr : fr.prof) {
+        if (!fr.profile) break;
         float ms = 0;
-        hipEventElapsedTime(&ms, fr.pev[i], fr.pev[i + 1]);
-        const int tag = (int)(intptr_t)fr.pev[i + 2];
-        const int cls = tag % 16;
+        hipEventElapsedTime(&ms, pr.a, pr.b);
+        const int cls = pr.cls;
         fr.prof_ms[cls] += ms; fr.prof_calls[cls] += 1;
         if (cls == 2) {
             // class 7: the rank-k launches whose arithmetic intensity (algorithmic flops / compulsory bytes) lies above the ridge of
             // the chip, 78.6 TFLOP/s / 8 TB/s = 9.8 flop per byte -- the ones the matrix cores can bound; the rest of class 2 is
             // bounded by HBM whatever the kernel does
-            const double fl = fr.pmeta[i / 3 * 2], by = fr.pmeta[i / 3 * 2 + 1];
+            const double fl = pr.flops, by = pr.bytes;
             if (by > 0 && fl / by >= 78.6e12 / 8.0e12) { fr.prof_ms[7] += ms; fr.prof_calls[7] += 1; fr.prof_flops[7] += fl; fr.prof_bytes[7] += by; }
         }
         if (c->opt.profile_verbose) {
-            if (cls == 2) fprintf(stderr, "prof level %d class %d %.1f us flops %.6e bytes %.6e\n", tag / 16, cls, ms * 1e3, fr.pmeta[i / 3 * 2], fr.pmeta[i / 3 * 2 + 1]);
-            else fprintf(stderr, "prof level %d class %d %.1f us\n", tag / 16, cls, ms * 1e3);
+            if (cls == 2) fprintf(stderr, "prof level %d class %d %.1f us flops %.6e bytes %.6e\n", pr.level, cls, ms * 1e3, pr.flops, pr.bytes);
+            else fprintf(stderr, "prof level %d class %d %.1f us\n", pr.level, cls, ms * 1e3);
         }
-        hipEventDestroy(fr.pev[i]); hipEventDestroy(fr.pev[i + 1]);
     }
-    fr.pev.clear();
-    fr.pmeta.clear();
+    fr.prof.clear();
     return pivot_rc;
 }
 
@@ -1369,11 +1366,11 @@ static int frontal_factorize(femo_ctx* c) { return frontal_factorize_range(c, 0,
 // v <- (L L^T)^-1 v   (c->tmp is the scratch vector: forward v -> tmp, backward tmp -> v)
 // Wide levels: two matrix-vector products per sweep (X = L11^-1 and L21), accumulated with atomics into entries that the
 // memset at the start of the sweep zeroed; the other levels: one workgroup per front.
-static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<hipEvent_t>* marks) {
+static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<Event>* marks) {
     auto& fr = c->fr;
     const FrontDev fd = front_dev(c);
     double* y = c->tmp;
-    auto mark = [&]() { if (marks) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, c->stream); marks->push_back(e); } };
+    auto mark = [&]() { if (marks) { marks->emplace_back(); hipEventCreate(marks->back().out()); hipEventRecord(marks->back(), c->stream); } };
     if (l0 == 0) HIPCHK(c, hipMemsetAsync(y, 0, (size_t)c->ndof * sizeof(double), c->stream));
     mark();
     for (int L = l0; L < l1; ++L) {
@@ -1429,11 +1426,11 @@ static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<hipEv
 // backward over levels l1-1 ... l0: y (in tmp) is consumed in place (running right-hand side), x lands in v.  After the
 // forward sweep nothing in v is alive (every entry is the pivot of a front behind us), so the sweep from the root starts
 // by zeroing it: the wide levels accumulate x with atomics.
-static int frontal_bwd(femo_ctx* c, double* v, int l0, int l1, std::vector<hipEvent_t>* marks = nullptr) {
+static int frontal_bwd(femo_ctx* c, double* v, int l0, int l1, std::vector<Event>* marks = nullptr) {
     auto& fr = c->fr;
     const FrontDev fd = front_dev(c);
     double* y = c->tmp;
-    auto mark = [&]() { if (marks) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, c->stream); marks->push_back(e); } };
+    auto mark = [&]() { if (marks) { marks->emplace_back(); hipEventCreate(marks->back().out()); hipEventRecord(marks->back(), c->stream); } };
     if (l1 == fr.nlevels) HIPCHK(c, hipMemsetAsync(v, 0, (size_t)c->ndof * sizeof(double), c->stream));
     mark();
     for (int L = l1 - 1; L >= l0; --L) {
@@ -1514,8 +1511,8 @@ static int frontal_solve(femo_ctx* c, double* v) {
 // ---- several right-hand sides through ONE pair of sweeps (sweeps_multi.h): V and Y hold NR interleaved vectors.  Same schedule as
 // frontal_fwd / frontal_bwd in its default form (level by level; the fused and the W forms are single-vector experiments).
 template <int NR>
-static int frontal_solve_multi(femo_ctx* c, double* V, double* Y, std::vector<hipEvent_t>* marks = nullptr) {
-    auto mark = [&]() { if (marks) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, c->stream); marks->push_back(e); } };
+static int frontal_solve_multi(femo_ctx* c, double* V, double* Y, std::vector<Event>* marks = nullptr) {
+    auto mark = [&]() { if (marks) { marks->emplace_back(); hipEventCreate(marks->back().out()); hipEventRecord(marks->back(), c->stream); } };
     auto& fr = c->fr;
     const FrontDev fd = front_dev(c);
     const size_t bytes = (size_t)c->ndof * NR * sizeof(double);
@@ -1572,23 +1569,19 @@ static int frontal_solve_multi(femo_ctx* c, double* V, double* Y, std::vector<hi
     return 0;
 }
 
-static double* mr_io_buffer(femo_ctx* c, size_t doubles) {
-    if (doubles > c->mr_io_cap) {
-        if (c->mr_io) { hipStreamSynchronize(c->stream); hipFree(c->mr_io); c->mr_io = nullptr; c->mr_io_cap = 0; }
-        if (hipMalloc((void**)&c->mr_io, doubles * sizeof(double)) != hipSuccess) { c->err = "out of device memory"; return nullptr; }
-        c->mr_io_cap = doubles;
-    }
-    return c->mr_io;
-}
-
+// all five buffers or none: they are moved into the context only once every allocation has succeeded
 static int mr_alloc(femo_ctx* c) {
     if (c->mr_v) return 0;
     const size_t n = (size_t)c->ndof;
-    HIPCHK(c, hipMalloc((void**)&c->mr_v, 4 * n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->mr_y, 4 * n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->mr_work, 20 * n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->mr_scal, 32 * sizeof(double)));
-    HIPCHK(c, hipHostMalloc((void**)&c->mr_scal_host, 32 * sizeof(double)));
+    DevBuf<double> v, y, work, scal;
+    PinnedBuf<double> scal_host;
+    HIPCHK(c, v.alloc(4 * n));
+    HIPCHK(c, y.alloc(4 * n));
+    HIPCHK(c, work.alloc(20 * n));
+    HIPCHK(c, scal.alloc(32));
+    HIPCHK(c, scal_host.alloc(32));
+    c->mr_v = std::move(v); c->mr_y = std::move(y); c->mr_work = std::move(work);
+    c->mr_scal = std::move(scal); c->mr_scal_host = std::move(scal_host);
     return 0;
 }
 
@@ -1698,15 +1691,14 @@ static int frontal_solve_z(femo_ctx* c) {
     if (join_xinv(c)) return 1;                            // the cross-stream join stays outside the capture
     const long long graph_key = 2 * c->opt_version + (fr.w_mode ? 1 : 0);
     if (!fr.sweep_graph || fr.sweep_graph_key != graph_key) {
-        if (fr.sweep_graph) { hipGraphExecDestroy(fr.sweep_graph); fr.sweep_graph = nullptr; }
-        hipGraph_t g = nullptr;
+        fr.sweep_graph.reset();
+        Graph g;
         HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         const int rc = frontal_solve(c, c->z);
-        const hipError_t e = hipStreamEndCapture(c->stream, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return rc; }
+        const hipError_t e = hipStreamEndCapture(c->stream, g.out());
+        if (rc) return rc;
         HIPCHK(c, e);
-        HIPCHK(c, hipGraphInstantiate(&fr.sweep_graph, g, nullptr, nullptr, 0));
-        hipGraphDestroy(g);
+        HIPCHK(c, hipGraphInstantiate(fr.sweep_graph.out(), g, nullptr, nullptr, 0));
         fr.sweep_graph_key = graph_key;
     }
     HIPCHK(c, hipGraphLaunch(fr.sweep_graph, c->stream));
@@ -1719,8 +1711,8 @@ static int snapshot_fields(femo_ctx* c) {
     double* cur[5] = {c->h, c->E, c->nu, c->rho, c->has_uhat ? c->uhat : nullptr};
     const int64_t len[5] = {c->nT, c->nT, c->nT, c->nT, 3 * (int64_t)c->nn};
     for (int i = 0; i < 5; ++i) {
-        if (!cur[i]) { if (c->fr.snap[i]) { hipFree(c->fr.snap[i]); c->fr.snap[i] = nullptr; } continue; }
-        if (!c->fr.snap[i]) HIPCHK(c, hipMalloc((void**)&c->fr.snap[i], (size_t)len[i] * sizeof(double)));
+        if (!cur[i]) { c->fr.snap[i].reset(); continue; }
+        if (!c->fr.snap[i]) HIPCHK(c, c->fr.snap[i].alloc((size_t)len[i]));
         HIPCHK(c, hipMemcpyAsync(c->fr.snap[i], cur[i], (size_t)len[i] * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     c->fr.snap_valid = true;
@@ -1874,7 +1866,7 @@ static int bicgstab(femo_ctx* c, double* b, double* x, bool zero_guess, int32_t*
         if (refresh_diag(c)) return 1;
     }
     for (int i = 0; i < 5; ++i)
-        if (!c->bi[i]) HIPCHK(c, hipMalloc((void**)&c->bi[i], (size_t)n * sizeof(double)));
+        if (!c->bi[i]) HIPCHK(c, c->bi[i].alloc((size_t)n));
     double *rh = c->bi[0], *v = c->bi[1], *s = c->bi[2], *t = c->bi[3], *y = c->bi[4], *r = c->r, *p = c->p, *z = c->z;
     auto dot = [&](const double* a, const double* bb, double* out) -> int {
         HIPCHK(c, hipMemsetAsync(c->scal + 7, 0, sizeof(double), c->stream));
@@ -1973,24 +1965,24 @@ int femo_device_count(void) {
 
 const char* femo_last_error(const femo_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-static int alloc_d(femo_ctx* c, double** p, int64_t n) {
-    HIPCHK(c, hipMalloc((void**)p, std::max<int64_t>(n, 1) * sizeof(double)));
+static int alloc_d(femo_ctx* c, DevBuf<double>* p, int64_t n) {
+    HIPCHK(c, p->alloc(std::max<int64_t>(n, 1)));
     HIPCHK(c, hipMemsetAsync(*p, 0, std::max<int64_t>(n, 1) * sizeof(double), c->stream));
     return 0;
 }
 
 static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, const int32_t* cell_p2, int nquad) {
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamCreate(&c->stream));
-    HIPCHK(c, hipStreamCreate(&c->stream2));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_la[i], hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sp[i], hipEventDisableTiming));
-    HIPCHK(c, hipStreamCreate(&c->stream3));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_x[i], hipEventDisableTiming));
-    HIPCHK(c, hipStreamCreate(&c->stream_g));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_g[i], hipEventDisableTiming));
-    HIPCHK(c, hipStreamCreate(&c->stream_a));      // (a lowest-priority stream here made the factorisation 6 ms SLOWER: 13.4 -> 19.4 ms)
-    for (int i = 0; i < 3; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_a[i], hipEventDisableTiming));
+    HIPCHK(c, hipStreamCreate(c->stream.out()));
+    HIPCHK(c, hipStreamCreate(c->stream2.out()));
+    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_la[i].out(), hipEventDisableTiming));
+    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_sp[i].out(), hipEventDisableTiming));
+    HIPCHK(c, hipStreamCreate(c->stream3.out()));
+    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_x[i].out(), hipEventDisableTiming));
+    HIPCHK(c, hipStreamCreate(c->stream_g.out()));
+    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_g[i].out(), hipEventDisableTiming));
+    HIPCHK(c, hipStreamCreate(c->stream_a.out()));   // (a lowest-priority stream here made the factorisation 6 ms SLOWER: 13.4 -> 19.4 ms)
+    for (int i = 0; i < 3; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_a[i].out(), hipEventDisableTiming));
     {
         // The diagonal look-ahead (factorize_fronts) runs the bulk of a panel's work on stream_m beside the next diagonal
         // block, whose one workgroup per front needs a whole CU's LDS: stream_m leaves 32 of the 256 CUs alone (bits whose
@@ -1999,10 +1991,10 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
         // is still correct; the option falls back to the plain super-panel order when the stream cannot be made.
         uint32_t cumask[8];
         for (int w = 0; w < 8; ++w) cumask[w] = (w & 1) ? 0xffffffffu : 0xffffff00u;
-        if (hipExtStreamCreateWithCUMask(&c->stream_m, 8, cumask) != hipSuccess) { (void)hipGetLastError(); c->stream_m = nullptr; }
-        for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->ev_da[i], hipEventDisableTiming));
+        if (hipExtStreamCreateWithCUMask(c->stream_m.out(), 8, cumask) != hipSuccess) (void)hipGetLastError();   // stream_m stays null
+        for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_da[i].out(), hipEventDisableTiming));
     }
-    for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventCreate(&c->ev[i]));
+    for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventCreate(c->ev[i].out()));
     const int nel = c->nel, nvc = c->nvc, npc = c->npc;
     // SoA connectivity
     std::vector<int> soa_c((size_t)nvc * nel), soa_p((size_t)npc * nel);
@@ -2021,11 +2013,11 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
             }
         hK[e] = d;
     }
-    HIPCHK(c, hipMalloc((void**)&c->xyz, (size_t)c->nn * 3 * sizeof(double)));
+    HIPCHK(c, c->xyz.alloc((size_t)c->nn * 3));
     HIPCHK(c, hipMemcpy(c->xyz, xyz, (size_t)c->nn * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&c->cells, soa_c.size() * sizeof(int)));
+    HIPCHK(c, c->cells.alloc(soa_c.size()));
     HIPCHK(c, hipMemcpy(c->cells, soa_c.data(), soa_c.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&c->cellp2, soa_p.size() * sizeof(int)));
+    HIPCHK(c, c->cellp2.alloc(soa_p.size()));
     HIPCHK(c, hipMemcpy(c->cellp2, soa_p.data(), soa_p.size() * sizeof(int), hipMemcpyHostToDevice));
     {   // Morton order of the element centroids (30 bits per axis on the bounding box)
         double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
@@ -2056,7 +2048,7 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
         std::sort(key.begin(), key.end());
         std::vector<int> eo(nel);
         for (int e = 0; e < nel; ++e) eo[e] = key[e].second;
-        HIPCHK(c, hipMalloc((void**)&c->eorder, (size_t)nel * sizeof(int)));
+        HIPCHK(c, c->eorder.alloc((size_t)nel));
         HIPCHK(c, hipMemcpy(c->eorder, eo.data(), (size_t)nel * sizeof(int), hipMemcpyHostToDevice));
         // inverted connectivity in slot order
         std::vector<int> off(c->nP2 + 1, 0), ent((size_t)nel * npc);
@@ -2067,47 +2059,47 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
             const int e = eo[slot];
             for (int a = 0; a < npc; ++a) ent[cur[cell_p2[(size_t)e * npc + a]]++] = slot * npc + a;
         }
-        HIPCHK(c, hipMalloc((void**)&c->n2e_off, off.size() * sizeof(int)));
+        HIPCHK(c, c->n2e_off.alloc(off.size()));
         HIPCHK(c, hipMemcpy(c->n2e_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc((void**)&c->n2e_ent, ent.size() * sizeof(int)));
+        HIPCHK(c, c->n2e_ent.alloc(ent.size()));
         HIPCHK(c, hipMemcpy(c->n2e_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc((void**)&c->ybuf, (size_t)nel * YSTRIDE * sizeof(double)));
+        HIPCHK(c, c->ybuf.alloc((size_t)nel * YSTRIDE));
         // vertex -> (cell, local vertex): the fixed-order sums of the per-cell results of the nodal-field derivatives
         std::vector<int> voff(c->nn + 1, 0), vent((size_t)nel * nvc);
         for (size_t i = 0; i < (size_t)nel * nvc; ++i) voff[cells[i] + 1]++;
         for (int v = 0; v < c->nn; ++v) voff[v + 1] += voff[v];
         std::vector<int> vcur(voff.begin(), voff.end() - 1);
         for (size_t i = 0; i < (size_t)nel * nvc; ++i) vent[vcur[cells[i]]++] = (int)i;
-        HIPCHK(c, hipMalloc((void**)&c->v2e_off, voff.size() * sizeof(int)));
+        HIPCHK(c, c->v2e_off.alloc(voff.size()));
         HIPCHK(c, hipMemcpy(c->v2e_off, voff.data(), voff.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc((void**)&c->v2e_ent, vent.size() * sizeof(int)));
+        HIPCHK(c, c->v2e_ent.alloc(vent.size()));
         HIPCHK(c, hipMemcpy(c->v2e_ent, vent.data(), vent.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    HIPCHK(c, hipMalloc((void**)&c->hK, (size_t)nel * sizeof(double)));
+    HIPCHK(c, c->hK.alloc((size_t)nel));
     HIPCHK(c, hipMemcpy(c->hK, hK.data(), (size_t)nel * sizeof(double), hipMemcpyHostToDevice));
     { double sum = 0; for (double v : hK) sum += v; c->hK_mean = sum / nel; }
     Tables T;
     c->nquad = nquad;
     build_tables(c->quad, nquad, T, 0, c->cg1, c->cr);
-    HIPCHK(c, hipMalloc((void**)&c->tab, sizeof(Tables)));
+    HIPCHK(c, c->tab.alloc(1));
     HIPCHK(c, hipMemcpy(c->tab, &T, sizeof(Tables), hipMemcpyHostToDevice));
     c->tab_nq = T.nq;
     Tables TS_;
     // quadrature_degree 4 (rm_shell_model.py:200-205): 3 x 3 Gauss on quadrilaterals, the 6-point rule of degree 4 on triangles
     build_tables(c->quad, c->quad ? 3 : 4, TS_, 0, c->cg1, c->cr);
-    HIPCHK(c, hipMalloc((void**)&c->tab_s, sizeof(Tables)));
+    HIPCHK(c, c->tab_s.alloc(1));
     HIPCHK(c, hipMemcpy(c->tab_s, &TS_, sizeof(Tables), hipMemcpyHostToDevice));
     c->nT = c->ewm ? nel : c->nn;
     c->nF = c->ewp ? nel : c->nn;
     if (alloc_d(c, &c->h, c->nT) || alloc_d(c, &c->E, c->nT) || alloc_d(c, &c->nu, c->nT) || alloc_d(c, &c->rho, c->nT) ||
         alloc_d(c, &c->f, 3 * c->nF) || alloc_d(c, &c->uhat, 3 * (int64_t)c->nn))
         return 1;
-    double** vecs[] = {&c->w, &c->lam, &c->r, &c->z, &c->p, &c->Ap, &c->dinv, &c->b, &c->tmp};
+    DevBuf<double>* vecs[] = {&c->w, &c->lam, &c->r, &c->z, &c->p, &c->Ap, &c->dinv, &c->b, &c->tmp};
     for (auto v : vecs)
         if (alloc_d(c, v, c->ndof)) return 1;
-    HIPCHK(c, hipMalloc((void**)&c->scal, 8 * sizeof(double)));
-    HIPCHK(c, hipHostMalloc((void**)&c->scal_host, 8 * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->mask, (size_t)c->ndof));
+    HIPCHK(c, c->scal.alloc(8));
+    HIPCHK(c, c->scal_host.alloc(8));
+    HIPCHK(c, c->mask.alloc((size_t)c->ndof));
     HIPCHK(c, hipMemset(c->mask, 0, (size_t)c->ndof));
     // FEA.add_input initial values (rm_shell_model.py:209-214): thickness 1e-3, others 1, uhat 0
     const int vgT = vec_grid(c->nT);
@@ -2185,56 +2177,7 @@ int femo_create_element(femo_ctx** out, int device, int32_t nn, int32_t nel, int
 void femo_destroy(femo_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    hipDeviceSynchronize();                   // stream2 / stream3 may still hold work that reads the buffers freed below
-    if (c->gdir) hipFree(c->gdir);
-    void* nptrs[] = {c->nm.W, c->nm.Fh, c->nm.wdot, c->nm.Fsw, c->nm.mu0, c->nm.mu1, c->nm.Lam, c->nm.Gh,
-                     c->sh.H, c->sh.ybuf, c->sh.tbuf, c->sh.acc, c->sh.bsum, c->sh.lev, c->sh.stage, c->sh.tout,
-                     c->sh.kpart, c->sh.kres};
-    for (void* p : nptrs)
-        if (p) hipFree(p);
-    void* mptrs[] = {c->mr_v, c->mr_y, c->mr_work, c->mr_scal, c->mr_io};
-    for (void* p : mptrs)
-        if (p) hipFree(p);
-    if (c->mr_scal_host) hipHostFree(c->mr_scal_host);
-    void* dptrs[] = {c->di.top_idx, c->di.sel, c->di.wdot, c->di.topbuf, c->di.topsave, c->di.gloc};
-    for (void* p : dptrs)
-        if (p) hipFree(p);
-    for (double* p : c->fp)
-        if (p) hipFree(p);
-    if (c->eq) hipFree(c->eq);
-    void* ptrs[] = {c->bi[0], c->bi[1], c->bi[2], c->bi[3], c->bi[4], c->ctag, c->gradbuf, c->csr_perm, c->csr_dest, c->csr_rowptr, c->csr_colidx, c->csr_vals, c->csr_ke, c->xyz, c->cells, c->cellp2, c->eorder, c->n2e_off, c->n2e_ent, c->ybuf, c->v2e_off, c->v2e_ent, c->hK, c->tab, c->tab_s, c->tab_pre, c->h, c->E, c->nu, c->rho, c->f, c->uhat, c->fcell, c->fledge,
-                    c->funode, c->fvnode, c->fM2, c->fM1, c->frnode, c->fMR, c->mask, c->w, c->lam, c->r, c->z, c->p, c->Ap, c->dinv, c->b, c->tmp,
-                    c->scal};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    void* fptrs[] = {c->fr.nf, c->fr.npiv, c->fr.dofs, c->fr.upmap, c->fr.parent, c->fr.left, c->fr.right, c->fr.level_nodes,
-                     c->fr.elem_front, c->fr.elem_map, c->fr.info, c->fr.poff, c->fr.soff, c->fr.doff, c->fr.linvoff, c->fr.P, c->fr.S, c->fr.Linv,
-                     c->fr.xoff, c->fr.X, c->fr.Xtmp, c->fr.Swork, c->fr.cinv0, c->fr.cinv1, c->fr.slot_of, c->fr.fel_off, c->fr.fel, c->fr.sweep_cnt, c->fr.ftasks,
-                     c->fr.btasks, c->fr.snap[0], c->fr.snap[1], c->fr.snap[2], c->fr.snap[3], c->fr.snap[4]};
-    for (void* p : fptrs)
-        if (p) hipFree(p);
-    if (c->fr.sweep_graph) hipGraphExecDestroy(c->fr.sweep_graph);
-    if (c->scal_host) hipHostFree(c->scal_host);
-    for (int i = 0; i < 4; ++i)
-        if (c->ev[i]) hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 2; ++i) {
-        if (c->ev_la[i]) hipEventDestroy(c->ev_la[i]);
-        if (c->ev_sp[i]) hipEventDestroy(c->ev_sp[i]);
-    }
-    for (int i = 0; i < 2; ++i)
-        if (c->ev_x[i]) hipEventDestroy(c->ev_x[i]);
-    for (int i = 0; i < 2; ++i)
-        if (c->ev_g[i]) hipEventDestroy(c->ev_g[i]);
-    if (c->stream_g) hipStreamDestroy(c->stream_g);
-    for (int i = 0; i < 3; ++i)
-        if (c->ev_a[i]) hipEventDestroy(c->ev_a[i]);
-    if (c->stream_a) hipStreamDestroy(c->stream_a);
-    for (int i = 0; i < 2; ++i)
-        if (c->ev_da[i]) hipEventDestroy(c->ev_da[i]);
-    if (c->stream_m) hipStreamDestroy(c->stream_m);
-    if (c->stream3) hipStreamDestroy(c->stream3);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    if (c->stream) hipStreamDestroy(c->stream);
+    hipDeviceSynchronize();                   // stream2 / stream3 may still hold work that reads the buffers the owners free
     delete c;
 }
 
@@ -2262,11 +2205,7 @@ int64_t femo_field_size(const femo_ctx* c, const char* name) {
 int femo_set_penalty_facets(femo_ctx* c, int32_t nf, const int32_t* cl, double beta) {
     HIPCHK(c, hipSetDevice(c->device));
     if (nf < 0 || (nf > 0 && !cl)) return fail(c, "bad facet list");
-    void* old[] = {c->fcell, c->fledge, c->funode, c->fvnode, c->fM2, c->fM1, c->frnode, c->fMR};
-    for (void* p : old)
-        if (p) hipFree(p);
-    c->fcell = c->fledge = c->funode = c->fvnode = c->frnode = nullptr;
-    c->fM2 = c->fM1 = c->fMR = nullptr;
+    c->fa = femo_ctx::Facets();
     c->nf = 0;
     c->beta = beta;
     c->penalty_dirty = true;
@@ -2287,24 +2226,24 @@ int femo_set_penalty_facets(femo_ctx* c, int32_t nf, const int32_t* cl, double b
         vn[2 * i] = hc[(size_t)k * c->nel + e];
         vn[2 * i + 1] = hc[(size_t)kb * c->nel + e];
     }
-    HIPCHK(c, hipMalloc((void**)&c->fcell, nf * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->fledge, nf * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->funode, 3 * (size_t)nf * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->fvnode, 2 * (size_t)nf * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->fM2, 9 * (size_t)nf * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->fM1, 4 * (size_t)nf * sizeof(double)));
-    HIPCHK(c, hipMemcpy(c->fcell, cell.data(), nf * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->fledge, le.data(), nf * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->funode, un.data(), un.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->fvnode, vn.data(), vn.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, c->fa.cell.alloc(nf));
+    HIPCHK(c, c->fa.ledge.alloc(nf));
+    HIPCHK(c, c->fa.unode.alloc(3 * (size_t)nf));
+    HIPCHK(c, c->fa.vnode.alloc(2 * (size_t)nf));
+    HIPCHK(c, c->fa.M2.alloc(9 * (size_t)nf));
+    HIPCHK(c, c->fa.M1.alloc(4 * (size_t)nf));
+    HIPCHK(c, hipMemcpy(c->fa.cell, cell.data(), nf * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->fa.ledge, le.data(), nf * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->fa.unode, un.data(), un.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->fa.vnode, vn.data(), vn.size() * sizeof(int), hipMemcpyHostToDevice));
     if (c->cr) {
         // CG2CR1: the three rotation nodes (edge midpoints) of the facet's cell and room for the 3 x 3 rotation block
         std::vector<int> rn(3 * (size_t)nf);
         for (int i = 0; i < nf; ++i)
             for (int a = 0; a < 3; ++a) rn[3 * i + a] = hp[(size_t)(c->nvc + a) * c->nel + cl[2 * i]] - c->nn;
-        HIPCHK(c, hipMalloc((void**)&c->frnode, rn.size() * sizeof(int)));
-        HIPCHK(c, hipMemcpy(c->frnode, rn.data(), rn.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc((void**)&c->fMR, 9 * (size_t)nf * sizeof(double)));
+        HIPCHK(c, c->fa.rnode.alloc(rn.size()));
+        HIPCHK(c, hipMemcpy(c->fa.rnode, rn.data(), rn.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, c->fa.MR.alloc(9 * (size_t)nf));
     }
     c->nf = nf;
     return 0;
@@ -2326,7 +2265,7 @@ int femo_set_strong_dofs(femo_ctx* c, int32_t n, const int32_t* dofs) {
 int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
     if (name && std::string(name) == "dirichlet" && !c->gdir) {
-        HIPCHK(c, hipMalloc((void**)&c->gdir, (size_t)c->ndof * sizeof(double)));
+        HIPCHK(c, c->gdir.alloc((size_t)c->ndof));
         HIPCHK(c, hipMemset(c->gdir, 0, (size_t)c->ndof * sizeof(double)));
     }
     int64_t len;
@@ -2450,7 +2389,7 @@ int femo_force_to_pressure(femo_ctx* c, const double* force, double* pressure, d
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = 3 * (int64_t)c->nn;
     for (int i = 0; i < 6; ++i)
-        if (!c->fp[i]) HIPCHK(c, hipMalloc((void**)&c->fp[i], (size_t)n * sizeof(double)));
+        if (!c->fp[i]) HIPCHK(c, c->fp[i].alloc((size_t)n));
     double *x = c->fp[0], *r = c->fp[1], *z = c->fp[2], *p = c->fp[3], *Ap = c->fp[4], *dg = c->fp[5];
     const int vg = vec_grid(n), eg = nblk(c->nel, 128);
     const MeshDev m = mesh_dev(c);
@@ -2509,14 +2448,12 @@ int femo_element_matrices(femo_ctx* c, int32_t first, int32_t count, double* Ke)
     HIPCHK(c, hipSetDevice(c->device));
     if (first < 0 || count < 0 || first + count > c->nel) return fail(c, "element range out of bounds");
     if (count == 0) return 0;
-    double* d = nullptr;
-    const size_t bytes = (size_t)count * c->ld * c->ld * sizeof(double);
-    HIPCHK(c, hipMalloc((void**)&d, bytes));
+    DevBuf<double> d;
+    const size_t len = (size_t)count * c->ld * c->ld;
+    HIPCHK(c, d.alloc(len));
     ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, count, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, first, count, d);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(Ke, d, bytes, hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIPCHK(c, e);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(Ke, d, len * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2795,51 +2732,40 @@ static int dRdarg_T_dev(femo_ctx* c, const std::string& arg, const double* lam, 
 
 int femo_dfunctional(femo_ctx* c, const char* name, const char* wrt, double* out, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, std::max<int64_t>(n, 1) * sizeof(double)));
-    int rc = dfunctional_dev(c, name ? name : "", wrt ? wrt : "", d, n);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    hipFree(d);
-    return rc;
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
+    if (int rc = dfunctional_dev(c, name ? name : "", wrt ? wrt : "", d, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int femo_dRdarg_T(femo_ctx* c, const char* arg, const double* lambda, double* out, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, std::max<int64_t>(n, 1) * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     hipMemsetAsync(d, 0, std::max<int64_t>(n, 1) * sizeof(double), c->stream);
     hipMemcpyAsync(c->lam, lambda, (size_t)c->ndof * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    int rc = dRdarg_T_dev(c, arg ? arg : "", c->lam, 1.0, d, n);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    hipFree(d);
-    return rc;
+    if (int rc = dRdarg_T_dev(c, arg ? arg : "", c->lam, 1.0, d, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, double* out, int64_t n, int32_t* iters,
                         double* relres) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fn(functional ? functional : ""), a(arg ? arg : "");
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, std::max<int64_t>(n, 1) * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     int rc = dfunctional_dev(c, fn, "disp_solid", c->b, c->ndof);          // dJ/dw
     if (!rc) rc = solve_dispatch(c, c->b, c->lam, true, iters, relres);     // lambda = K^-1 dJ/dw
     if (!rc) rc = dfunctional_dev(c, fn, a, d, n);                          // dJ/d arg (zero-fills d)
     if (!rc) rc = dRdarg_T_dev(c, a, c->lam, -1.0, d, n);                   // - (dR/d arg)^T lambda
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    hipFree(d);
-    return rc;
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 
@@ -2872,8 +2798,8 @@ int femo_solve_linear_multi(femo_ctx* c, int32_t nrhs, const double* rhs, double
     HIPCHK(c, hipSetDevice(c->device));
     if (nrhs < 1 || !rhs || !x) return fail(c, "femo_solve_linear_multi: nrhs >= 1 right-hand sides, one vector after the other");
     const size_t n = (size_t)c->ndof;
-    double* Bd = mr_io_buffer(c, 2 * (size_t)nrhs * n);
-    if (!Bd) return 1;
+    HIPCHK(c, c->mr_io.grow(2 * (size_t)nrhs * n));
+    double* Bd = c->mr_io;
     double* Xd = Bd + (size_t)nrhs * n;
     std::vector<double*> B(nrhs), X(nrhs);
     for (int r = 0; r < nrhs; ++r) { B[r] = Bd + r * n; X[r] = Xd + r * n; }
@@ -2901,8 +2827,8 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
     const int keep_sel = c->csel;
     for (int i = 0; i < nfun; ++i)
         if (subdomains && (subdomains[i] < -1 || subdomains[i] >= c->ntags)) return fail(c, "unknown sub-domain");
-    double* Bd = mr_io_buffer(c, (size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1)));
-    if (!Bd) return 1;
+    HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
+    double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
     std::vector<double*> B(nfun), X(nfun);
     for (int i = 0; i < nfun; ++i) { B[i] = Bd + i * nd; X[i] = Xd + i * nd; }
@@ -3045,18 +2971,18 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
         fr.h_soff = soff;
     }
     fr.linv_doubles = linvoff[ntree];
-#define UPI(dst, src, n) do { HIPCHK(c, hipMalloc((void**)&dst, std::max<size_t>((size_t)(n), 1) * sizeof(*dst))); \
+#define UPI(dst, src, n) do { HIPCHK(c, dst.alloc(std::max<size_t>((size_t)(n), 1))); \
         HIPCHK(c, hipMemcpy(dst, src, (size_t)(n) * sizeof(*dst), hipMemcpyHostToDevice)); } while (0)
     UPI(fr.nf, nf, ntree); UPI(fr.npiv, npiv, ntree); UPI(fr.parent, parent, ntree); UPI(fr.left, left, ntree);
     UPI(fr.right, right, ntree); UPI(fr.level_nodes, level_nodes, ntree); UPI(fr.dofs, front_dofs, ndofs_total);
     UPI(fr.upmap, up_map, ndofs_total); UPI(fr.elem_front, elem_front, c->nel); UPI(fr.elem_map, elem_map, (size_t)c->nel * c->ld);
-    HIPCHK(c, hipMalloc((void**)&fr.poff, (ntree + 1) * sizeof(long long)));
+    HIPCHK(c, fr.poff.alloc(ntree + 1));
     HIPCHK(c, hipMemcpy(fr.poff, poff.data(), (ntree + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&fr.soff, std::max(ntree, 1) * sizeof(long long)));
+    HIPCHK(c, fr.soff.alloc(std::max(ntree, 1)));
     HIPCHK(c, hipMemcpy(fr.soff, soff.data(), ntree * sizeof(long long), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&fr.doff, (ntree + 1) * sizeof(long long)));
+    HIPCHK(c, fr.doff.alloc(ntree + 1));
     HIPCHK(c, hipMemcpy(fr.doff, dof_off, (ntree + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&fr.linvoff, (ntree + 1) * sizeof(long long)));
+    HIPCHK(c, fr.linvoff.alloc(ntree + 1));
     HIPCHK(c, hipMemcpy(fr.linvoff, linvoff.data(), (ntree + 1) * sizeof(long long), hipMemcpyHostToDevice));
     {
         // X = L11^-1 of every front of the wide levels (leading dimension ldx_of(npiv)); Xtmp: scratch of the same shape
@@ -3070,16 +2996,16 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
             xoff[t + 1] = xoff[t] + ld * ld;
         }
         fr.x_doubles = xoff[ntree];
-        HIPCHK(c, hipMalloc((void**)&fr.xoff, (ntree + 1) * sizeof(long long)));
+        HIPCHK(c, fr.xoff.alloc(ntree + 1));
         HIPCHK(c, hipMemcpy(fr.xoff, xoff.data(), (ntree + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc((void**)&fr.X, std::max<size_t>((size_t)fr.x_doubles, 1) * sizeof(double)));
-        HIPCHK(c, hipMalloc((void**)&fr.Xtmp, std::max<size_t>((size_t)fr.x_doubles, 1) * sizeof(double)));
+        HIPCHK(c, fr.X.alloc(std::max<size_t>((size_t)fr.x_doubles, 1)));
+        HIPCHK(c, fr.Xtmp.alloc(std::max<size_t>((size_t)fr.x_doubles, 1)));
         // scratch for the diagonal-block inverses of the other levels (needed only between k_diag_block and k_panel_rows)
         int max_cnt = 0;
         for (int L = 0; L < nlevels; ++L)
             if (!fr.h_level_wide[L]) max_cnt = std::max(max_cnt, level_off[L + 1] - level_off[L]);
         fr.swork_slots = std::max(1, std::min(max_cnt, std::max(1, c->opt.swork_slots)));
-        HIPCHK(c, hipMalloc((void**)&fr.Swork, (size_t)fr.swork_slots * SPD * SPD * sizeof(double)));
+        HIPCHK(c, fr.Swork.alloc((size_t)fr.swork_slots * SPD * SPD));
     }
     {
         // row maps of the extend-add gather: for every row of a front, the row of each child's front that lands there
@@ -3147,15 +3073,15 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
             UPI(fr.fel_off, fel_off.data(), cnt0 + 1); UPI(fr.fel, fel.data(), c->nel);
         }
         UPI(fr.ftasks, ft.data(), ft.size()); UPI(fr.btasks, bt.data(), bt.size());
-        HIPCHK(c, hipMalloc((void**)&fr.sweep_cnt, (size_t)std::max(ntree, 1) * 2 * sizeof(int)));
+        HIPCHK(c, fr.sweep_cnt.alloc((size_t)std::max(ntree, 1) * 2));
     }
-    HIPCHK(c, hipMalloc((void**)&fr.P, (size_t)std::max<long long>(fr.p_doubles, 1) * sizeof(double)));
+    HIPCHK(c, fr.P.alloc((size_t)std::max<long long>(fr.p_doubles, 1)));
     HIPCHK(c, hipMemset(fr.P, 0, (size_t)std::max<long long>(fr.p_doubles, 1) * sizeof(double)));   // once: the upper triangles of L11 are never written
     // two doubles of padding: the gathering updates read Sc[0] of a child without a Schur block (or of the front itself when a
     // child is missing) as their "safe address", which may be the very end of the arena
-    HIPCHK(c, hipMalloc((void**)&fr.S, (size_t)(std::max<long long>(fr.s_doubles, 1) + 2) * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&fr.Linv, (size_t)std::max<long long>(fr.linv_doubles, 1) * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&fr.info, sizeof(int)));
+    HIPCHK(c, fr.S.alloc((size_t)(std::max<long long>(fr.s_doubles, 1) + 2)));
+    HIPCHK(c, fr.Linv.alloc((size_t)std::max<long long>(fr.linv_doubles, 1)));
+    HIPCHK(c, fr.info.alloc(1));
     // dynamic LDS of the one-workgroup-per-front sweeps: forward maxnp + SMALL_PART, backward maxnp + maxnb + SMALL_PART
     // doubles, where the two maxima of a level may come from different fronts
     int max_sweep = fr.max_nf + SMALL_PART;
@@ -3184,7 +3110,7 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block2<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block2_lds_blocks(NBO / NB) * sizeof(blk32))));
     fr.ready = true;
-    if (fr.sweep_graph) { hipGraphExecDestroy(fr.sweep_graph); fr.sweep_graph = nullptr; }     // captured for another plan
+    fr.sweep_graph.reset();                // captured for another plan
     fr.factored = false;
     return 0;
 }
@@ -3225,7 +3151,7 @@ int femo_sweep_profile(femo_ctx* c, double* out, int64_t n) {
     if (!fr.factored)
         if (int rc = frontal_factorize(c)) return rc;
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(c->ndof)), dim3(256), 0, c->stream, c->z, 1.0, (int64_t)c->ndof);
-    std::vector<hipEvent_t> mf, mb;
+    std::vector<Event> mf, mb;
     int rc = frontal_fwd(c, c->z, 0, fr.nlevels, &mf);
     if (!rc) rc = frontal_bwd(c, c->z, 0, fr.nlevels, &mb);
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3242,8 +3168,6 @@ int femo_sweep_profile(femo_ctx* c, double* out, int64_t n) {
     } else if (!rc) {
         rc = fail(c, "internal: unexpected number of sweep marks");
     }
-    for (auto e : mf) hipEventDestroy(e);
-    for (auto e : mb) hipEventDestroy(e);
     return rc;
 }
 
@@ -3260,7 +3184,7 @@ int femo_sweep_profile_multi(femo_ctx* c, int32_t nrhs, double* out, int64_t n) 
     if (mr_alloc(c)) return 1;
     hipLaunchKernelGGL(k_fill, dim3(vec_grid((int64_t)c->ndof * nrhs)), dim3(256), 0, c->stream, c->mr_v, 1.0, (int64_t)c->ndof * nrhs);
     if (join_xinv(c)) return 1;
-    std::vector<hipEvent_t> mk;
+    std::vector<Event> mk;
     int rc = nrhs == 2 ? frontal_solve_multi<2>(c, c->mr_v, c->mr_y, &mk) : frontal_solve_multi<4>(c, c->mr_v, c->mr_y, &mk);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, "synchronisation failed");
     if (!rc && (int)mk.size() == 2 * fr.nlevels + 2) {
@@ -3274,7 +3198,6 @@ int femo_sweep_profile_multi(femo_ctx* c, int32_t nrhs, double* out, int64_t n) 
     } else if (!rc) {
         rc = fail(c, "internal: unexpected number of sweep marks");
     }
-    for (auto e : mk) hipEventDestroy(e);
     return rc;
 }
 
@@ -3387,17 +3310,14 @@ int femo_field_gradient_vec(femo_ctx* c, const char* functional, const char* arg
     HIPCHK(c, hipSetDevice(c->device));
     double* l = vec_by_id(c, lam);
     if (!l) return fail(c, "bad vector id");
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, std::max<int64_t>(n, 1) * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     int rc = dfunctional_dev(c, functional ? functional : "", arg ? arg : "", d, n);
     if (!rc) rc = dRdarg_T_dev(c, arg ? arg : "", l, -1.0, d, n);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    hipFree(d);
-    return rc;
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 
@@ -3419,16 +3339,16 @@ int femo_dist_setup(femo_ctx* c, int32_t ntop, const int32_t* top_idx, int32_t n
     d.ntop = ntop; d.nranks = nranks; d.nl = n_local_levels; d.nsel = nsel;
     std::vector<double> w((size_t)c->ndof, 1.0);
     for (int i = 0; i < ntop; ++i) w[top_idx[i]] = 1.0 / nranks;
-    HIPCHK(c, hipMalloc((void**)&d.wdot, (size_t)c->ndof * sizeof(double)));
+    HIPCHK(c, d.wdot.alloc((size_t)c->ndof));
     HIPCHK(c, hipMemcpy(d.wdot, w.data(), (size_t)c->ndof * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&d.top_idx, (size_t)std::max(ntop, 1) * sizeof(int)));
+    HIPCHK(c, d.top_idx.alloc((size_t)std::max(ntop, 1)));
     if (ntop) HIPCHK(c, hipMemcpy(d.top_idx, top_idx, (size_t)ntop * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&d.topbuf, (size_t)(ntop + 2) * sizeof(double)));
+    HIPCHK(c, d.topbuf.alloc((size_t)(ntop + 2)));
     HIPCHK(c, hipMemset(d.topbuf, 0, (size_t)(ntop + 2) * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&d.topsave, (size_t)std::max(ntop, 1) * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&d.sel, (size_t)std::max(nsel, 1) * sizeof(int)));
+    HIPCHK(c, d.topsave.alloc((size_t)std::max(ntop, 1)));
+    HIPCHK(c, d.sel.alloc((size_t)std::max(nsel, 1)));
     if (nsel) HIPCHK(c, hipMemcpy(d.sel, sel, (size_t)nsel * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&d.gloc, (size_t)std::max<int64_t>(std::max<int64_t>(c->nT, 3 * c->nF), 1) * sizeof(double)));
+    HIPCHK(c, d.gloc.alloc((size_t)std::max<int64_t>(std::max<int64_t>(c->nT, 3 * c->nF), 1)));
     d.ready = true;
     return 0;
 }
@@ -3691,7 +3611,7 @@ int femo_vec_mask_zero(femo_ctx* c, int32_t id) {
 // thickness-gradient accumulator on the device:  g += scale * y^T (dK/dh) x   or   g += scale * y^T (dM/dh) x
 int femo_grad_reset(femo_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->gradbuf) HIPCHK(c, hipMalloc((void**)&c->gradbuf, (size_t)std::max<int64_t>(c->nT, 1) * sizeof(double)));
+    if (!c->gradbuf) HIPCHK(c, c->gradbuf.alloc((size_t)std::max<int64_t>(c->nT, 1)));
     HIPCHK(c, hipMemsetAsync(c->gradbuf, 0, (size_t)c->nT * sizeof(double), c->stream));
     return 0;
 }
@@ -3731,15 +3651,13 @@ int femo_newmark_setup(femo_ctx* c, int32_t time_levels, double dt) {
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (time_levels < 2 || !(dt > 0)) return fail(c, "femo_newmark_setup: need at least two time levels and dt > 0");
-    void* old[] = {nm.W, nm.Fh, nm.wdot, nm.Fsw, nm.mu0, nm.mu1, nm.Lam, nm.Gh};
-    for (void* p : old) if (p) hipFree(p);
     nm = femo_ctx::Newmark();
     const size_t n = (size_t)c->ndof;
-    HIPCHK(c, hipMalloc((void**)&nm.W, (size_t)time_levels * n * sizeof(double)));
+    HIPCHK(c, nm.W.alloc((size_t)time_levels * n));
     HIPCHK(c, hipMemset(nm.W, 0, (size_t)time_levels * n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&nm.wdot, n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&nm.mu0, n * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&nm.mu1, n * sizeof(double)));
+    HIPCHK(c, nm.wdot.alloc(n));
+    HIPCHK(c, nm.mu0.alloc(n));
+    HIPCHK(c, nm.mu1.alloc(n));
     nm.levels = time_levels; nm.dt = dt; nm.a = 2.0 / (dt * dt); nm.b = 2.0 / dt;
     if (0.5 != c->op_aK || nm.a != c->op_aM) { c->op_aK = 0.5; c->op_aM = nm.a; operator_changed(c); }
     nm.ready = true;
@@ -3752,10 +3670,9 @@ int femo_newmark_set_forces(femo_ctx* c, const double* f_history, int32_t levels
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
     if (levels_given < 1 || !f_history) return fail(c, "empty force history");
-    if (nm.Fh) { hipFree(nm.Fh); nm.Fh = nullptr; }
-    const size_t bytes = (size_t)levels_given * 3 * c->nF * sizeof(double);
-    HIPCHK(c, hipMalloc((void**)&nm.Fh, bytes));
-    HIPCHK(c, hipMemcpy(nm.Fh, f_history, bytes, hipMemcpyHostToDevice));
+    const size_t len = (size_t)levels_given * 3 * c->nF;
+    HIPCHK(c, nm.Fh.alloc(len));
+    HIPCHK(c, hipMemcpy(nm.Fh, f_history, len * sizeof(double), hipMemcpyHostToDevice));
     nm.flevels = levels_given;
     return 0;
 }
@@ -3767,7 +3684,7 @@ int femo_newmark_set_constant_load(femo_ctx* c, const double* F) {
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
     nm.has_sw = F != nullptr;
     if (!F) return 0;
-    if (!nm.Fsw) HIPCHK(c, hipMalloc((void**)&nm.Fsw, (size_t)c->ndof * sizeof(double)));
+    if (!nm.Fsw) HIPCHK(c, nm.Fsw.alloc((size_t)c->ndof));
     HIPCHK(c, hipMemcpy(nm.Fsw, F, (size_t)c->ndof * sizeof(double), hipMemcpyHostToDevice));
     return 0;
 }
@@ -3826,7 +3743,7 @@ int femo_newmark_set_history(femo_ctx* c, int32_t which, const double* H) {     
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
     if (which != 0 && which != 2) return fail(c, "which: 0 displacement history, 2 adjoint history");
     const size_t hb = (size_t)nm.levels * c->ndof * sizeof(double);
-    if (which == 2 && !nm.Lam) HIPCHK(c, hipMalloc((void**)&nm.Lam, hb));
+    if (which == 2 && !nm.Lam) HIPCHK(c, nm.Lam.alloc((size_t)nm.levels * c->ndof));
     HIPCHK(c, hipMemcpy(which == 0 ? nm.W : nm.Lam, H, hb, hipMemcpyHostToDevice));
     return 0;
 }
@@ -3843,7 +3760,7 @@ static int newmark_adjoint_sweep(femo_ctx* c, int32_t levels) {
     const int vg = vec_grid(n);
     const unsigned char* mask = c->has_mask ? c->mask : nullptr;
     const size_t hb = (size_t)nm.levels * n * sizeof(double);
-    if (!nm.Lam) HIPCHK(c, hipMalloc((void**)&nm.Lam, hb));
+    if (!nm.Lam) HIPCHK(c, nm.Lam.alloc((size_t)nm.levels * n));
     HIPCHK(c, hipMemsetAsync(nm.Lam, 0, hb, c->stream));
     HIPCHK(c, hipMemsetAsync(nm.mu0, 0, (size_t)n * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(c->lam, 0, (size_t)n * sizeof(double), c->stream));
@@ -3872,7 +3789,7 @@ int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
     if (levels < 1 || levels > nm.levels) return fail(c, "bad number of levels");
     const int64_t n = c->ndof;
     const size_t hb = (size_t)nm.levels * n * sizeof(double);
-    if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, hb));
+    if (!nm.Gh) HIPCHK(c, nm.Gh.alloc((size_t)nm.levels * n));
     HIPCHK(c, hipMemcpyAsync(nm.Gh, G, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return newmark_adjoint_sweep(c, levels);
 }
@@ -3900,11 +3817,11 @@ int femo_newmark_residual_T(femo_ctx* c, int32_t levels, double* g_t, double* dF
     const MeshDev m = mesh_dev(c);
     const FieldsDev f = fields_dev(c);
     const int g = nblk(c->nel, EB);
-    if (!c->gradbuf) HIPCHK(c, hipMalloc((void**)&c->gradbuf, (size_t)std::max<int64_t>(c->nT, 1) * sizeof(double)));
+    if (!c->gradbuf) HIPCHK(c, c->gradbuf.alloc((size_t)std::max<int64_t>(c->nT, 1)));
     HIPCHK(c, hipMemsetAsync(c->gradbuf, 0, (size_t)c->nT * sizeof(double), c->stream));
-    double* dFd = nullptr;
+    DevBuf<double> dFd;
     const size_t fl = (size_t)3 * c->nF;
-    HIPCHK(c, hipMalloc((void**)&dFd, (size_t)levels * fl * sizeof(double)));
+    HIPCHK(c, dFd.alloc((size_t)levels * fl));
     hipMemsetAsync(dFd, 0, (size_t)levels * fl * sizeof(double), c->stream);
     // the velocity recursion of the stored history is re-marched in a SCRATCH vector (mu1: free once the adjoint sweep is done) --
     // nm.wdot stays the velocity of the last level the march reached, which femo_newmark_ptr(ctx, 1) exposes
@@ -3919,12 +3836,10 @@ int femo_newmark_residual_T(femo_ctx* c, int32_t levels, double* g_t, double* dF
         ELEM_LAUNCH(c, k_dRdf_T, NOEXTRA, g, EB, m, f, c->tab, li, -1.0, dFd + (size_t)i * fl);
         hipLaunchKernelGGL(k_newmark_wdot, dim3(vg), dim3(256), 0, c->stream, wdv, wi, wo, nm.b, n);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && g_t) e = hipMemcpy(g_t, c->gradbuf, (size_t)c->nT * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && dF) e = hipMemcpy(dF, dFd, (size_t)levels * fl * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(dFd);
-    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (g_t) HIPCHK(c, hipMemcpy(g_t, c->gradbuf, (size_t)c->nT * sizeof(double), hipMemcpyDeviceToHost));
+    if (dF) HIPCHK(c, hipMemcpy(dF, dFd, (size_t)levels * fl * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -3943,18 +3858,18 @@ int femo_newmark_jvp(femo_ctx* c, int32_t levels, const double* dY, const double
     const int vg = vec_grid(n);
     const unsigned char* mask = c->has_mask ? c->mask : nullptr;
     const size_t hb = (size_t)nm.levels * n * sizeof(double);
-    if (!nm.Lam) HIPCHK(c, hipMalloc((void**)&nm.Lam, hb));
-    if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, hb));
+    if (!nm.Lam) HIPCHK(c, nm.Lam.alloc((size_t)nm.levels * n));
+    if (!nm.Gh) HIPCHK(c, nm.Gh.alloc((size_t)nm.levels * n));
     HIPCHK(c, hipMemsetAsync(nm.Lam, 0, hb, c->stream));
     if (dY) HIPCHK(c, hipMemcpyAsync(nm.Gh, dY, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    double *dh = nullptr, *dFd = nullptr;
+    DevBuf<double> dh, dFd;
     const size_t fl = (size_t)3 * c->nF;
     if (dthickness) {
-        HIPCHK(c, hipMalloc((void**)&dh, (size_t)std::max<int64_t>(c->nT, 1) * sizeof(double)));
+        HIPCHK(c, dh.alloc((size_t)std::max<int64_t>(c->nT, 1)));
         HIPCHK(c, hipMemcpyAsync(dh, dthickness, (size_t)c->nT * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     if (dF) {
-        HIPCHK(c, hipMalloc((void**)&dFd, (size_t)levels * fl * sizeof(double)));
+        HIPCHK(c, dFd.alloc((size_t)levels * fl));
         HIPCHK(c, hipMemcpyAsync(dFd, dF, (size_t)levels * fl * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     const MeshDev m = mesh_dev(c);
@@ -3998,8 +3913,6 @@ int femo_newmark_jvp(femo_ctx* c, int32_t levels, const double* dY, const double
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (dh) hipFree(dh);
-    if (dFd) hipFree(dFd);
     if (rc) return rc;
     HIPCHK(c, e);
     return 0;
@@ -4017,8 +3930,8 @@ int femo_newmark_tangent(femo_ctx* c, const double* dR, int32_t levels) {
     const int vg = vec_grid(n);
     const unsigned char* mask = c->has_mask ? c->mask : nullptr;
     const size_t hb = (size_t)nm.levels * n * sizeof(double);
-    if (!nm.Lam) HIPCHK(c, hipMalloc((void**)&nm.Lam, hb));
-    if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, hb));
+    if (!nm.Lam) HIPCHK(c, nm.Lam.alloc((size_t)nm.levels * n));
+    if (!nm.Gh) HIPCHK(c, nm.Gh.alloc((size_t)nm.levels * n));
     HIPCHK(c, hipMemsetAsync(nm.Lam, 0, hb, c->stream));
     HIPCHK(c, hipMemcpyAsync(nm.Gh, dR, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(nm.Lam, nm.Gh, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -4049,16 +3962,6 @@ int femo_newmark_tangent(femo_ctx* c, const double* dR, int32_t levels) {
 // of femo_alpha/dynamic_rm_shell/plate_sim.py:427-449, the constraint the gust examples leave commented out
 // (ex_gust_response_opt.py:320,329,724; ex_lpc_gust_response_opt.py:49,55,445).  m, rho, alpha and the regularisation coefficient are
 // the static path's settings (femo_set_stress_params, femo_set_stress_alpha(sel = -1), option "stress_regularization").
-static int sh_grow(femo_ctx* c, int k, double** p, size_t n) {
-    size_t& cap = c->sh.cap[k];
-    if (cap >= n && *p) return 0;
-    if (*p) hipFree(*p);
-    *p = nullptr; cap = 0;
-    HIPCHK(c, hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(double)));
-    cap = n;
-    return 0;
-}
-
 // per_level (host, levels; may be null), total (host; may be null).  grad: g_t (host, thickness length; may be null) = dS/dt;
 // dS/dW level-major into nm.Gh (seed) and / or the host array G (may be null).  The level chunks of the gradient share one scratch.
 static int stress_history_run(femo_ctx* c, int32_t levels, const double* H, bool grad, double* per_level, double* total, double* g_t,
@@ -4072,7 +3975,7 @@ static int stress_history_run(femo_ctx* c, int32_t levels, const double* H, bool
     const int64_t n = c->ndof;
     const double* Hd = nm.W;
     if (H) {               // the caller's history goes to a buffer of its own: nm.W stays the march's (femo_newmark_residual_T reads it)
-        if (sh_grow(c, 0, &sh.H, (size_t)levels * n)) return 1;
+        HIPCHK(c, sh.H.grow((size_t)levels * n));
         HIPCHK(c, hipMemcpyAsync(sh.H, H, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         Hd = sh.H;
     }
@@ -4086,17 +3989,19 @@ static int stress_history_run(femo_ctx* c, int32_t levels, const double* H, bool
     if (grad) chunk = c->opt.sh_chunk > 0 ? c->opt.sh_chunk : (int)std::max<size_t>(1, ((size_t)128 << 20) / (lev_doubles * sizeof(double)));
     chunk = std::min(chunk, (int)levels);
     auto lpg_of = [&](int nlev) { return c->opt.sh_levels_per_thread > 0 ? c->opt.sh_levels_per_thread : std::max(1, (nlev + fill - 1) / fill); };
-    if (sh_grow(c, 4, &sh.bsum, (size_t)levels * nbx) || sh_grow(c, 5, &sh.lev, (size_t)levels)) return 1;
+    HIPCHK(c, sh.bsum.grow((size_t)levels * nbx));
+    HIPCHK(c, sh.lev.grow((size_t)levels));
     double* gdst = nullptr;
     if (grad) {
-        if (sh_grow(c, 1, &sh.ybuf, (size_t)chunk * lev_doubles) || sh_grow(c, 2, &sh.tbuf, (size_t)chunk * nel * nvc) ||      // at most `chunk` level groups
-            sh_grow(c, 3, &sh.acc, (size_t)nel * nvc) || sh_grow(c, 7, &sh.tout, (size_t)std::max<int64_t>(c->nT, 1)))
-            return 1;
+        HIPCHK(c, sh.ybuf.grow((size_t)chunk * lev_doubles));
+        HIPCHK(c, sh.tbuf.grow((size_t)chunk * nel * nvc));      // at most `chunk` level groups
+        HIPCHK(c, sh.acc.grow((size_t)nel * nvc));
+        HIPCHK(c, sh.tout.grow((size_t)std::max<int64_t>(c->nT, 1)));
         if (seed) {
-            if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, (size_t)nm.levels * n * sizeof(double)));
+            if (!nm.Gh) HIPCHK(c, nm.Gh.alloc((size_t)nm.levels * n));
             gdst = nm.Gh;
         } else if (G) {
-            if (sh_grow(c, 6, &sh.stage, (size_t)chunk * n)) return 1;
+            HIPCHK(c, sh.stage.grow((size_t)chunk * n));
         }
     }
     const MeshDev m = mesh_dev(c);
@@ -4195,7 +4100,7 @@ static int disp_history_run(femo_ctx* c, int32_t levels, const double* H, int32_
     const int64_t n = c->ndof, ncols = components == 1 ? (int64_t)c->ndof_u : n;
     const double* Hd = nm.W;
     if (H) {               // the caller's history goes to the buffer of its own: nm.W stays the march's
-        if (sh_grow(c, 0, &sh.H, (size_t)levels * n)) return 1;
+        HIPCHK(c, sh.H.grow((size_t)levels * n));
         HIPCHK(c, hipMemcpyAsync(sh.H, H, (size_t)levels * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         Hd = sh.H;
     }
@@ -4203,7 +4108,8 @@ static int disp_history_run(femo_ctx* c, int32_t levels, const double* H, int32_
     const int64_t items = vec ? ncols / 2 : ncols;
     // ~4096 workgroups over all levels, none with fewer than 256 items
     const int nbx = (int)std::max<int64_t>(1, std::min<int64_t>((4096 + levels - 1) / levels, (items + 255) / 256));
-    if (sh_grow(c, 8, &sh.kpart, (size_t)levels * nbx * 3) || sh_grow(c, 9, &sh.kres, (size_t)4 * levels + 2)) return 1;
+    HIPCHK(c, sh.kpart.grow((size_t)levels * nbx * 3));
+    HIPCHK(c, sh.kres.grow((size_t)4 * levels + 2));
     const double cu = rho * std::fabs(scaler);
     if (vec) hipLaunchKernelGGL(k_disp_ks_partial<true>, dim3(nbx, levels), dim3(256), 0, c->stream, Hd, n, ncols, cu, sh.kpart);
     else hipLaunchKernelGGL(k_disp_ks_partial<false>, dim3(nbx, levels), dim3(256), 0, c->stream, Hd, n, ncols, cu, sh.kpart);
@@ -4228,10 +4134,10 @@ static int disp_history_run(femo_ctx* c, int32_t levels, const double* H, int32_
                                                                   : (int)std::max<int64_t>(1, ((int64_t)128 << 20) / (n * (int64_t)sizeof(double))));
         double* dst = nullptr;
         if (seed) {
-            if (!nm.Gh) HIPCHK(c, hipMalloc((void**)&nm.Gh, (size_t)nm.levels * n * sizeof(double)));
+            if (!nm.Gh) HIPCHK(c, nm.Gh.alloc((size_t)nm.levels * n));
             dst = nm.Gh;
         } else if (G) {
-            if (sh_grow(c, 6, &sh.stage, (size_t)chunk * n)) return 1;
+            HIPCHK(c, sh.stage.grow((size_t)chunk * n));
             dst = sh.stage;
         }
         const int64_t gitems = vec ? n / 2 : n;
@@ -4276,16 +4182,13 @@ int femo_set_csr_map(femo_ctx* c, int32_t nnz, int64_t ncontrib, const int32_t* 
         if (perm[k] < 0 || perm[k] >= ncontrib || dest[k] < 0 || dest[k] >= nnz || (k && dest[k] < dest[k - 1]))
             return fail(c, "bad CSR map (range or ordering)");
     }
-    void* old[] = {c->csr_perm, c->csr_dest, c->csr_vals, c->csr_ke};
-    for (void* p : old) if (p) hipFree(p);
-    c->csr_perm = c->csr_dest = nullptr; c->csr_vals = c->csr_ke = nullptr;
-    HIPCHK(c, hipMalloc((void**)&c->csr_perm, (size_t)ncontrib * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_dest, (size_t)ncontrib * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_vals, (size_t)nnz * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_ke, (size_t)ncontrib * sizeof(double)));
-    HIPCHK(c, hipMemcpy(c->csr_perm, perm, (size_t)ncontrib * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->csr_dest, dest, (size_t)ncontrib * sizeof(int), hipMemcpyHostToDevice));
-    c->csr_ncontrib = ncontrib; c->csr_nnz = nnz;
+    HIPCHK(c, c->csr.perm.alloc((size_t)ncontrib));
+    HIPCHK(c, c->csr.dest.alloc((size_t)ncontrib));
+    HIPCHK(c, c->csr.vals.alloc((size_t)nnz));
+    HIPCHK(c, c->csr.ke.alloc((size_t)ncontrib));
+    HIPCHK(c, hipMemcpy(c->csr.perm, perm, (size_t)ncontrib * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->csr.dest, dest, (size_t)ncontrib * sizeof(int), hipMemcpyHostToDevice));
+    c->csr.ncontrib = ncontrib; c->csr.nnz = nnz;
     return 0;
 }
 
@@ -4294,46 +4197,45 @@ int femo_build_csr_map(femo_ctx* c, int32_t* nnz_out) {
     HIPCHK(c, hipSetDevice(c->device));
     const long long nc = (long long)c->nel * c->ld * c->ld;
     if (nc >= (1ll << 31)) return fail(c, "CSR export: more than 2^31 element contributions (the matrix-free solvers have no such limit)");
-    void* old[] = {c->csr_perm, c->csr_dest, c->csr_rowptr, c->csr_colidx, c->csr_vals, c->csr_ke};
-    for (void* p : old) if (p) hipFree(p);
-    c->csr_perm = c->csr_dest = c->csr_rowptr = c->csr_colidx = nullptr; c->csr_vals = c->csr_ke = nullptr;
-    long long *k0 = nullptr, *k1 = nullptr;
-    int *v0 = nullptr, *flags = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0, t2 = 0;
-    HIPCHK(c, hipMalloc((void**)&k0, nc * sizeof(long long)));
-    HIPCHK(c, hipMalloc((void**)&k1, nc * sizeof(long long)));
-    HIPCHK(c, hipMalloc((void**)&v0, nc * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_perm, nc * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_dest, nc * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&flags, nc * sizeof(int)));
-    const unsigned gb = (unsigned)((nc + 255) / 256);
-    hipLaunchKernelGGL(k_csr_keys, dim3(gb), dim3(256), 0, c->stream, nc, c->nel, c->ld, c->npc, c->ndof_u, (long long)c->ndof, (const int*)c->cellp2,
-                       (const int*)c->cells, k0, v0, c->cr ? c->nn : -1);
-    int bits = 1;
-    while (bits < 63 && (1ull << bits) <= (unsigned long long)c->ndof * (unsigned long long)c->ndof) ++bits;
-    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k0, k1, v0, c->csr_perm, (int)nc, 0, bits, c->stream));
-    HIPCHK(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, flags, c->csr_dest, (int)nc, c->stream));
-    tmp_bytes = std::max(tmp_bytes, t2);
-    HIPCHK(c, hipMalloc(&tmp, tmp_bytes));
-    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, k0, k1, v0, c->csr_perm, (int)nc, 0, bits, c->stream));
-    hipLaunchKernelGGL(k_csr_heads, dim3(gb), dim3(256), 0, c->stream, nc, (const long long*)k1, flags);
-    HIPCHK(c, hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, flags, c->csr_dest, (int)nc, c->stream));
+    c->csr = femo_ctx::Csr();
     int nnz = 0;
-    HIPCHK(c, hipMemcpyAsync(&nnz, c->csr_dest + (nc - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMalloc((void**)&c->csr_colidx, (size_t)nnz * sizeof(int)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_rowptr, ((size_t)c->ndof + 1) * sizeof(int)));
-    HIPCHK(c, hipMemsetAsync(c->csr_rowptr, 0, ((size_t)c->ndof + 1) * sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_csr_pattern, dim3(gb), dim3(256), 0, c->stream, nc, (const long long*)k1, (const int*)flags, c->csr_dest, (long long)c->ndof,
-                       c->csr_colidx, c->csr_rowptr);
-    HIPCHK(c, hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, c->csr_rowptr, c->csr_rowptr, c->ndof + 1, c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(k0); hipFree(k1); hipFree(v0); hipFree(flags); hipFree(tmp);
-    HIPCHK(c, hipMalloc((void**)&c->csr_vals, (size_t)nnz * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->csr_ke, (size_t)nc * sizeof(double)));
-    c->csr_ncontrib = nc; c->csr_nnz = nnz;
+    {   // the sort's keys, values, flags and scratch are freed before the value arrays are allocated
+        DevBuf<long long> k0, k1;
+        DevBuf<int> v0, flags;
+        DevBuf<char> tmp;
+        size_t tmp_bytes = 0, t2 = 0;
+        HIPCHK(c, k0.alloc(nc));
+        HIPCHK(c, k1.alloc(nc));
+        HIPCHK(c, v0.alloc(nc));
+        HIPCHK(c, c->csr.perm.alloc(nc));
+        HIPCHK(c, c->csr.dest.alloc(nc));
+        HIPCHK(c, flags.alloc(nc));
+        const unsigned gb = (unsigned)((nc + 255) / 256);
+        hipLaunchKernelGGL(k_csr_keys, dim3(gb), dim3(256), 0, c->stream, nc, c->nel, c->ld, c->npc, c->ndof_u, (long long)c->ndof, (const int*)c->cellp2,
+                           (const int*)c->cells, k0, v0, c->cr ? c->nn : -1);
+        int bits = 1;
+        while (bits < 63 && (1ull << bits) <= (unsigned long long)c->ndof * (unsigned long long)c->ndof) ++bits;
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k0.get(), k1.get(), v0.get(), c->csr.perm.get(), (int)nc, 0, bits, c->stream));
+        HIPCHK(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, flags.get(), c->csr.dest.get(), (int)nc, c->stream));
+        tmp_bytes = std::max(tmp_bytes, t2);
+        HIPCHK(c, tmp.alloc(tmp_bytes));
+        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, k0.get(), k1.get(), v0.get(), c->csr.perm.get(), (int)nc, 0, bits, c->stream));
+        hipLaunchKernelGGL(k_csr_heads, dim3(gb), dim3(256), 0, c->stream, nc, (const long long*)k1, flags);
+        HIPCHK(c, hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, flags.get(), c->csr.dest.get(), (int)nc, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nnz, c->csr.dest + (nc - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->csr.colidx.alloc((size_t)nnz));
+        HIPCHK(c, c->csr.rowptr.alloc((size_t)c->ndof + 1));
+        HIPCHK(c, hipMemsetAsync(c->csr.rowptr, 0, ((size_t)c->ndof + 1) * sizeof(int), c->stream));
+        hipLaunchKernelGGL(k_csr_pattern, dim3(gb), dim3(256), 0, c->stream, nc, (const long long*)k1, (const int*)flags, c->csr.dest, (long long)c->ndof,
+                           c->csr.colidx, c->csr.rowptr);
+        HIPCHK(c, hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, c->csr.rowptr.get(), c->csr.rowptr.get(), c->ndof + 1, c->stream));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    HIPCHK(c, c->csr.vals.alloc((size_t)nnz));
+    HIPCHK(c, c->csr.ke.alloc((size_t)nc));
+    c->csr.ncontrib = nc; c->csr.nnz = nnz;
     if (nnz_out) *nnz_out = nnz;
     return 0;
 }
@@ -4341,22 +4243,22 @@ int femo_build_csr_map(femo_ctx* c, int32_t* nnz_out) {
 // the pattern to the host: rowptr (ndof + 1), colidx (nnz), int32 (sorted columns per row)
 int femo_get_csr_pattern(femo_ctx* c, int32_t* rowptr, int32_t* colidx) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->csr_rowptr) return fail(c, "call femo_build_csr_map first");
-    HIPCHK(c, hipMemcpy(rowptr, c->csr_rowptr, ((size_t)c->ndof + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(colidx, c->csr_colidx, (size_t)c->csr_nnz * sizeof(int), hipMemcpyDeviceToHost));
+    if (!c->csr.rowptr) return fail(c, "call femo_build_csr_map first");
+    HIPCHK(c, hipMemcpy(rowptr, c->csr.rowptr, ((size_t)c->ndof + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(colidx, c->csr.colidx, (size_t)c->csr.nnz * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
 // vals (host, nnz) = CSR values of aK K + (no inertia) for the current fields; ms[0] = element matrices, ms[1] = scatter
 int femo_assemble_csr(femo_ctx* c, double* vals, double* ms2) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->csr_perm) return fail(c, "call femo_set_csr_map first");
+    if (!c->csr.perm) return fail(c, "call femo_set_csr_map first");
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, c->nel, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, 0, c->nel, c->csr_ke);
+    ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, c->nel, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, 0, c->nel, c->csr.ke);
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipMemsetAsync(c->csr_vals, 0, (size_t)c->csr_nnz * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_csr_segmented, dim3((unsigned)((c->csr_ncontrib + 256 * CSR_R - 1) / (256 * CSR_R))), dim3(256), 0, c->stream, c->csr_ncontrib,
-                       c->csr_perm, c->csr_dest, c->csr_ke, c->csr_vals);
+    HIPCHK(c, hipMemsetAsync(c->csr.vals, 0, (size_t)c->csr.nnz * sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_csr_segmented, dim3((unsigned)((c->csr.ncontrib + 256 * CSR_R - 1) / (256 * CSR_R))), dim3(256), 0, c->stream, c->csr.ncontrib,
+                       c->csr.perm, c->csr.dest, c->csr.ke, c->csr.vals);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4364,7 +4266,7 @@ int femo_assemble_csr(femo_ctx* c, double* vals, double* ms2) {
     hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
     hipEventElapsedTime(&b, c->ev[1], c->ev[2]);
     if (ms2) { ms2[0] = a; ms2[1] = b; }
-    if (vals) HIPCHK(c, hipMemcpy(vals, c->csr_vals, (size_t)c->csr_nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (vals) HIPCHK(c, hipMemcpy(vals, c->csr.vals, (size_t)c->csr.nnz * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4388,7 +4290,7 @@ int femo_set_cell_tags(femo_ctx* c, const int32_t* tags, int64_t n, int32_t ntag
     if (ntags < 0) return fail(c, "negative number of sub-domains");
     for (int64_t i = 0; i < n; ++i)
         if (tags[i] < -1 || tags[i] >= ntags) return fail(c, "cell tag out of range");
-    if (!c->ctag) HIPCHK(c, hipMalloc((void**)&c->ctag, (size_t)c->nel * sizeof(int)));
+    if (!c->ctag) HIPCHK(c, c->ctag.alloc((size_t)c->nel));
     HIPCHK(c, hipMemcpy(c->ctag, tags, (size_t)c->nel * sizeof(int), hipMemcpyHostToDevice));
     c->ntags = ntags; c->csel = -1;
     c->alpha_tag.assign(ntags, -1.0);
@@ -4408,13 +4310,11 @@ int femo_field_output(femo_ctx* c, const char* name, double* out, int64_t n) {
     const double zf = fname == "stress" ? 0.5 : fname == "stress_mid" ? 0.0 : fname == "stress_bot" ? -0.5 : 2.0;
     if (zf > 1.0) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
     if (n != (int64_t)c->nvc * c->nel) return fail(c, "the DG1 stress field has nvc * nel entries");
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, (size_t)n * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)n));
     ELEM_LAUNCH(c, k_stress_field, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->w, zf, d);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIPCHK(c, e);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4492,19 +4392,15 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
     if (field_arg_len(c, a, n)) return 1;
     const size_t nc = (size_t)c->nvc * c->nel;
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, ((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)) * sizeof(double)));
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)));
     double* o = d + (size_t)nbar * nc;
-    int rc = 0;
-    if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
-    for (int64_t k = 0; k < nbar && !rc; ++k) rc = field_vjp_dev(c, zf, a, d + k * nc, o + k * n, n);
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    hipFree(d);
-    return rc;
+    if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(c, "copy of the cotangents failed");
+    for (int64_t k = 0; k < nbar; ++k)
+        if (int rc = field_vjp_dev(c, zf, a, d + k * nc, o + k * n, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wrt, int64_t* nnz) {
@@ -4531,10 +4427,10 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     const int64_t nrow = (int64_t)c->nvc * c->nel;
     for (int64_t r = 0; r <= nrow; ++r) rowptr[r] = r * wd;
     if (nnz == 0) return 0;
-    double* dv = nullptr;
-    int* dc = nullptr;
-    HIPCHK(c, hipMalloc((void**)&dv, (size_t)nnz * sizeof(double)));
-    if (hipMalloc((void**)&dc, (size_t)nnz * sizeof(int)) != hipSuccess) { hipFree(dv); return fail(c, "out of device memory"); }
+    DevBuf<double> dv;
+    DevBuf<int> dc;
+    HIPCHK(c, dv.alloc((size_t)nnz));
+    if (dc.alloc((size_t)nnz) != hipSuccess) return fail(c, "out of device memory");
     const MeshDev m = mesh_dev_all(c);
     const FieldsDev f = fields_dev(c);
     if (a == "uhat") {
@@ -4543,13 +4439,10 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
         const int mode = a == "disp_solid" ? 1 : a == "thickness" ? 2 : a == "E" ? 3 : 4;
         ELEM_LAUNCH(c, k_field_jac, NOEXTRA, nblk(nrow, EB), EB, m, f, c->tab, c->w, zf, mode, dv, dc);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(vals, dv, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(colidx, dc, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(dv);
-    hipFree(dc);
-    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(vals, dv, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(colidx, dc, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4565,8 +4458,8 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
     if (field_arg_len(c, a, n)) return 1;
     const size_t nd = (size_t)c->ndof, nc = (size_t)c->nvc * c->nel;
-    double* Bd = mr_io_buffer(c, (size_t)nbar * (2 * nd + (size_t)std::max<int64_t>(n, 1) + nc));
-    if (!Bd) return 1;
+    HIPCHK(c, c->mr_io.grow((size_t)nbar * (2 * nd + (size_t)std::max<int64_t>(n, 1) + nc)));
+    double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * std::max<int64_t>(n, 1);
     std::vector<double*> B(nbar), X(nbar);
     for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }

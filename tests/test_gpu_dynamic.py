@@ -221,3 +221,61 @@ def test_forward_mode_of_the_transient_operator(ewt, self_weight):
     op.apply_inverse_jacobian({}, {}, out, {op.state_name: R.ravel(order="F")}, "fwd")
     ref = ps.tangent_history(R)          # (the sweeps of the factor add with atomics: repeatable to rounding, not bit for bit)
     assert np.abs(out[op.state_name].reshape(W0.shape, order="F") - ref).max() < 1e-9 * np.abs(ref).max()
+
+
+def test_set_up_entry_points_rerun_on_one_context():
+    """The set-up entry points re-run on ONE context free and re-allocate its buffers: a second newmark_setup with another level count,
+    the staging buffer the stress history and the displacement aggregate share, the stress-history scratch grown for more levels, a
+    second CSR map and a second facet list.  Everything computed afterwards must match a fresh context: bit for bit where the kernels
+    add without atomics (the aggregates, the CSR pattern), to the repeatability of the atomic sums elsewhere (solves, CSR values)."""
+    from femo_alpha_amd.backend import ShellContext
+    from femo_alpha_amd.dynamic_rm_shell.plate_sim import PlateSim
+    mesh = plate_mesh(2.0, 10.0, 4, 12)
+    E, nu, rho, dt, N = 1e8, 0.3, 10.0, 0.01, 12
+    t0 = 0.1 * (1 + 0.2 * np.random.default_rng(0).uniform(-1, 1, mesh.nn))
+    F = _gust(N + 1, mesh.nn, dt)
+
+    def sim():
+        ps = PlateSim(mesh, E, nu, rho, dt, N, quad_deg=3, leaf_size=8)
+        ps.update_t(t0); ps.update_f_history(F)
+        ps.ctx.set_stress_alpha(1.0)
+        return ps
+    used, fresh = sim(), sim()
+    used.solve_dynamic_problem()
+    used.ctx.newmark_setup(5, dt)                      # another level count, then the one of the march again
+    used.ctx.newmark_setup(N + 1, dt)
+    W = used.solve_dynamic_problem()
+    W_ref = fresh.solve_dynamic_problem()
+    assert np.abs(W - W_ref).max() <= 1e-10 * np.abs(W_ref).max()
+
+    H = W_ref.T.copy()                                 # one host history for both contexts: the aggregates see the same bits
+    T = N + 1
+    used.ctx.set_option("stress_history_chunk", 2); fresh.ctx.set_option("stress_history_chunk", 2)
+    used.ctx.newmark_stress_history_grad(5, H[:5])     # scratch sized for 5 levels (and the shared staging buffer for 2)
+    used.ctx.newmark_disp_aggregate_grad(T, 50.0, 1.0, H=H)   # the staging buffer grows for the aggregate's own chunk
+    for name, args in [("newmark_stress_history_grad", (T, H)), ("newmark_disp_aggregate_grad", (T, 50.0, 1.0, "all", H)),
+                       ("newmark_stress_history", (T, H)), ("newmark_disp_aggregate", (T, 50.0, 1.0, "all", H))]:
+        a, b = getattr(used.ctx, name)(*args), getattr(fresh.ctx, name)(*args)
+        for x, y in zip(a, b):
+            assert np.array_equal(np.asarray(x), np.asarray(y)), name
+
+    clamp = mesh.penalty_facets(lambda x: np.less(x[0], 3e-16))
+    c1, c2 = ShellContext(mesh), ShellContext(mesh)
+    for c in (c1, c2):
+        for k, v in dict(thickness=t0, E=[E], nu=[nu], density=[rho], F_solid=np.tile([0.0, 0.0, 5.0], (mesh.nn, 1))).items():
+            c.set_field(k, v)
+    c1.set_penalty_facets(mesh.penalty_facets(lambda x: np.less(x[1], 1e-12)))
+    c1.set_penalty_facets(clamp)
+    c2.set_penalty_facets(clamp)
+    c1.enable_csr(); info1 = c1.enable_csr(); info2 = c2.enable_csr()
+    assert info1["nnz"] == info2["nnz"]
+    assert np.array_equal(info1["rowptr"], info2["rowptr"]) and np.array_equal(info1["colidx"], info2["colidx"])
+    K1, K2 = c1.assemble_csr(), c2.assemble_csr()
+    assert abs(K1 - K2).max() <= 1e-13 * abs(K2).max()
+    for c in (c1, c2):
+        c.use_direct_solver()
+        c.solve_state(True)
+    w1, w2 = c1.get_state(), c2.get_state()
+    assert np.abs(w1 - w2).max() <= 1e-10 * np.abs(w2).max()
+    for c in (c1, c2, used.ctx, fresh.ctx):
+        c.close()
