@@ -30,6 +30,7 @@ SIGNATURES = {
     "femo_set_strong_dofs": (C.c_int, [C.c_void_p, C.c_int32, _c_int32_p]),
     "femo_set_field": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, C.c_int64]),
     "femo_get_field": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, C.c_int64]),
+    "femo_set_laminate": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
     "femo_set_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_get_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_apply_K": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),

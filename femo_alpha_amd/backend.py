@@ -124,6 +124,19 @@ class ShellContext:
             varies = (not self.element_wise_material) and v.size > 1 and bool(np.any(v != v[0]))
             self.set_quadrature(self.mesh.recommended_nquad(nodal_nu_varies=varies))
 
+    def set_laminate(self, clt=None, c_drill=None):
+        """Laminated composite law (femo_set_laminate): ``clt`` is the (nel, 32) array of ``laminate.pack`` in solver cell order, or a
+        tuple (A, B, D, A_s) -- the reference's CLT_data -- packed here with ``c_drill`` (None: the reference's 12 max(D)).
+        ``None`` returns to the single-layer law."""
+        if clt is None:
+            self._chk(self.lib.femo_set_laminate(self._h, None, 0))
+            return
+        if isinstance(clt, (tuple, list)):
+            from .laminate import pack
+            clt = pack(*clt, c_drill=c_drill)
+        v = self._vec(clt)
+        self._chk(self.lib.femo_set_laminate(self._h, dptr(v), v.size))
+
     def set_quadrature(self, nquad):
         """The rule of the static forms (femo_set_quadrature): Gauss points per direction on quadrilaterals, the degree of the symmetric
         rule (4, 6, 9, 12) on triangles."""

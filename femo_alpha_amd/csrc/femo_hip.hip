@@ -31,7 +31,7 @@ constexpr int WIDE_NP_DEFAULT = 512;    // option "wide_np" overrides it for the
 constexpr int WIDE_CNT_DEFAULT = 512;   // option "wide_cnt": levels with at most this many fronts also take the wide (many workgroups per
                                         // front) solve kernels -- one workgroup per front cannot pull a level's factor out of HBM
 
-#define FEMO_VERSION 100
+#define FEMO_VERSION 101
 
 static std::string g_create_error;
 
@@ -117,6 +117,10 @@ struct femo_ctx {
     int nquad = 4, nred = 0;
     // fields
     DevBuf<double> h, E, nu, rho, f, uhat;
+    // laminate mode (femo_set_laminate): LAM_W values per cell replace the single-layer law inside the elastic energy
+    DevBuf<double> clt;             // as the caller gave them (femo_get_field, the stale_factor snapshot)
+    DevBuf<double> clt_sym;         // every block replaced by its symmetric part: what the kernels read (FieldsDev.clt)
+    bool laminate = false;
     // dirichlet
     int nf = 0;
     struct Facets {
@@ -244,7 +248,7 @@ struct femo_ctx {
     struct Frontal {
         bool ready = false, factored = false;
         bool have_factor = false;             // a complete factorisation of SOME earlier operator sits in the panel store (option "stale_factor")
-        DevBuf<double> snap[5];               // thickness, E, nu, density, uhat as they were when that factor was made
+        DevBuf<double> snap[6];               // thickness, E, nu, density, uhat, laminate as they were when that factor was made
         bool snap_valid = false;
         bool w_mode = false;                  // the wide levels of the stored factor hold W = L21 X where L21 was (option "sweep_w" at the time of the factorisation)
         double* ahead_vec = nullptr;          // option "sweep_ahead": the vector whose forward sweep the running factorisation starts (null: none)
@@ -535,6 +539,7 @@ static FieldsDev fields_dev(const femo_ctx* c) {
     FieldsDev f;
     f.h = c->h; f.E = c->E; f.nu = c->nu; f.rho = c->rho; f.f = c->f; f.uhat = c->uhat;
     f.ewm = c->ewm; f.ewp = c->ewp;
+    f.clt = c->laminate ? (const double*)c->clt_sym : nullptr;
     return f;
 }
 static FacetDev facet_dev(const femo_ctx* c) {
@@ -593,6 +598,8 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_H , DERIV_H
 #define COMMA_E , DERIV_E
 #define COMMA_NU , DERIV_NU
+#define COMMA_LAM , true
+#define COMMA_FALSE_LAM , false, true
 
 static const int EB = 128;   // element kernels: threads per block (one element per thread)
 
@@ -616,7 +623,8 @@ static int refresh_penalty(femo_ctx* c) {
 static int op_apply(femo_ctx* c, const double* x, double* y, double* dotslot, double* za, double* zb, bool with_penalty,
                     double aK = 1.0, double aM = 0.0) {
     {
-        const int lanes = c->opt.apply_lanes == 5 ? 5 : 4;
+        if (c->laminate && aM != 0.0) return fail(c, "laminate mode: the operator has no inertia term (transient laminates are not supported)");
+        const int lanes = c->opt.apply_lanes == 5 && !c->laminate ? 5 : 4;    // the laminate instantiation exists for the DPP quad only
         const int nb = ((nblk(c->nel, apply_epb(lanes)) + 7) / 8) * 8;      // multiple of 8 for the XCD-aware block order
 #define COMMA_TRUE , true
 #define COMMA_FALSE , false
@@ -624,7 +632,10 @@ static int op_apply(femo_ctx* c, const double* x, double* y, double* dotslot, do
 #define COMMA_FALSE_4 , false, 4
 #define COMMA_TRUE_5 , true, 5
 #define COMMA_FALSE_5 , false, 5
-        if (lanes == 5) {
+#define COMMA_FALSE_4_LAM , false, 4, true
+        if (c->laminate) {
+            ELEM_LAUNCH(c, k_apply4, COMMA_FALSE_4_LAM, nb, 256, mesh_dev(c), fields_dev(c), c->tab, c->eorder, aK, aM, x, c->ybuf, dotslot, za, zb);
+        } else if (lanes == 5) {
             if (aM != 0.0) ELEM_LAUNCH(c, k_apply4, COMMA_TRUE_5, nb, 256, mesh_dev(c), fields_dev(c), c->tab, c->eorder, aK, aM, x, c->ybuf, dotslot, za, zb);
             else ELEM_LAUNCH(c, k_apply4, COMMA_FALSE_5, nb, 256, mesh_dev(c), fields_dev(c), c->tab, c->eorder, aK, aM, x, c->ybuf, dotslot, za, zb);
         } else {
@@ -652,7 +663,8 @@ static int refresh_diag(femo_ctx* c) {
     if (!c->jacobi_dirty) return 0;
     const int64_t n = c->ndof;
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, c->dinv, 0.0, n);
-    ELEM_LAUNCH(c, k_diag, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->dinv);
+    if (c->laminate) ELEM_LAUNCH(c, k_diag, COMMA_LAM, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->dinv);
+    else ELEM_LAUNCH(c, k_diag, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->dinv);
     if (c->nf > 0) {
         if (refresh_penalty(c)) return 1;
         hipLaunchKernelGGL(k_penalty_apply, dim3(nblk(c->nf, 64)), dim3(64), 0, c->stream, facet_dev(c), c->ndof_u, 1,
@@ -862,13 +874,19 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             const int cnt0 = fr.h_level_off[1] - fr.h_level_off[0];
             const int ablk = assemble_block(c->ld);
             const size_t alds = assemble_lds(c->ld, qlds);
-            if (c->op_aM != 0.0)
+            if (c->laminate)         // static only: femo_set_operator refuses an inertia term in laminate mode
+                ELEM_LAUNCH_S(c, k_front_assemble_fc, COMMA_FALSE_LAM, cnt0, ablk, alds, mesh_dev(c), fields_dev(c), atab, c->op_aK, c->op_aM, fd,
+                              (const int*)fr.level_nodes, (const int*)fr.fel_off, (const int*)fr.fel, fr.elem_map, mask, eq);
+            else if (c->op_aM != 0.0)
                 ELEM_LAUNCH_S(c, k_front_assemble_fc, COMMA_TRUE, cnt0, ablk, alds, mesh_dev(c), fields_dev(c), atab, c->op_aK, c->op_aM, fd,
                               (const int*)fr.level_nodes, (const int*)fr.fel_off, (const int*)fr.fel, fr.elem_map, mask, eq);
             else
                 ELEM_LAUNCH_S(c, k_front_assemble_fc, COMMA_FALSE, cnt0, ablk, alds, mesh_dev(c), fields_dev(c), atab, c->op_aK, c->op_aM, fd,
                               (const int*)fr.level_nodes, (const int*)fr.fel_off, (const int*)fr.fel, fr.elem_map, mask, eq);
-        } else if (c->op_aM != 0.0)
+        } else if (c->laminate)
+            ELEM_LAUNCH_S(c, k_front_assemble, COMMA_FALSE_LAM, c->nel, 64, qlds, mesh_dev(c), fields_dev(c), atab, c->op_aK, c->op_aM, fd, fr.elem_front,
+                          fr.elem_map, mask, eq);
+        else if (c->op_aM != 0.0)
             ELEM_LAUNCH_S(c, k_front_assemble, COMMA_TRUE, c->nel, 64, qlds, mesh_dev(c), fields_dev(c), atab, c->op_aK, c->op_aM, fd, fr.elem_front,
                           fr.elem_map, mask, eq);
         else
@@ -1708,9 +1726,9 @@ static int frontal_solve_z(femo_ctx* c) {
 // option "stale_factor": remember the fields the factor just made belongs to
 static int snapshot_fields(femo_ctx* c) {
     if (c->opt.stale_factor <= 0) { c->fr.snap_valid = false; return 0; }
-    double* cur[5] = {c->h, c->E, c->nu, c->rho, c->has_uhat ? c->uhat : nullptr};
-    const int64_t len[5] = {c->nT, c->nT, c->nT, c->nT, 3 * (int64_t)c->nn};
-    for (int i = 0; i < 5; ++i) {
+    double* cur[6] = {c->h, c->E, c->nu, c->rho, c->has_uhat ? c->uhat : nullptr, c->laminate ? c->clt : nullptr};
+    const int64_t len[6] = {c->nT, c->nT, c->nT, c->nT, 3 * (int64_t)c->nn, (int64_t)LAM_W * c->nel};
+    for (int i = 0; i < 6; ++i) {
         if (!cur[i]) { c->fr.snap[i].reset(); continue; }
         if (!c->fr.snap[i]) HIPCHK(c, c->fr.snap[i].alloc((size_t)len[i]));
         HIPCHK(c, hipMemcpyAsync(c->fr.snap[i], cur[i], (size_t)len[i] * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -1730,9 +1748,9 @@ static int pcg_frontal(femo_ctx* c, double* b, double* x, bool zero_guess, int32
     if (stale) {
         // how far the design has moved from the one the factor belongs to: beyond stale_rel the iterations a kept factor needs cost
         // more than a factorisation (profiles/r5_stale_factor.txt), so it is refreshed at once
-        double* cur[5] = {c->h, c->E, c->nu, c->rho, c->has_uhat ? c->uhat : nullptr};
-        const int64_t len[5] = {c->nT, c->nT, c->nT, c->nT, 3 * (int64_t)c->nn};
-        for (int i = 0; i < 5 && stale; ++i) {
+        double* cur[6] = {c->h, c->E, c->nu, c->rho, c->has_uhat ? c->uhat : nullptr, c->laminate ? c->clt : nullptr};
+        const int64_t len[6] = {c->nT, c->nT, c->nT, c->nT, 3 * (int64_t)c->nn, (int64_t)LAM_W * c->nel};
+        for (int i = 0; i < 6 && stale; ++i) {
             if (!cur[i] && !c->fr.snap[i]) continue;                                  // mesh motion absent then and now
             if (!cur[i] || !c->fr.snap[i]) { stale = false; break; }                  // switched on or off since: a different operator
             HIPCHK(c, hipMemsetAsync(c->scal + 5, 0, 2 * sizeof(double), c->stream));
@@ -2192,6 +2210,7 @@ static double* field_ptr(const femo_ctx* c, const char* name, int64_t* n) {
     if (s == "F_solid") { *n = 3 * c->nF; return c->f; }
     if (s == "uhat") { *n = 3 * (int64_t)c->nn; return c->uhat; }
     if (s == "dirichlet" && c->gdir) { *n = c->ndof; return c->gdir; }
+    if (s == "laminate" && c->laminate) { *n = (int64_t)LAM_W * c->nel; return c->clt; }
     *n = -1;
     return nullptr;
 }
@@ -2264,6 +2283,11 @@ int femo_set_strong_dofs(femo_ctx* c, int32_t n, const int32_t* dofs) {
 
 int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
+    if (name && std::string(name) == "laminate") {
+        if (!c->laminate) return fail(c, "field 'laminate' exists in laminate mode only (femo_set_laminate)");
+        if (!v) return fail(c, "null values");
+        return femo_set_laminate(c, v, n);
+    }
     if (name && std::string(name) == "dirichlet" && !c->gdir) {
         HIPCHK(c, c->gdir.alloc((size_t)c->ndof));
         HIPCHK(c, hipMemset(c->gdir, 0, (size_t)c->ndof * sizeof(double)));
@@ -2308,6 +2332,103 @@ int femo_get_field(femo_ctx* c, const char* name, double* v, int64_t n) {
     if (!d) return fail(c, "unknown field");
     if (n != len) return fail(c, "length mismatch");
     HIPCHK(c, hipMemcpy(v, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// laminate mode is a static feature: the transient march (the reference's PlateSim is isotropic) and the element-partitioned driver refuse it
+static int laminate_refused(femo_ctx* c, const char* who) {
+    return fail(c, std::string(who) + ": not available in laminate mode (femo_set_laminate); return to the isotropic law with femo_set_laminate(ctx, NULL, 0)");
+}
+
+// Cholesky of the symmetric part of an n x n row-major block (stride ld): false if a pivot is not positive
+static bool sym_block_pd(const double* a, int n, int ld) {
+    double L[6][6];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double v = 0.5 * (a[i * ld + j] + a[j * ld + i]);
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            if (i == j) {
+                if (!(v > 0.0)) return false;
+                L[i][i] = sqrt(v);
+            } else {
+                L[i][j] = v / L[j][j];
+            }
+        }
+    return true;
+}
+
+int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!clt && n == 0) {                                  // back to the single-layer law
+        if (c->laminate) {
+            c->laminate = false;
+            c->clt.reset();
+            c->clt_sym.reset();
+            operator_changed(c);
+            ++c->opt_version;
+        }
+        return 0;
+    }
+    const int64_t len = (int64_t)LAM_W * c->nel;
+    if (!clt || n != len) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "laminate: expected %d values per cell [A (3x3), B (3x3), D (3x3), A_s (2x2), c_drill] = %lld, got %lld%s",
+                 LAM_W, (long long)len, (long long)n, clt ? "" : " (null values)");
+        return fail(c, buf);
+    }
+    if (c->op_aM != 0.0) return fail(c, "laminate: the operator has an inertia term (femo_set_operator); transient laminates are not supported");
+    for (int e = 0; e < c->nel; ++e) {
+        const double* L = clt + (size_t)LAM_W * e;
+        char buf[200];
+        for (int k = 0; k < LAM_W; ++k)
+            if (!std::isfinite(L[k])) {
+                snprintf(buf, sizeof buf, "laminate: value %d of cell %d is not finite", k, e);
+                return fail(c, buf);
+            }
+        double ABD[36];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                ABD[i * 6 + j] = L[3 * i + j];
+                ABD[i * 6 + 3 + j] = L[9 + 3 * i + j];
+                ABD[(3 + i) * 6 + j] = L[9 + 3 * i + j];         // B below the diagonal too: the symmetric part is [[sym A, sym B], [sym B, sym D]]
+                ABD[(3 + i) * 6 + 3 + j] = L[18 + 3 * i + j];
+            }
+        if (!sym_block_pd(ABD, 6, 6)) {
+            snprintf(buf, sizeof buf, "laminate: the block [[A, B], [B, D]] of cell %d is not positive definite", e);
+            return fail(c, buf);
+        }
+        if (!sym_block_pd(L + 27, 2, 2)) {
+            snprintf(buf, sizeof buf, "laminate: the shear block A_s of cell %d is not positive definite", e);
+            return fail(c, buf);
+        }
+        if (!(L[31] > 0.0)) {
+            snprintf(buf, sizeof buf, "laminate: the drilling coefficient c_drill of cell %d is not positive", e);
+            return fail(c, buf);
+        }
+    }
+    const bool entering = !c->laminate;
+    std::vector<double> sym(clt, clt + len);
+    for (int e = 0; e < c->nel; ++e) {
+        double* L = sym.data() + (size_t)LAM_W * e;
+        for (int blk = 0; blk < 3; ++blk)
+            for (int i = 0; i < 3; ++i)
+                for (int j = i + 1; j < 3; ++j) {
+                    double& a = L[9 * blk + 3 * i + j];
+                    double& b = L[9 * blk + 3 * j + i];
+                    a = b = 0.5 * (a + b);
+                }
+        L[28] = L[29] = 0.5 * (L[28] + L[29]);
+    }
+    if (!c->clt) HIPCHK(c, c->clt.alloc((size_t)len));
+    if (!c->clt_sym) HIPCHK(c, c->clt_sym.alloc((size_t)len));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(c->clt, clt, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->clt_sym, sym.data(), (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    c->laminate = true;
+    // a new law is a different operator; new values of the same law may keep the factor as a preconditioner (option "stale_factor",
+    // which measures the laminate against its snapshot like the other fields)
+    operator_changed(c, !entering);
+    ++c->opt_version;
     return 0;
 }
 
@@ -2451,7 +2572,8 @@ int femo_element_matrices(femo_ctx* c, int32_t first, int32_t count, double* Ke)
     DevBuf<double> d;
     const size_t len = (size_t)count * c->ld * c->ld;
     HIPCHK(c, d.alloc(len));
-    ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, count, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, first, count, d);
+    if (c->laminate) ELEM_LAUNCH_S(c, k_element_matrices, COMMA_LAM, count, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, first, count, d);
+    else ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, count, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, first, count, d);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(Ke, d, len * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
@@ -2638,8 +2760,12 @@ static int shape_gradient_dev(femo_ctx* c, int mode, const double* w, const doub
     const int nthreads = c->nel * 3 * c->nvc;
     const Tables* tb = mode == 4 ? c->tab_s : c->tab;
 #define SHAPE_LAUNCH(NPC, NVC, QUAD)                                                                                              \
-    hipLaunchKernelGGL((k_shape_gradient<NPC, NVC, QUAD>), dim3(nblk(nthreads, 128)), dim3(128), 0, c->stream, m, f, tb, mode, w, lam, \
-                       scale, c->stress_m, c->stress_rho, c->stress_reg, out)
+    if (c->laminate && (mode == 0 || mode == 3))                                                                                      \
+        hipLaunchKernelGGL((k_shape_gradient<NPC, NVC, QUAD, true>), dim3(nblk(nthreads, 128)), dim3(128), 0, c->stream, m, f, tb, mode, w, \
+                           lam, scale, c->stress_m, c->stress_rho, c->stress_reg, out);                                                 \
+    else                                                                                                                              \
+        hipLaunchKernelGGL((k_shape_gradient<NPC, NVC, QUAD>), dim3(nblk(nthreads, 128)), dim3(128), 0, c->stream, m, f, tb, mode, w, lam, \
+                           scale, c->stress_m, c->stress_rho, c->stress_reg, out)
     if (c->cg1) { if (c->quad) SHAPE_LAUNCH(4, 4, true); else SHAPE_LAUNCH(3, 3, false); }
     else        { if (c->quad) SHAPE_LAUNCH(9, 4, true); else SHAPE_LAUNCH(6, 3, false); }
 #undef SHAPE_LAUNCH
@@ -2696,6 +2822,8 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
         if (wrt == "thickness") ELEM_LAUNCH(c, k_field_grad, NOEXTRA, g, EB, m, f, c->tab, 3, out);
     } else if (fn == "elastic_energy") {
         if (wrt == "disp_solid") { if (op_apply(c, c->w, out, nullptr, nullptr, nullptr, false)) return 1; }
+        else if (wrt == "laminate") ELEM_LAUNCH(c, k_dRdlam_T, NOEXTRA, g, EB, m, f, c->tab, c->w, c->w, 0.5, out);
+        else if (c->laminate) { /* the laminate replaces thickness, E and nu inside the elastic energy */ }
         else if (wrt == "thickness") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_H, g, EB, m, f, c->tab, c->w, c->w, 0.5, out);
         else if (wrt == "E") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_E, g, EB, m, f, c->tab, c->w, c->w, 0.5, out);
         else if (wrt == "nu") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_NU, g, EB, m, f, c->tab, c->w, c->w, 0.5, out);
@@ -2719,7 +2847,9 @@ static int dRdarg_T_dev(femo_ctx* c, const std::string& arg, const double* lam, 
     const MeshDev m = mesh_dev(c);
     const FieldsDev f = fields_dev(c);
     const int g = nblk(c->nel, EB);
-    if (arg == "thickness") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_H, g, EB, m, f, c->tab, c->w, lam, scale, out);
+    if (arg == "laminate") ELEM_LAUNCH(c, k_dRdlam_T, NOEXTRA, g, EB, m, f, c->tab, c->w, lam, scale, out);
+    else if (c->laminate && (arg == "thickness" || arg == "E" || arg == "nu")) { /* R does not depend on them in laminate mode */ }
+    else if (arg == "thickness") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_H, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "E") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_E, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "nu") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_NU, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "F_solid") ELEM_LAUNCH(c, k_dRdf_T, NOEXTRA, g, EB, m, f, c->tab, lam, -scale, out);
@@ -3329,6 +3459,7 @@ int femo_field_gradient_vec(femo_ctx* c, const char* functional, const char* arg
 // replicated entries: this rank's share of r.r (first collective) or of p.Ap (second).
 int femo_dist_setup(femo_ctx* c, int32_t ntop, const int32_t* top_idx, int32_t nranks, int32_t n_local_levels, int32_t nsel,
                     const int32_t* sel) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_setup");
     HIPCHK(c, hipSetDevice(c->device));
     auto& d = c->di;
     if (d.ready) return fail(c, "femo_dist_setup was already called for this context");
@@ -3358,6 +3489,7 @@ void* femo_dist_ptr(femo_ctx* c, int32_t which) { return which == 0 ? (void*)c->
 #define DIST_READY(c) do { HIPCHK(c, hipSetDevice((c)->device)); if (!(c)->di.ready) return fail(c, "call femo_dist_setup first"); } while (0)
 
 int femo_dist_pack(femo_ctx* c, int32_t vec) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_pack");
     DIST_READY(c);
     double* v = vec_by_id(c, vec);
     if (!v) return fail(c, "bad vector id");
@@ -3367,6 +3499,7 @@ int femo_dist_pack(femo_ctx* c, int32_t vec) {
 }
 
 int femo_dist_unpack(femo_ctx* c, int32_t vec) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_unpack");
     DIST_READY(c);
     double* v = vec_by_id(c, vec);
     if (!v) return fail(c, "bad vector id");
@@ -3377,6 +3510,7 @@ int femo_dist_unpack(femo_ctx* c, int32_t vec) {
 
 // x = 0, r = b; this rank's share of b.b goes into scal[3] (it travels with the first collective of the first iteration)
 int femo_dist_pcg_start(femo_ctx* c, int32_t b, int32_t x) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_pcg_start");
     DIST_READY(c);
     double *vb = vec_by_id(c, b), *vx = vec_by_id(c, x);
     if (!vb || !vx || vb == vx || vb == c->r || vb == c->z || vb == c->p || vb == c->Ap || vx == c->r || vx == c->z || vx == c->p || vx == c->Ap)
@@ -3392,6 +3526,7 @@ int femo_dist_pcg_start(femo_ctx* c, int32_t b, int32_t x) {
 
 // z = r; forward sweep over this rank's subtree; topbuf = what it added to the replicated entries, topbuf[ntop] = share of r.r
 int femo_dist_precond_fwd(femo_ctx* c) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_precond_fwd");
     DIST_READY(c);
     auto& d = c->di;
     if (!c->fr.factored) return fail(c, "the factorisation is stale");
@@ -3407,6 +3542,7 @@ int femo_dist_precond_fwd(femo_ctx* c) {
 
 // after the collective: out2 = { global r.r, global p.Ap of the previous iteration }  (the one host synchronisation per iteration)
 int femo_dist_read(femo_ctx* c, double* out2) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_read");
     DIST_READY(c);
     HIPCHK(c, hipMemcpyAsync(c->scal_host, c->di.topbuf + c->di.ntop, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->scal_host + 1, c->scal + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3418,6 +3554,7 @@ int femo_dist_read(femo_ctx* c, double* out2) {
 // replicated entries of z <- saved + summed delta; the replicated top of the tree forward and backward; this rank's subtree
 // backward; scal[1] = share of r.z
 int femo_dist_precond_rest(femo_ctx* c) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_precond_rest");
     DIST_READY(c);
     auto& d = c->di;
     const int64_t n = c->ndof;
@@ -3434,6 +3571,7 @@ int femo_dist_precond_rest(femo_ctx* c) {
 // p = z + (r.z / previous r.z) p; Ap = (local operator) p; topbuf = Ap on the replicated entries, topbuf[ntop] = p . Ap_local
 // (p^T A p is the sum over the ranks of p^T A_local p: the scalar needs no collective of its own)
 int femo_dist_direction_apply(femo_ctx* c, int first) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_direction_apply");
     DIST_READY(c);
     auto& d = c->di;
     const int64_t n = c->ndof;
@@ -3451,6 +3589,7 @@ int femo_dist_direction_apply(femo_ctx* c, int first) {
 
 // after the collective: Ap's replicated entries and the global p.Ap are in topbuf; x += alpha p, r -= alpha Ap, scal[3] = share of r.r
 int femo_dist_update(femo_ctx* c, int32_t x) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_update");
     DIST_READY(c);
     auto& d = c->di;
     double* vx = vec_by_id(c, x);
@@ -3465,6 +3604,7 @@ int femo_dist_update(femo_ctx* c, int32_t x) {
 
 // gglob (device, nglob doubles, zeroed by the caller) [sel] = - (dR/d arg)^T lambda + d functional / d arg over this rank's cells
 int femo_dist_gradient(femo_ctx* c, const char* functional, const char* arg, int32_t lam, void* gglob, int64_t nglob) {
+    if (c->laminate) return laminate_refused(c, "femo_dist_gradient");
     DIST_READY(c);
     auto& d = c->di;
     double* l = vec_by_id(c, lam);
@@ -3518,6 +3658,7 @@ int femo_factorize_profile_get(femo_ctx* c, double* out32) {
 
 // ---- dynamic shell: operator A = aK K + aM M, device-vector building blocks (femo_alpha_amd/dynamic_rm_shell) ----
 int femo_set_operator(femo_ctx* c, double aK, double aM) {
+    if (c->laminate && aM != 0.0) return fail(c, "laminate mode: the transient operator (inertia term) is not supported");
     if (aK != c->op_aK || aM != c->op_aM) { c->op_aK = aK; c->op_aM = aM; operator_changed(c); }
     return 0;
 }
@@ -3648,6 +3789,7 @@ int femo_grad_get(femo_ctx* c, double* out, int64_t n) {
 //   w_mid = (w_old + w)/2,  wdot = 2/dt (w - w_old) - wdot_old,  wddot = (wdot - wdot_old)/dt      (plate_sim.py:131-140)
 //   step:  (a M + K/2) w_i = F_i + M (a w_{i-1} + b wdot_{i-1}) - K/2 w_{i-1},   a = 2/dt^2, b = 2/dt
 int femo_newmark_setup(femo_ctx* c, int32_t time_levels, double dt) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_setup");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (time_levels < 2 || !(dt > 0)) return fail(c, "femo_newmark_setup: need at least two time levels and dt > 0");
@@ -3666,6 +3808,7 @@ int femo_newmark_setup(femo_ctx* c, int32_t time_levels, double dt) {
 
 // pressure history, (levels_given x field length of F_solid) row-major; levels beyond the last one repeat it
 int femo_newmark_set_forces(femo_ctx* c, const double* f_history, int32_t levels_given) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_set_forces");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3679,6 +3822,7 @@ int femo_newmark_set_forces(femo_ctx* c, const double* f_history, int32_t levels
 
 // a load vector added to every step's right-hand side (the self weight of element-wise thickness as consistent nodal loads); null: none
 int femo_newmark_set_constant_load(femo_ctx* c, const double* F) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_set_constant_load");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3694,6 +3838,7 @@ void* femo_newmark_ptr(femo_ctx* c, int32_t which) { return which == 0 ? (void*)
 // March levels 1 .. nsteps from zero initial conditions.  reassemble != 0: the step operator is re-assembled and re-factorised
 // before every solve, as the reference does (nonlinear_utils.py:210-233).  iters / relres: nsteps entries (may be null).
 int femo_newmark_march(femo_ctx* c, int32_t nsteps, int reassemble, int32_t* iters, double* relres) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_march");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready || !nm.Fh) return fail(c, "femo_newmark_march: set-up or force history missing");
@@ -3729,6 +3874,7 @@ int femo_newmark_march(femo_ctx* c, int32_t nsteps, int reassemble, int32_t* ite
 
 // history to the host, (time_levels x ndof) row-major (level-major); which: 0 displacement history, 2 adjoint history
 int femo_newmark_get_history(femo_ctx* c, int32_t which, double* out) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_get_history");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     const double* src = which == 0 ? nm.W : which == 2 ? nm.Lam : nullptr;
@@ -3738,6 +3884,7 @@ int femo_newmark_get_history(femo_ctx* c, int32_t which, double* out) {
 }
 
 int femo_newmark_set_history(femo_ctx* c, int32_t which, const double* H) {      // a history from outside (the caller's adjoint seed, restarts): level-major
+    if (c->laminate) return laminate_refused(c, "femo_newmark_set_history");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3783,6 +3930,7 @@ static int newmark_adjoint_sweep(femo_ctx* c, int32_t levels) {
 }
 
 int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_adjoint");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3796,6 +3944,7 @@ int femo_newmark_adjoint(femo_ctx* c, const double* G, int32_t levels) {
 
 // the same sweep from the seed a device producer left in nm.Gh (femo_newmark_stress_history_grad(.., seed_adjoint = 1)): no host copy
 int femo_newmark_adjoint_seeded(femo_ctx* c, int32_t levels) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_adjoint_seeded");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3808,6 +3957,7 @@ int femo_newmark_adjoint_seeded(femo_ctx* c, int32_t levels) {
 // dF (levels x field length of F_solid, level-major; level 0 zero) = (dR_i/df)^T lam_i, for the resident displacement and
 // adjoint histories (state_operation_dynamic.py:406-427: the thickness gradient re-assembled per level)
 int femo_newmark_residual_T(femo_ctx* c, int32_t levels, double* g_t, double* dF) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_residual_T");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready || !nm.Lam) return fail(c, "femo_newmark_residual_T: no adjoint history (femo_newmark_adjoint)");
@@ -3850,6 +4000,7 @@ int femo_newmark_residual_T(femo_ctx* c, int32_t levels, double* g_t, double* dF
 // out_i = [J dY]_i + (dR_i/dt) dthickness + (dR_i/df) dF_i.  Any of dY (levels x ndof), dthickness, dF (levels x F length) may be
 // null.  The result lands in the adjoint-history buffer (femo_newmark_get_history(ctx, 2, ..)).
 int femo_newmark_jvp(femo_ctx* c, int32_t levels, const double* dY, const double* dthickness, const double* dF) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_jvp");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -3922,6 +4073,7 @@ int femo_newmark_jvp(femo_ctx* c, int32_t levels, const double* dY, const double
 // rows, dw_i = dr_i on the Dirichlet rows (their coupling into the free rows moved to the right-hand side).  The result lands in the
 // adjoint-history buffer.
 int femo_newmark_tangent(femo_ctx* c, const double* dR, int32_t levels) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_tangent");
     HIPCHK(c, hipSetDevice(c->device));
     auto& nm = c->nm;
     if (!nm.ready) return fail(c, "call femo_newmark_setup first");
@@ -4068,10 +4220,12 @@ static int stress_history_run(femo_ctx* c, int32_t levels, const double* H, bool
 }
 
 int femo_newmark_stress_history(femo_ctx* c, int32_t levels, const double* H, double* per_level, double* total) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_stress_history");
     return stress_history_run(c, levels, H, false, per_level, total, nullptr, nullptr, false);
 }
 
 int femo_newmark_stress_history_grad(femo_ctx* c, int32_t levels, const double* H, double* g_thickness, double* G, int seed_adjoint) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_stress_history_grad");
     return stress_history_run(c, levels, H, true, nullptr, nullptr, g_thickness, G, seed_adjoint != 0);
 }
 
@@ -4163,11 +4317,13 @@ static int disp_history_run(femo_ctx* c, int32_t levels, const double* H, int32_
 
 int femo_newmark_disp_aggregate(femo_ctx* c, int32_t levels, const double* H, int32_t components, double rho, double scaler,
                                 double* per_level, double* total) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_disp_aggregate");
     return disp_history_run(c, levels, H, components, rho, scaler, false, per_level, total, nullptr, false);
 }
 
 int femo_newmark_disp_aggregate_grad(femo_ctx* c, int32_t levels, const double* H, int32_t components, double rho, double scaler,
                                      double* total, double* G, int seed_adjoint) {
+    if (c->laminate) return laminate_refused(c, "femo_newmark_disp_aggregate_grad");
     return disp_history_run(c, levels, H, components, rho, scaler, true, nullptr, total, G, seed_adjoint != 0);
 }
 
@@ -4254,7 +4410,8 @@ int femo_assemble_csr(femo_ctx* c, double* vals, double* ms2) {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->csr.perm) return fail(c, "call femo_set_csr_map first");
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, c->nel, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, 0, c->nel, c->csr.ke);
+    if (c->laminate) ELEM_LAUNCH_S(c, k_element_matrices, COMMA_LAM, c->nel, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, 0, c->nel, c->csr.ke);
+    else ELEM_LAUNCH_S(c, k_element_matrices, NOEXTRA, c->nel, 64, QPOINT_LDS(c), mesh_dev(c), fields_dev(c), c->tab, 0, c->nel, c->csr.ke);
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipMemsetAsync(c->csr.vals, 0, (size_t)c->csr.nnz * sizeof(double), c->stream));
     hipLaunchKernelGGL(k_csr_segmented, dim3((unsigned)((c->csr.ncontrib + 256 * CSR_R - 1) / (256 * CSR_R))), dim3(256), 0, c->stream, c->csr.ncontrib,
@@ -4501,7 +4658,11 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
         if (s == "apply") return op_apply(c, c->p, c->Ap, c->scal + 7, nullptr, nullptr, false);
         if (s == "pcg_update") { hipLaunchKernelGGL(k_pcg_update, dim3(vg), dim3(256), 0, c->stream, c->tmp, c->r, c->z, c->p, c->Ap, c->dinv, (const unsigned char*)nullptr, n, c->scal, 0); return 0; }
         if (s == "pcg_direction") { hipLaunchKernelGGL(k_pcg_direction, dim3(vg), dim3(256), 0, c->stream, c->p, c->z, c->Ap, n, c->scal, 0); return 0; }
-        if (s == "diag") { ELEM_LAUNCH(c, k_diag, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->tmp); return 0; }
+        if (s == "diag") {
+            if (c->laminate) ELEM_LAUNCH(c, k_diag, COMMA_LAM, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->tmp);
+            else ELEM_LAUNCH(c, k_diag, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->tmp);
+            return 0;
+        }
         // one application of the factor to 1 / 2 / 4 vectors (the sweeps alone: no interleaving copies); needs a factorisation
         if (s == "sweeps1" || s == "sweeps2" || s == "sweeps4") {
             if (!c->fr.factored) return fail(c, "no factorisation to sweep with");

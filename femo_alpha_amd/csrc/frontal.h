@@ -79,7 +79,7 @@ __device__ __host__ inline int ldx_of(int np) { return (np + SPD - 1) / SPD * SP
 // ------------------------------------------------------------------------------------------ assembly
 // one wave per element; lane j evaluates column j of K_e (operator applied to e_j) and adds its
 // lower-triangle entries into the element's leaf front.  Masked (strong-BC) rows/columns are skipped.
-template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS, bool LAM = false>
 __global__ void __launch_bounds__(64)          // 239 registers, two waves per SIMD; capped at 167 (three waves, 52 B of scratch): 1.33 against 1.07 ms
 k_front_assemble(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double aK, double aM, FrontDev fd,
                  const int* __restrict__ elem_front, const int* __restrict__ elem_map, const unsigned char* __restrict__ mask,
@@ -93,8 +93,9 @@ k_front_assemble(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double 
     // the quadrature-point data all lanes share: computed once, by lane q for point q, and parked in LDS (stage_qpoints)
     extern __shared__ double sq_raw[];
     QPoint<NPC, NVC>* sq = reinterpret_cast<QPoint<NPC, NVC>*>(sq_raw);
-    stage_qpoints<NPC, NVC, QUAD, UHAT>(tab, el, aK, j, 64, sq);
+    stage_qpoints<NPC, NVC, QUAD, UHAT, LAM>(tab, el, aK, j, 64, sq);
     if (j >= LD) return;
+    const double* L = LAM ? f.clt + (size_t)LAM_W * e : nullptr;     // laminate mode: the cell's values, uniform over the wave
     double ye[LD];
 #pragma unroll
     for (int i = 0; i < LD; ++i) ye[i] = 0.0;
@@ -121,7 +122,7 @@ k_front_assemble(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double 
             T1[c] = is_u ? 0.0 : dk1 * ec;
         }
         const Gen s = strains_reduced(p.g, G0, G1, th, T0, T1);
-        const Gen t = stress_of(s, p.mat);
+        const Gen t = law<LAM>(s, p.mat, L);
         strains_T<NPC, NVC>(p.g, p.d, p.mm, tab->NR[q], t, ye);
     }
     if (MASS) {
@@ -181,7 +182,7 @@ __device__ __host__ constexpr size_t assemble_lds(int ld, size_t qpoint_bytes) {
     const size_t part = (size_t)(assemble_block(ld) / ld) * ld * (ld | 1) * sizeof(double);
     return part > qpoint_bytes ? part : qpoint_bytes;
 }
-template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS, bool LAM = false>
 __global__ void __launch_bounds__(assemble_block(3 * NPC + 3 * NVC))
 k_front_assemble_fc(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double aK, double aM, FrontDev fd,
                     const int* __restrict__ level_nodes, const int* __restrict__ fel_off, const int* __restrict__ fel,
@@ -221,7 +222,8 @@ k_front_assemble_fc(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, doub
         Elem<NPC, NVC> el;
         load_elem<NPC, NVC, UHAT>(m, f, e, el);
         __syncthreads();                                      // the previous element's partial columns have been read (and the zero fill is done)
-        stage_qpoints<NPC, NVC, QUAD, UHAT>(tab, el, aK, tid, BLK, sq);
+        stage_qpoints<NPC, NVC, QUAD, UHAT, LAM>(tab, el, aK, tid, BLK, sq);
+        const double* L = LAM ? f.clt + (size_t)LAM_W * e : nullptr;
         double ye[LD];
 #pragma unroll
         for (int i = 0; i < LD; ++i) ye[i] = 0.0;
@@ -242,7 +244,10 @@ k_front_assemble_fc(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, doub
                 T1[c] = is_u ? 0.0 : dk1 * ec;
             }
             const Gen s = strains_reduced(p.g, G0, G1, th, T0, T1);
-            const Gen tt = stress_of(s, p.mat);
+            // the laminate is re-read per point (scalar loads): hoisted out of the loop its 21 values cost the kernel its second wave per SIMD
+            const double* Lq = L;
+            if constexpr (LAM) asm volatile("" : "+s"(Lq));
+            const Gen tt = law<LAM>(s, p.mat, Lq);
             strains_T<NPC, NVC>(p.g, p.d, p.mm, tab->NR[q], tt, ye);
         }
         if (MASS) {

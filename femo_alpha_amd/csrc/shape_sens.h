@@ -168,12 +168,26 @@ __device__ __forceinline__ D1 energy_density_dual(const GenD& a, const GenD& b, 
     return mem + ben + cs * (a.ga0 * b.ga0 + a.ga1 * b.ga1) + cd * (a.om * b.om);
 }
 
+// the same with the laminate law (shell_device.h, stress_lam): A, B, D without J(uhat), A_s and drilling with it
+__device__ __forceinline__ D1 energy_density_dual_lam(const GenD& a, const GenD& b, const double* L, double hK, double wdetS, double wdet,
+                                                      D1 Ju) {
+    auto S = [&](int blk, int i, int j) { return L[9 * blk + 3 * i + j]; };      // L symmetrised (FieldsDev.clt)
+    const D1 ea[3] = {a.e00, a.e11, a.g01}, ka[3] = {a.k00, a.k11, a.k01}, eb[3] = {b.e00, b.e11, b.g01}, kb[3] = {b.k00, b.k11, b.k01};
+    D1 mb = mk(0.0);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            mb = mb + S(0, i, j) * (ea[i] * eb[j]) + S(1, i, j) * (ea[i] * kb[j] + ka[i] * eb[j]) + S(2, i, j) * (ka[i] * kb[j]);
+    const double as01 = L[28];
+    const D1 sh = L[27] * (a.ga0 * b.ga0) + as01 * (a.ga0 * b.ga1 + a.ga1 * b.ga0) + L[30] * (a.ga1 * b.ga1);
+    return wdetS * mb + (wdetS * sh) * Ju + (L[31] / (hK * hK) * wdet * (a.om * b.om)) * Ju;
+}
+
 // mode 0: lam . (K w - F)   (the residual's elastic + load part; penalty handled per facet)
 // mode 1: int u.u J dx      (compliance without the regularisation, which has no uhat dependence)
 // mode 2: int rho h J dx    (mass)
 // mode 3: 1/2 w . K w       (elastic energy)
 // mode 4: int (m vm_top)^rho J dx   (p-norm stress before the 1/alpha scaling)
-template <int NPC, int NVC, bool QUAD>
+template <int NPC, int NVC, bool QUAD, bool LAM = false>
 __global__ void __launch_bounds__(128)
 k_shape_gradient(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int mode, const double* __restrict__ w,
                  const double* __restrict__ lam, double scale, double ms, double rho, double regc, double* __restrict__ out) {
@@ -218,9 +232,13 @@ k_shape_gradient(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int mod
             const double Eq = interp<NVC>(tab->N1[q], el.En), nuq = interp<NVC>(tab->N1[q], el.nun);
             const GenD sw = strains_dual<NPC, NVC>(*tab, q, g, s, we);
             if (mode == 3) {
+                if constexpr (LAM) phi = phi + 0.5 * energy_density_dual_lam(sw, sw, f.clt + (size_t)LAM_W * e, el.hK, wdetS, wdet, s.Ju);
+                else
                 phi = phi + 0.5 * energy_density_dual(sw, sw, hq, Eq, nuq, el.hK, wdetS, wdet, s.Ju);
             } else {
                 const GenD sl = strains_dual<NPC, NVC>(*tab, q, g, s, le);
+                if constexpr (LAM) phi = phi + energy_density_dual_lam(sw, sl, f.clt + (size_t)LAM_W * e, el.hK, wdetS, wdet, s.Ju);
+                else
                 phi = phi + energy_density_dual(sw, sl, hq, Eq, nuq, el.hK, wdetS, wdet, s.Ju);
                 double fq[3] = {0, 0, 0}, lq[3] = {0, 0, 0};
                 for (int b = 0; b < NVC; ++b)

@@ -61,6 +61,7 @@ struct FieldsDev {
     const double* f;
     const double* uhat;
     int ewm, ewp;
+    const double* clt;    // laminate mode: LAM_W doubles per cell (femo_set_laminate); null on the isotropic path
 };
 
 // ------------------------------------------------------------------------------------------ helpers
@@ -326,6 +327,49 @@ struct Mat {
 
 enum { DERIV_NONE = 0, DERIV_H = 1, DERIV_E = 2, DERIV_NU = 3 };
 
+// ---- laminate law (MaterialModelComposite / ElasticModelShapeOpt, linear_shell_model.py:159-190, 268-296).  Per cell LAM_W values
+// [A (3x3 row-major), B (3x3), D (3x3), A_s (2x2), c_drill] act on the Voigt strains eps = (e00, e11, g01), kappa = (k00, k11, k01),
+// gamma = (ga0, ga1) of the point's local frame; the operator is the Hessian of 1/2 (eps.A eps + eps.B kappa + kappa.B eps + kappa.D kappa)
+// + 1/2 gamma.A_s gamma + the drilling term, so only the symmetric parts act.  The measures stay those of the single-layer law: Mat.cm
+// carries w_S det (membrane, bending, coupling), Mat.cs w_S det J (shear), Mat.cd w det J / h_K^2 (drilling, times c_drill); cb and nu
+// are unused.  Kernels take the law as a template flag (LAM): the isotropic instantiations never see it.
+constexpr int LAM_W = 32;
+
+__device__ __forceinline__ void lam_measures(double hK, double wdetS, double wdet, double Ju, Mat& m) {
+    m.cm = wdetS;
+    m.cb = 0.0;
+    m.cs = wdetS * Ju;
+    m.cd = wdet * Ju / (hK * hK);
+    m.nu = 0.0;
+}
+
+// the conjugate stresses of the laminate law.  L: the cell's values with every block replaced by its symmetric part -- the device copy
+// FieldsDev.clt holds them so (femo_set_laminate symmetrises on upload; the caller's values are kept as given for femo_get_field)
+__device__ __forceinline__ Gen stress_lam(const Gen& s, const Mat& m, const double* L) {
+    auto A = [&](int blk, int i, int j) { return L[9 * blk + 3 * i + j]; };
+    const double ep[3] = {s.e00, s.e11, s.g01}, kp[3] = {s.k00, s.k11, s.k01};
+    double n[3], mo[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        n[i] = 0.0; mo[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double b = A(1, i, j);
+            n[i] += A(0, i, j) * ep[j] + b * kp[j];
+            mo[i] += b * ep[j] + A(2, i, j) * kp[j];
+        }
+    }
+    const double as01 = L[28];
+    Gen t;
+    t.e00 = m.cm * n[0]; t.e11 = m.cm * n[1]; t.g01 = m.cm * n[2];
+    t.k00 = m.cm * mo[0]; t.k11 = m.cm * mo[1]; t.k01 = m.cm * mo[2];
+    t.ga0 = m.cs * (L[27] * s.ga0 + as01 * s.ga1);
+    t.ga1 = m.cs * (as01 * s.ga0 + L[30] * s.ga1);
+    t.om = m.cd * L[31] * s.om;
+    return t;
+}
+
+
 // constitutive coefficients at a point; which = derivative selector
 template <int WHICH>
 __device__ __forceinline__ void material(double h, double E, double nu, double hK, double wdetS, double wdet, double Ju, Mat& m,
@@ -389,6 +433,13 @@ __device__ __forceinline__ void stress_add_dnu(const Gen& s, const Mat& x, Gen& 
 __device__ __forceinline__ double gen_dot(const Gen& a, const Gen& b) {
     return a.e00 * b.e00 + a.e11 * b.e11 + a.g01 * b.g01 + a.k00 * b.k00 + a.k11 * b.k11 + a.k01 * b.k01 +
            a.ga0 * b.ga0 + a.ga1 * b.ga1 + a.om * b.om;
+}
+
+// the law of a kernel instantiation: the single-layer law, or the laminate L of the cell
+template <bool LAM>
+__device__ __forceinline__ Gen law(const Gen& s, const Mat& m, const double* L) {
+    if constexpr (LAM) return stress_lam(s, m, L);
+    else return stress_of(s, m);
 }
 
 template <int NPC, int NVC>
@@ -516,7 +567,7 @@ struct QPoint {
     double d[NPC][2], mm[NVC][2];
     double hq;
 };
-template <int NPC, int NVC, bool QUAD, bool UHAT>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool LAM = false>
 __device__ __forceinline__ void stage_qpoints(const Tables* __restrict__ tab, const Elem<NPC, NVC>& el, double aK, int lane, int nlanes,
                                               QPoint<NPC, NVC>* sq) {
     const int nq = tab->nq;
@@ -524,10 +575,14 @@ __device__ __forceinline__ void stage_qpoints(const Tables* __restrict__ tab, co
         QPoint<NPC, NVC> p;
         qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], p.g);
         local_derivs<NPC, NVC>(*tab, q, p.g.Q, p.d, p.mm);
-        Mat ex;
         p.hq = interp<NVC>(tab->N1[q], el.hn);
+        if constexpr (LAM) {
+            lam_measures(el.hK, tab->wS[q] * p.g.det, tab->w[q] * p.g.det, p.g.Ju, p.mat);
+        } else {
+        Mat ex;
         material<DERIV_NONE>(p.hq, interp<NVC>(tab->N1[q], el.En), interp<NVC>(tab->N1[q], el.nun), el.hK, tab->wS[q] * p.g.det,
                              tab->w[q] * p.g.det, p.g.Ju, p.mat, ex);
+        }
         p.mat.cm *= aK; p.mat.cb *= aK; p.mat.cs *= aK; p.mat.cd *= aK;
         sq[q] = p;
     }
@@ -730,7 +785,7 @@ __device__ __forceinline__ double group5_sum(double v, int s1, int s2, int s4) {
 }
 __device__ __host__ constexpr int apply_epb(int lpe) { return 4 * (64 / lpe); }      // elements per block of four waves
 
-template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS, int LPE>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool MASS, int LPE, bool LAM = false>
 __global__ void __launch_bounds__(256, 2)
 k_apply4(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const int* __restrict__ eorder, double aK, double aM,
          const double* __restrict__ x, double* __restrict__ ybuf, double* dotslot, double* zero_a, double* zero_b) {
@@ -744,6 +799,8 @@ k_apply4(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const int* __re
     __shared__ double sx[EPB][LD + 1];
     __shared__ double sg[EPB][GEO + 1];
     __shared__ double scm[MASS ? EPB : 1][MASS ? MAXQ : 1];     // inertia coefficient per (element, point); written and read by the same lane
+    // laminate mode: the cell's LAM_W (symmetrised) values, staged like the geometry (never held in registers)
+    __shared__ double slam[LAM ? EPB : 1][LAM ? LAM_W + 1 : 1];
     // the lanes of a quad work on different quadrature points, so the tables are indexed per lane: keep
     // them in LDS (a per-lane global/scalar load would park ~40 doubles of table data in VGPRs)
     __shared__ Tables stab;
@@ -802,6 +859,12 @@ k_apply4(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const int* __re
                 sx[le][i] = x[g];
             }
         }
+        if constexpr (LAM) {
+            const double* L = f.clt + (size_t)LAM_W * e;
+#pragma unroll
+            for (int k = 0; k < LAM_W; ++k)
+                if ((k % LPE) == sub) slam[le][k] = L[k];
+        }
     }
     __syncthreads();
     if (active) {
@@ -822,11 +885,17 @@ k_apply4(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const int* __re
             qp_geometry<NVC, QUAD, UHAT>(X, Uh, stab.N1[q], stab.dN1[q], g);
             Mat mat, ex;
             const double hq = interp<NVC>(stab.N1[q], ge + 6 * NVC);
+            if constexpr (LAM) {
+                lam_measures(hK, stab.wS[q] * g.det, stab.w[q] * g.det, g.Ju, mat);
+            } else {
             material<DERIV_NONE>(hq, interp<NVC>(stab.N1[q], ge + 7 * NVC), interp<NVC>(stab.N1[q], ge + 8 * NVC), hK,
                                  stab.wS[q] * g.det, stab.w[q] * g.det, g.Ju, mat, ex);
+            }
             mat.cm *= aK; mat.cb *= aK; mat.cs *= aK; mat.cd *= aK;
             const Gen s = strains_q<NPC, NVC>(stab, q, g, xe);
-            const Gen t = stress_of(s, mat);
+            Gen t;
+            if constexpr (LAM) t = stress_lam(s, mat, slam[row]);
+            else t = stress_of(s, mat);
             strains_T_q<NPC, NVC>(stab, q, g, t, ye);
             if (MASS)            // the inertia term's coefficient at this point, parked in LDS for the loop below
                 scm[row][q] = aM * interp<NVC>(stab.N1[q], ge + 9 * NVC) * hq * stab.w[q] * g.det * g.Ju;
@@ -865,7 +934,7 @@ k_apply4(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const int* __re
 }
 
 // diag += diag(K_elastic)
-template <int NPC, int NVC, bool QUAD, bool UHAT>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool LAM = false>
 __global__ void __launch_bounds__(128)
 k_diag(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double* __restrict__ diag) {
     constexpr int LD = 3 * NPC + 3 * NVC;
@@ -882,6 +951,32 @@ k_diag(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, double* __restric
         qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
         double d[NPC][2], mm[NVC][2];
         local_derivs<NPC, NVC>(*tab, q, g.Q, d, mm);
+        if constexpr (LAM) {
+            // laminate: diag = s_i . C s_i with s_i the strains of unit vector i (the coupling B ties the membrane and bending rows)
+            Mat mat;
+            lam_measures(el.hK, tab->wS[q] * g.det, tab->w[q] * g.det, g.Ju, mat);
+            const double* L = f.clt + (size_t)LAM_W * e;
+#pragma unroll
+            for (int i = 0; i < LD; ++i) {
+                const bool is_u = i < 3 * NPC;
+                const int a = is_u ? i / 3 : (i - 3 * NPC) / 3, cc = i - 3 * (is_u ? a : NPC + a);
+                const double dk0 = is_u ? d[a][0] : mm[a][0], dk1 = is_u ? d[a][1] : mm[a][1];
+                const double Mj = is_u ? 0.0 : tab->NR[q][a];
+                double G0[3], G1[3], th[3], T0[3], T1[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double ec = (c == cc) ? 1.0 : 0.0;
+                    G0[c] = is_u ? dk0 * ec : 0.0;
+                    G1[c] = is_u ? dk1 * ec : 0.0;
+                    th[c] = Mj * ec;
+                    T0[c] = is_u ? 0.0 : dk0 * ec;
+                    T1[c] = is_u ? 0.0 : dk1 * ec;
+                }
+                const Gen s = strains_reduced(g, G0, G1, th, T0, T1);
+                de[i] += gen_dot(s, stress_lam(s, mat, L));
+            }
+            continue;
+        }
         Mat mat, ex;
         material<DERIV_NONE>(interp<NVC>(tab->N1[q], el.hn), interp<NVC>(tab->N1[q], el.En),
                              interp<NVC>(tab->N1[q], el.nun), el.hK, tab->wS[q] * g.det, tab->w[q] * g.det, g.Ju, mat, ex);
@@ -1162,6 +1257,69 @@ k_dRdfield_T(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doubl
     }
 }
 
+// out[e][k] += scale * lam^T (dK / d laminate_e[k]) w  for the LAM_W values of every cell (laminate mode).  One thread per cell, which
+// owns its row of out: no atomics.  With lam = w and scale 1/2 it is the partial of the elastic energy.  The law acts through the
+// symmetric parts, so A_ij and A_ji share the derivative of their mean (the kernel never reads the laminate itself).
+template <int NPC, int NVC, bool QUAD, bool UHAT>
+__global__ void __launch_bounds__(128)
+k_dRdlam_T(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const double* __restrict__ w, const double* __restrict__ lam,
+           double scale, double* __restrict__ out) {
+    constexpr int LD = 3 * NPC + 3 * NVC;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m.nel) return;
+    Elem<NPC, NVC> el;
+    load_elem<NPC, NVC, UHAT>(m, f, e, el);
+    double we[LD], le[LD];
+#pragma unroll
+    for (int a = 0; a < NPC; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            we[3 * a + c] = w[3 * el.pid[a] + c];
+            le[3 * a + c] = lam[3 * el.pid[a] + c];
+        }
+#pragma unroll
+    for (int b = 0; b < NVC; ++b)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            we[3 * NPC + 3 * b + c] = w[m.ndof_u + 3 * rot_node(m, el, b) + c];
+            le[3 * NPC + 3 * b + c] = lam[m.ndof_u + 3 * rot_node(m, el, b) + c];
+        }
+    double ge[LAM_W];
+#pragma unroll
+    for (int k = 0; k < LAM_W; ++k) ge[k] = 0.0;
+    const int nq = tab->nq;
+    for (int q = 0; q < nq; ++q) {
+        QPG g;
+        qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
+        double d[NPC][2], mm[NVC][2];
+        local_derivs<NPC, NVC>(*tab, q, g.Q, d, mm);
+        Mat mat;
+        lam_measures(el.hK, tab->wS[q] * g.det, tab->w[q] * g.det, g.Ju, mat);
+        const Gen sw = strains<NPC, NVC>(g, d, mm, tab->NR[q], we);
+        const Gen sl = strains<NPC, NVC>(g, d, mm, tab->NR[q], le);
+        const double ew[3] = {sw.e00, sw.e11, sw.g01}, kw[3] = {sw.k00, sw.k11, sw.k01};
+        const double el_[3] = {sl.e00, sl.e11, sl.g01}, kl[3] = {sl.k00, sl.k11, sl.k01};
+        const double gw[2] = {sw.ga0, sw.ga1}, gl[2] = {sl.ga0, sl.ga1};
+        const double hm = 0.5 * mat.cm, hs = 0.5 * mat.cs;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                ge[3 * i + j] += hm * (el_[i] * ew[j] + el_[j] * ew[i]);
+                ge[9 + 3 * i + j] += hm * (el_[i] * kw[j] + el_[j] * kw[i] + kl[i] * ew[j] + kl[j] * ew[i]);
+                ge[18 + 3 * i + j] += hm * (kl[i] * kw[j] + kl[j] * kw[i]);
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) ge[27 + 2 * i + j] += hs * (gl[i] * gw[j] + gl[j] * gw[i]);
+        ge[31] += mat.cd * sl.om * sw.om;
+    }
+    double* o = out + (size_t)LAM_W * e;
+#pragma unroll
+    for (int k = 0; k < LAM_W; ++k) o[k] += scale * ge[k];
+}
+
 // y += (aK dK/dh[dh] + aM dM/dh[dh]) x : the directional derivative of the step operator along a thickness perturbation dh
 // (forward mode of the transient operator, state_operation_dynamic.py:295-316: dRdt assembled per level and multiplied by
 // d_inputs['thickness']) -- matrix-free, one thread per cell.  Not a hot kernel: T launches per forward-mode product.
@@ -1300,7 +1458,7 @@ k_dRdf_T(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const double* _
 
 // dense element matrices, one wave per element: K_e[i][j] = sum_q B_i^T C B_j
 // Column j of K_e is the operator applied to the unit vector e_j, so lanes own columns.
-template <int NPC, int NVC, bool QUAD, bool UHAT>
+template <int NPC, int NVC, bool QUAD, bool UHAT, bool LAM = false>
 __global__ void __launch_bounds__(64)          // 238 registers, two waves per SIMD (three: 1.05 against 0.95 ms; four: 3.4 ms, 212 B of scratch)
 k_element_matrices(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int first, int count, double* __restrict__ Ke) {
     constexpr int LD = 3 * NPC + 3 * NVC;
@@ -1312,8 +1470,9 @@ k_element_matrices(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int f
     load_elem<NPC, NVC, UHAT>(m, f, e, el);
     extern __shared__ double sq_raw[];
     QPoint<NPC, NVC>* sq = reinterpret_cast<QPoint<NPC, NVC>*>(sq_raw);     // nq points (stage_qpoints)
-    stage_qpoints<NPC, NVC, QUAD, UHAT>(tab, el, 1.0, j, 64, sq);
+    stage_qpoints<NPC, NVC, QUAD, UHAT, LAM>(tab, el, 1.0, j, 64, sq);
     if (j >= LD) return;
+    const double* L = LAM ? f.clt + (size_t)LAM_W * e : nullptr;     // laminate mode: the cell's values, uniform over the wave
     double ye[LD];
 #pragma unroll
     for (int i = 0; i < LD; ++i) ye[i] = 0.0;
@@ -1339,7 +1498,7 @@ k_element_matrices(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, int f
             T1[c] = is_u ? 0.0 : dk1 * ec;
         }
         const Gen s = strains_reduced(p.g, G0, G1, th, T0, T1);
-        const Gen t = stress_of(s, p.mat);
+        const Gen t = law<LAM>(s, p.mat, L);
         strains_T<NPC, NVC>(p.g, p.d, p.mm, tab->NR[q], t, ye);
     }
     double* out = Ke + (size_t)le * LD * LD;

@@ -20,13 +20,14 @@ from ..mesh_io import readFEAMesh, reconstructFEAMesh            # noqa: F401  (
 
 
 class FunctionSpace:
-    """kind: 'W' (CG2xCG1 state), 'VT' (thickness-like scalars), 'VF' (pressure), 'VU' (mesh motion)."""
+    """kind: 'W' (CG2xCG1 state), 'VT' (thickness-like scalars), 'VF' (pressure), 'VU' (mesh motion), 'VL' (the laminate: DG0,
+    32 values per cell, femo_set_laminate)."""
 
     def __init__(self, ctx: ShellContext, kind: str):
         self.ctx, self.kind = ctx, kind
         m = ctx.mesh
         self.dim = {"W": m.ndof, "VT": m.nel if ctx.element_wise_material else m.nn,
-                    "VF": 3 * (m.nel if ctx.elementwise_pressure else m.nn), "VU": 3 * m.nn}[kind]
+                    "VF": 3 * (m.nel if ctx.elementwise_pressure else m.nn), "VU": 3 * m.nn, "VL": 32 * m.nel}[kind]
 
 
 class Function:
@@ -303,7 +304,7 @@ class FEA:
     def add_input(self, name, function: Function, init_val=1.0, record=False):
         if name in self.inputs_dict:
             raise ValueError("name has already been used for an input")
-        function.set(np.array([init_val]))
+        function.set(np.asarray(init_val, dtype=np.float64).ravel())       # a scalar broadcasts; the laminate needs all its values
         self.inputs_dict[name] = dict(function=function, function_space=function.function_space,
                                       shape=function.function_space.dim, recorder=None, record=False)
 

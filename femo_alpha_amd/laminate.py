@@ -1,0 +1,145 @@
+"""Laminate stiffness for the composite shell law (host numpy; ``ShellContext.set_laminate`` / ``femo_set_laminate``).
+
+The reference's ``MaterialModelComposite`` takes per-cell CLT matrices ``A``, ``B``, ``D`` (3 x 3) and ``A_s`` (2 x 2)
+(femo_alpha/rm_shell/linear_shell_fenicsx/linear_shell_model.py:159-190) and leaves their computation to the caller.  This module is
+that caller-side step: classical lamination theory from orthotropic plies, a rotation in the element plane, and the 32-wide packing of
+the C ABI.
+
+Conventions (include/femo_hip.h, femo_set_laminate):
+  * Voigt strains eps = (e00, e11, 2 e01), kappa = (k00, k11, 2 k01), gamma = (g0, g1) in the local frame of every point:
+    laminate axis 1 lies along E0, from vertex 0 toward vertex 1 of the cell.
+  * Plies are listed bottom to top (z from -H/2 to H/2 along the cell normal); angles in degrees, measured from E0 toward E1.
+  * ``A_s = K_SHEAR * sum_k Qs_k t_k`` with the project's shear correction 0.833, so one isotropic ply of thickness h gives the
+    single-layer law: (h C, 0, h^3 / 12 C, 0.833 G h I).
+  * The strain at height z above the reference surface is eps - z kappa (u(z) = u_mid - z E2 x theta, linear_shell_model.py:392-398),
+    so B = -int z Qbar dz: a ply above the mid-surface contributes a negative B.
+  * A reference-plane offset -- the mid-surface o above the reference surface (the reference's ``shl_offset``; its single layer on
+    top of the reference surface, ``getSingleLayerCLT`` with BOT, is o = h / 2) -- is the transform A' = A, B' = B - o A,
+    D' = D - o (B + B^T) + o^2 A (``offset``).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+K_SHEAR = 0.833          # linear_shell_model.py:146
+LAM_W = 32               # [A (9), B (9), D (9), A_s (4), c_drill] per cell
+
+
+def _t_eps(theta_deg):
+    """Strain transformation eps_ply = T(theta) eps_frame of the in-plane Voigt strains (engineering shear), (..., 3, 3)."""
+    th = np.deg2rad(np.asarray(theta_deg, dtype=np.float64))
+    m, n = np.cos(th), np.sin(th)
+    T = np.empty(th.shape + (3, 3))
+    T[..., 0, 0], T[..., 0, 1], T[..., 0, 2] = m * m, n * n, m * n
+    T[..., 1, 0], T[..., 1, 1], T[..., 1, 2] = n * n, m * m, -m * n
+    T[..., 2, 0], T[..., 2, 1], T[..., 2, 2] = -2 * m * n, 2 * m * n, m * m - n * n
+    return T
+
+
+def _r_shear(theta_deg):
+    """gamma_ply = R(theta) gamma_frame of the transverse shear strains, (..., 2, 2)."""
+    th = np.deg2rad(np.asarray(theta_deg, dtype=np.float64))
+    m, n = np.cos(th), np.sin(th)
+    R = np.empty(th.shape + (2, 2))
+    R[..., 0, 0], R[..., 0, 1], R[..., 1, 0], R[..., 1, 1] = m, n, -n, m
+    return R
+
+
+def ply_stiffness(E1, E2, G12, nu12, G13, G23, theta):
+    """Reduced stiffness Qbar (..., 3, 3) and transverse shear stiffness Qs (..., 2, 2) of plies rotated by ``theta`` degrees."""
+    E1, E2, G12, nu12, G13, G23 = (np.asarray(x, dtype=np.float64) for x in (E1, E2, G12, nu12, G13, G23))
+    shape = np.broadcast(E1, E2, G12, nu12, G13, G23, np.asarray(theta)).shape
+    nu21 = nu12 * E2 / E1
+    den = 1.0 - nu12 * nu21
+    Q = np.zeros(shape + (3, 3))
+    Q[..., 0, 0] = E1 / den
+    Q[..., 1, 1] = E2 / den
+    Q[..., 0, 1] = Q[..., 1, 0] = nu12 * E2 / den
+    Q[..., 2, 2] = G12
+    Qs = np.zeros(shape + (2, 2))
+    Qs[..., 0, 0], Qs[..., 1, 1] = G13, G23
+    T = np.broadcast_to(_t_eps(theta), shape + (3, 3))
+    R = np.broadcast_to(_r_shear(theta), shape + (2, 2))
+    Qbar = np.einsum("...ki,...kl,...lj->...ij", T, Q, T)
+    Qsbar = np.einsum("...ki,...kl,...lj->...ij", R, Qs, R)
+    return Qbar, Qsbar
+
+
+def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacobian=False):
+    """Classical lamination theory.  Every argument is an array of shape (nply,) (one layup for all cells) or (nel, nply); plies bottom
+    to top, ``theta`` in degrees from E0.  Returns (A, B, D, A_s) of shapes (nel, 3, 3) x 3 and (nel, 2, 2) (nel = 1 for a single
+    layup); with ``jacobian=True`` also (dA, dB, dD, dA_s), the derivatives with respect to the ply thicknesses, shapes
+    (nel, nply, 3, 3) x 3 and (nel, nply, 2, 2) -- the chain from d/d laminate to d/d t."""
+    args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, G13, G23, t, theta)]
+    args = np.broadcast_arrays(*args)
+    E1, E2, G12, nu12, G13, G23, t, theta = args
+    Qb, Qs = ply_stiffness(E1, E2, G12, nu12, G13, G23, theta)          # (nel, nply, 3, 3), (nel, nply, 2, 2)
+    H = t.sum(axis=1, keepdims=True)
+    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H    # (nel, nply + 1) ply interfaces
+    z0, z1 = z[:, :-1], z[:, 1:]
+    A = np.einsum("ek,ekij->eij", z1 - z0, Qb)
+    # the strain at height z is eps - z kappa (u(z) = u_mid - z E2 x theta, linear_shell_model.py:392-398): B = -int z Qbar dz
+    B = -0.5 * np.einsum("ek,ekij->eij", z1 ** 2 - z0 ** 2, Qb)
+    D = np.einsum("ek,ekij->eij", z1 ** 3 - z0 ** 3, Qb) / 3.0
+    As = k_shear * np.einsum("ek,ekij->eij", t, Qs)
+    if not jacobian:
+        return A, B, D, As
+    nply = t.shape[1]
+    # dz_i / dt_j = -1/2 + [j < i]
+    dz = -0.5 + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)     # (nply + 1, nply) [i, j]
+    dz0, dz1 = dz[:-1], dz[1:]                                                                    # (nply, nply) [k, j]
+    dA = np.einsum("kj,ekab->ejab", dz1 - dz0, Qb)
+    dB = np.einsum("ek,kj,ekab->ejab", z0, dz0, Qb) - np.einsum("ek,kj,ekab->ejab", z1, dz1, Qb)
+    dD = np.einsum("ek,kj,ekab->ejab", z1 ** 2, dz1, Qb) - np.einsum("ek,kj,ekab->ejab", z0 ** 2, dz0, Qb)
+    dAs = k_shear * Qs
+    return (A, B, D, As), (dA, dB, dD, dAs)
+
+
+def offset(clt, o):
+    """(A, B, D, A_s) about a reference surface that lies ``o`` below the mid-surface the laminate was built about."""
+    A, B, D, As = (np.asarray(x, dtype=np.float64) for x in clt)
+    o = np.asarray(o, dtype=np.float64).reshape(-1, 1, 1) if np.ndim(o) else o
+    return A, B - o * A, D - o * (B + np.swapaxes(B, -1, -2)) + o * o * A, As
+
+
+def rotate_clt(clt, angle):
+    """The laminate (A, B, D, A_s) turned by ``angle`` degrees in the element plane: every ply angle grows by ``angle``.
+    ``angle``: a scalar or one value per cell."""
+    A, B, D, As = (np.asarray(x, dtype=np.float64) for x in clt)
+    T = _t_eps(angle)
+    R = _r_shear(angle)
+    rot = lambda X, M: np.einsum("...ki,...kl,...lj->...ij", M, X, M)
+    return rot(A, T), rot(B, T), rot(D, T), rot(As, R)
+
+
+def pack(A, B, D, As, c_drill=None):
+    """The (nel, 32) array femo_set_laminate takes: [A, B, D (row-major), A_s, c_drill] per cell.  ``c_drill=None`` applies the
+    reference's drilling coefficient alpha = 12 max(D) over all entries of all cells (linear_shell_model.py:284-296), a constant;
+    a scalar or one value per cell is used as given (c_drill = E h^3 reproduces the single-layer law's drilling term)."""
+    A, B, D = (np.asarray(x, dtype=np.float64).reshape(-1, 3, 3) for x in (A, B, D))
+    As = np.asarray(As, dtype=np.float64).reshape(-1, 2, 2)
+    nel = max(len(A), len(B), len(D), len(As))
+    out = np.empty((nel, LAM_W))
+    out[:, 0:9] = np.broadcast_to(A.reshape(-1, 9), (nel, 9))
+    out[:, 9:18] = np.broadcast_to(B.reshape(-1, 9), (nel, 9))
+    out[:, 18:27] = np.broadcast_to(D.reshape(-1, 9), (nel, 9))
+    out[:, 27:31] = np.broadcast_to(As.reshape(-1, 4), (nel, 4))
+    out[:, 31] = 12.0 * float(np.max(D)) if c_drill is None else np.broadcast_to(np.asarray(c_drill, dtype=np.float64), (nel,))
+    return out
+
+
+def unpack(clt):
+    """(A, B, D, A_s, c_drill) of a (nel, 32) array."""
+    c = np.asarray(clt, dtype=np.float64).reshape(-1, LAM_W)
+    return (c[:, 0:9].reshape(-1, 3, 3), c[:, 9:18].reshape(-1, 3, 3), c[:, 18:27].reshape(-1, 3, 3), c[:, 27:31].reshape(-1, 2, 2),
+            c[:, 31].copy())
+
+
+def isotropic(h, E, nu, c_drill=None):
+    """The per-cell laminate of one isotropic ply (thickness h, E, nu per cell): the single-layer law of the isotropic path;
+    ``c_drill=None`` gives E h^3, which makes it reproduce that path's drilling term too."""
+    h, E, nu = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64).ravel() for x in (h, E, nu)))
+    G = E / (2 * (1 + nu))
+    A, B, D, As = clt_from_plies(E[:, None], E[:, None], G[:, None], nu[:, None], G[:, None], G[:, None], h[:, None],
+                                 np.zeros((len(h), 1)))
+    return pack(A, B, D, As, E * h ** 3 if c_drill is None else c_drill)

@@ -67,7 +67,7 @@ def createCustomMeasure(mesh: ShellMesh, dim, SubdomainFunc, measure: str, tag: 
 class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
-                 device=0, renumber=False, nquad=None):
+                 device=0, renumber=False, nquad=None, laminate=False):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -98,6 +98,9 @@ class RMShellModel:
         self.nel, self.nn = mesh.nel, mesh.nn
         self.elementwise_pressure = elementwise_pressure
         self.device = device
+        # laminate=True: the composite law with a DG0 "laminate" input of (nel, 32) values per cell in caller order
+        # ([A, B, D, A_s, c_drill], femo_alpha_amd.laminate.pack), an argument of disp_solid and elastic_energy
+        self.laminate = bool(laminate)
         # n x n Gauss points per quadrilateral for the static forms (2..5).  The reference leaves the degree to UFL's
         # estimate, which on quadrilaterals comes out near 47 (scripts/ufl_degree_estimate.py): exact integration.  Default:
         # what the mesh asks for -- 4 on affine cells (exact there), 5 as soon as one cell is warped (within 1e-9 of the
@@ -142,7 +145,7 @@ class RMShellModel:
         mesh = self.mesh
         shell_pde = self.shell_pde = RMShellPDE(mesh, element_wise_material=self.element_wise_material,
                                                 elementwise_pressure=self.elementwise_pressure, device=self.device,
-                                                nquad=self._nquad_arg)
+                                                nquad=self._nquad_arg, laminate=self.laminate)
         fea = FEA(mesh)
         fea.PDE_SOLVER = "Newton"
         fea.REPORT = False
@@ -171,11 +174,16 @@ class RMShellModel:
         fea.add_input("nu", nu, init_val=1.0)
         fea.add_input("density", density, init_val=1.0)
         fea.add_input("uhat", uhat, init_val=0.0)
+        lam_args = []
+        if self.laminate:
+            lam = Function(shell_pde.VL).bind("laminate")
+            fea.add_input("laminate", lam, init_val=shell_pde.laminate_init)
+            lam_args = ["laminate"]
         fea.add_state(name="disp_solid", function=w, residual_form=residual_form,
-                      arguments=["thickness", "F_solid", "E", "nu", "uhat"])
+                      arguments=["thickness", "F_solid", "E", "nu", "uhat"] + lam_args)
         fea.add_output(name="compliance", form=compliance_form, arguments=["disp_solid", "F_solid", "thickness", "uhat"])
         fea.add_output(name="mass", form=mass_form, arguments=["thickness", "density", "uhat"])
-        fea.add_output(name="elastic_energy", form=elastic_energy_form, arguments=["thickness", "disp_solid", "E", "uhat"])
+        fea.add_output(name="elastic_energy", form=elastic_energy_form, arguments=["thickness", "disp_solid", "E", "uhat"] + lam_args)
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         if self.mesh_tags is not None:
             self.set_up_subdomains(self.mesh_tags)
@@ -188,7 +196,11 @@ class RMShellModel:
                              function_space=("DG", 1), record=False, vtk=True)
         self.fea = fea
 
-    def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True):
+    def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None):
+        """laminate: (nel, 32) per cell in caller order -- required with laminate=True, refused otherwise.  thickness, E, nu and density
+        stay inputs in laminate mode (mass, regularisation, stress outputs)."""
+        if self.laminate != (laminate is not None):
+            raise ValueError("a laminate is required with laminate=True and refused without it")
         shell_inputs = csdl.VariableGroup()
         mesh = self.mesh
         # caller order == solver order here; the gathers are kept so that a renumbered mesh object
@@ -217,6 +229,9 @@ class RMShellModel:
         shell_inputs.uhat = reshaped_node_disp
         for n in ("thickness", "E", "nu", "density"):
             getattr(shell_inputs, n).add_name(n)
+        if self.laminate:
+            shell_inputs.laminate = laminate[self.cell_of_new].reshape((-1,))      # caller cell order -> solver order
+            shell_inputs.laminate.add_name("laminate")
 
         solid_model = FEAModel(fea=[self.fea], fea_name="rm_shell")
         shell_outputs = solid_model.evaluate(shell_inputs, debug_mode=debug_mode)

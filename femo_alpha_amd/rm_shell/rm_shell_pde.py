@@ -23,7 +23,7 @@ class FacetSet:
 
 class RMShellPDE:
     def __init__(self, mesh, element_wise_material=False, elementwise_pressure=False, nquad=None, device=0, solver="direct",
-                 element_type=None):
+                 element_type=None, laminate=False):
         # element_type: 'CG2CG1' (what the reference's RMShellPDE hard-codes, rm_shell_pde.py:27) or 'CG1CG1' (the other quadrilateral /
         # triangle choice of ShellElement.setUpFunctionSpace, linear_shell_model.py:74-79); None: the element the mesh object carries
         if element_type is not None and element_type != mesh.element:
@@ -43,6 +43,16 @@ class RMShellPDE:
         self.VT = FunctionSpace(self.ctx, "VT")        # rm_shell_pde.py:37-40
         self.VF = FunctionSpace(self.ctx, "VF")        # :41-44
         self.VU = FunctionSpace(self.ctx, "VU")        # :45
+        # laminate=True: the composite law (MaterialModelComposite, linear_shell_model.py:159-190) with per-cell CLT data, a DG0 space
+        # of 32 values per cell [A, B, D, A_s, c_drill] (femo_alpha_amd.laminate.pack).  The context enters laminate mode at once with a
+        # one-ply placeholder (1 mm of a unit-modulus isotropic ply) that the model's "laminate" input replaces.
+        self.laminate = bool(laminate)
+        self.VL = None
+        if self.laminate:
+            from ..laminate import isotropic
+            self.VL = FunctionSpace(self.ctx, "VL")
+            self.laminate_init = isotropic(np.full(mesh.nel, 1e-3), 1.0, 0.3).ravel()
+            self.ctx.set_laminate(self.laminate_init)
 
     # ------------------------------------------------------------------ residual
     def pdeRes(self, h, w, uhat, f, E, nu, penalty=False, dss=None, dSS=None, g=None):

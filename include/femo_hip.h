@@ -67,7 +67,8 @@ int femo_create_element(femo_ctx** out, int device, int32_t nn, int32_t nel, int
 void femo_destroy(femo_ctx* ctx);
 
 int64_t femo_ndof(const femo_ctx* ctx);
-/* Length of an input field: "thickness","E","nu","density" (nn or nel), "F_solid" (3*nn or 3*nel), "uhat" (3*nn). */
+/* Length of an input field: "thickness","E","nu","density" (nn or nel), "F_solid" (3*nn or 3*nel), "uhat" (3*nn),
+ * "laminate" (32*nel, laminate mode only; -1 otherwise). */
 int64_t femo_field_size(const femo_ctx* ctx, const char* name);
 
 /* Dirichlet data.
@@ -85,6 +86,31 @@ int femo_set_strong_dofs(femo_ctx* ctx, int32_t n, const int32_t* dofs);
  * (linear_shell_model.py:323-333; the reference's RMShellModel always passes zeros, rm_shell_model.py:183-185). */
 int femo_set_field(femo_ctx* ctx, const char* name, const double* values, int64_t n);
 int femo_get_field(femo_ctx* ctx, const char* name, double* values, int64_t n);
+
+/* Laminated composite law -- the reference's MaterialModelComposite with ElasticModelShapeOpt (linear_shell_model.py:159-190, 268-296).
+ * n == 32 * nel enters laminate mode (or replaces its values): per cell, row-major,
+ *     [A (3x3), B (3x3), D (3x3), A_s (2x2), c_drill]
+ * acting on the Voigt strains eps = (e00, e11, 2 e01), kappa = (k00, k11, 2 k01), gamma = (g0, g1) of the local frame of every
+ * quadrature point, E0 = unit(J[:,0]), E1 = E2 x E0 (kinematics.py:54-70).  Frame convention: laminate axis 1 lies along E0, i.e. from
+ * vertex 0 toward vertex 1 of the cell as given; reversing a cell's orientation (its normal E2) flips the sign of B.  Through the thickness
+ * the strain at height z along E2 is eps - z kappa (u(z) = u_mid - z E2 x theta, linear_shell_model.py:392-398), so a laminate built about
+ * its mid-surface has B = -int z Qbar dz (femo_alpha_amd/laminate.py, plies bottom to top along E2).  The energy density is
+ * 1/2 (eps.A eps + eps.B kappa + kappa.B eps + kappa.D kappa) + 1/2 gamma.A_s gamma + 1/2 c_drill / h_K^2 omega^2; the operator is its
+ * Hessian, so only the symmetric parts act (non-symmetric input is accepted, as in the reference).  Measures as on the isotropic path:
+ * membrane, bending and coupling with the strain rule and no J(uhat); shear with the strain rule times J(uhat); drilling with the full
+ * rule times J(uhat) (femo_set_strain_quadrature applies).  The reference's drilling coefficient is 12 max(D) over all cells, a constant
+ * (the Python layer fills it in); a per-cell c_drill = E h^3 makes a one-ply isotropic laminate reproduce the single-layer law.
+ * A reference-plane offset (the mid-surface o above the reference surface) is the host transform A' = A, B' = B - o A,
+ * D' = D - o (B + B^T) + o^2 A.
+ * Refused with the cell index: non-finite values, a [[A, B], [B, D]] or A_s block whose symmetric part is not positive definite, c_drill <= 0.
+ * clt == NULL with n == 0 returns to the single-layer law.  Either way the factor and the Jacobi diagonal are rebuilt before the next solve.
+ * In laminate mode:
+ *   - "laminate" is an ordinary field (femo_field_size / femo_set_field / femo_get_field), and an argument of femo_dRdarg_T,
+ *     femo_total_gradient(s) and femo_dfunctional(ctx, "elastic_energy", "laminate", ...);
+ *   - thickness, E, nu and density stay inputs: mass, volume, the compliance regularisation and the stress outputs (the reference's
+ *     ShellStressRM: the single-layer recovery from thickness, E and nu) use them; R does not, so (dR/d thickness|E|nu)^T lambda is zero;
+ *   - the transient operator (femo_set_operator with aM != 0, femo_newmark_*) and the element-partitioned driver (femo_dist_*) are refused. */
+int femo_set_laminate(femo_ctx* ctx, const double* clt, int64_t n);
 
 /* State access -- replaces getFuncArray / setFuncArray on the state Function
  * (fea/utils_dolfinx.py:174-186). */
