@@ -52,6 +52,7 @@ SIGNATURES = {
     "femo_solve_state": (C.c_int, [C.c_void_p, C.c_int, _c_int32_p, _c_double_p]),
     "femo_solve_linear": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
     "femo_solve_linear_multi": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
+    "femo_frontal_apply": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p]),
     "femo_total_gradients": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), _c_int32_p, C.c_char_p, _c_double_p, C.c_int64,
                                        _c_int32_p, _c_double_p]),
     "femo_force_to_pressure": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_double, C.c_int32, _c_int32_p, _c_double_p]),

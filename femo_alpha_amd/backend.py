@@ -307,6 +307,16 @@ class ShellContext:
         self._chk(self.lib.femo_solve_linear_multi(self._h, nr, dptr(rhs), dptr(x), iptr(it), dptr(rr)))
         return x, it, rr
 
+    def frontal_apply(self, V):
+        """M^-1 applied once to the rows of ``V`` ((nrhs, ndof) or one vector), M the multifrontal factorisation (made if there is none),
+        no Krylov iteration: the preconditioner application of the PCG loop, one vector or grouped as femo_solve_linear_multi groups them
+        (femo_frontal_apply).  Returns an array of the shape of ``V``."""
+        V = np.asarray(V, dtype=np.float64)
+        rhs = np.ascontiguousarray(V.reshape(-1, self.ndof))
+        out = np.empty_like(rhs)
+        self._chk(self.lib.femo_frontal_apply(self._h, rhs.shape[0], dptr(rhs), dptr(out)))
+        return out.reshape(V.shape)
+
     def force_to_pressure(self, force, rtol=1e-13, maxit=500):
         """pressure = A^-1 force, A the consistent mass matrix of [CG1]^3 (rm_shell_model.py:414-421): Jacobi-PCG on the device."""
         f = self._vec(force)

@@ -274,6 +274,7 @@ struct femo_ctx {
         long long p_doubles = 0, s_doubles = 0, linv_doubles = 0, x_doubles = 0;
         int swork_slots = 1;                  // 128 x 128 scratch blocks for the diagonal-block inverses of the non-wide levels
         int max_nf = 0;
+        int multi_nr = 4;                     // most interleaved vectors whose one-workgroup-per-front sweeps fit the LDS (4, 2 or 1)
         double t_factor_ms = 0, t_assemble_ms = 0;
         int pivots_fixed = 0;
         bool profile = false;                 // time every kernel class with HIP events (slower)
@@ -1603,9 +1604,15 @@ static int mr_alloc(femo_ctx* c) {
     return 0;
 }
 
-// z_r = (L L^T)^-1 r_r for g = 1 .. 4 vectors at once: 3 vectors ride as 4 (the fourth lane carries zeros)
+// z_r = (L L^T)^-1 r_r for g = 1 .. 4 vectors at once: 3 vectors ride as 4 (the fourth lane carries zeros).  A group larger than the
+// plan's LDS allows (fr.multi_nr: the largest one-workgroup-per-front sweep times the vectors) goes through in pairs or one by one.
 static int frontal_apply_group(femo_ctx* c, int g, double* const* rin, double* const* zout) {
     const int64_t n = c->ndof;
+    if (g > c->fr.multi_nr) {
+        for (int r0 = 0; r0 < g; r0 += c->fr.multi_nr)
+            if (int rc = frontal_apply_group(c, std::min(c->fr.multi_nr, g - r0), rin + r0, zout + r0)) return rc;
+        return 0;
+    }
     if (g == 1) {
         HIPCHK(c, hipMemcpyAsync(zout[0], rin[0], (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         return frontal_solve(c, zout[0]);
@@ -1655,7 +1662,11 @@ static int pcg_frontal_group(femo_ctx* c, int g, double* const* B, double* const
     HIPCHK(c, hipStreamSynchronize(c->stream));
     bool active[4] = {false, false, false, false};
     int its[4] = {0, 0, 0, 0};
-    for (int r = 0; r < g; ++r) { bb[r] = rr[r] = c->mr_scal_host[8 * r + 3]; active[r] = bb[r] > 0; }
+    for (int r = 0; r < g; ++r) {
+        bb[r] = rr[r] = c->mr_scal_host[8 * r + 3];
+        if (!std::isfinite(bb[r])) return fail(c, "PCG: the right-hand side is not finite (NaN or infinite b.b)");
+        active[r] = bb[r] > 0;
+    }
     int k = 0;
     auto any_active = [&]() { for (int r = 0; r < g; ++r) if (active[r]) return true; return false; };
     while (any_active() && k < c->maxit) {
@@ -1682,6 +1693,7 @@ static int pcg_frontal_group(femo_ctx* c, int g, double* const* B, double* const
             rr[r] = c->mr_scal_host[8 * r + 3];
             its[r] = k;
             if (!(pAp > 0)) return fail(c, "PCG broke down: p.Ap <= 0 (preconditioner or operator not positive definite)");
+            if (!(rr[r] == rr[r])) return fail(c, "PCG broke down (NaN residual)");
             if (!(rr[r] > c->rtol * c->rtol * bb[r])) active[r] = false;
         }
     }
@@ -1792,6 +1804,10 @@ static int pcg_frontal(femo_ctx* c, double* b, double* x, bool zero_guess, int32
     if (mask) hipLaunchKernelGGL(k_mask_zero, dim3(vg), dim3(256), 0, c->stream, b, mask, n);
     double bb = 0, rr = 0, pAp = 0;
     if (dot(b, b, &bb)) return 1;
+    if (!std::isfinite(bb)) {
+        if (c->fr.ahead_levels > 0) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_a[2], 0)); c->fr.ahead_levels = 0; }   // the started sweep ends first
+        return fail(c, "PCG: the right-hand side is not finite (NaN or infinite b.b)");
+    }
     // r = b - A x
     if (zero_guess) {
         hipLaunchKernelGGL(k_fill, dim3(vg), dim3(256), 0, c->stream, x, 0.0, n);
@@ -2944,6 +2960,38 @@ int femo_solve_linear_multi(femo_ctx* c, int32_t nrhs, const double* rhs, double
     return rc;
 }
 
+int femo_frontal_apply(femo_ctx* c, int32_t nrhs, const double* in, double* out) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nrhs < 1 || !in || !out) return fail(c, "femo_frontal_apply: nrhs >= 1 vectors, one after the other");
+    if (!c->fr.ready) return fail(c, "no frontal plan");
+    if (!c->fr.factored)
+        if (int rc = frontal_factorize(c)) return rc;
+    const size_t n = (size_t)c->ndof;
+    if (nrhs == 1 || !multi_sweeps_apply(c)) {
+        // the route of pcg_frontal: the vector in c->z, the captured graph when "sweep_graph" is on, the scaling of "equilibrate"
+        for (int r = 0; r < nrhs; ++r) {
+            HIPCHK(c, hipMemcpy(c->z, in + (size_t)r * n, n * sizeof(double), hipMemcpyHostToDevice));
+            if (int rc = frontal_solve_z(c)) return rc;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipMemcpy(out + (size_t)r * n, c->z, n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+    // the route of pcg_frontal_group: groups of up to four (three ride as four)
+    if (mr_alloc(c)) return 1;
+    HIPCHK(c, c->mr_io.grow(2 * (size_t)nrhs * n));
+    double* Bd = c->mr_io;
+    double* Xd = Bd + (size_t)nrhs * n;
+    std::vector<double*> B(nrhs), X(nrhs);
+    for (int r = 0; r < nrhs; ++r) { B[r] = Bd + r * n; X[r] = Xd + r * n; }
+    HIPCHK(c, hipMemcpy(Bd, in, (size_t)nrhs * n * sizeof(double), hipMemcpyHostToDevice));
+    for (int r0 = 0; r0 < nrhs; r0 += 4)
+        if (int rc = frontal_apply_group(c, std::min(4, nrhs - r0), B.data() + r0, X.data() + r0)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, Xd, (size_t)nrhs * n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Total derivatives of SEVERAL functionals of the state with respect to one argument: the adjoint right-hand sides dJ_i/dw are known
 // together, so their solves share the sweeps (the reference solves one adjoint per output: state_operation.py:188-220 called once per
 // registered output of `disp_solid`, rm_shell_model.py:221-253).  subdomains[i] restricts functional i to a tagged sub-domain
@@ -3230,7 +3278,26 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
         HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_wide_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_wide_bwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     }
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block, hipFuncAttributeMaxDynamicSharedMemorySize,
+    // ... and of their NR-vector forms (sweeps_multi.h), NR times as much on the levels that are not wide: the grouped applications
+    // take as many interleaved vectors as fit (frontal_apply_group splits a group into pairs or single vectors beyond that)
+    {
+        int small_sweep = 0;
+        for (int L = 0; L < nlevels; ++L)
+            if (!fr.h_level_wide[L] && fr.h_level_maxnp[L] > 0)
+                small_sweep = std::max(small_sweep, fr.h_level_maxnp[L] + fr.h_level_maxnb[L] + SMALL_PART);
+        const size_t lds_max = 150 * 1024;
+        fr.multi_nr = (size_t)small_sweep * 4 * sizeof(double) <= lds_max ? 4 : (size_t)small_sweep * 2 * sizeof(double) <= lds_max ? 2 : 1;
+        // the attribute is per kernel, not per context: the bound itself, so that no later plan lowers it under an earlier one
+        if (fr.multi_nr >= 2) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_front_fwd_small_m<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_front_bwd_small_m<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        }
+        if (fr.multi_nr >= 4) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_front_fwd_small_m<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_front_bwd_small_m<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        }
+    }
+    HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block,hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block_lds_blocks(NBO / NB) * sizeof(blk32))));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_panel_rows_preload, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_ROWS_PRELOAD_LDS));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_trailing_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * sizeof(double) * 16 * LSTRB)));
@@ -3308,6 +3375,7 @@ int femo_sweep_profile_multi(femo_ctx* c, int32_t nrhs, double* out, int64_t n) 
     auto& fr = c->fr;
     if (!fr.ready) return fail(c, "no frontal plan");
     if (nrhs != 2 && nrhs != 4) return fail(c, "nrhs: 2 or 4");
+    if (nrhs > fr.multi_nr) return fail(c, "the largest front's sweeps do not fit the LDS with this many interleaved vectors");
     if (n < 2 * (int64_t)fr.nlevels) return fail(c, "output too small: 2 * nlevels doubles");
     if (!fr.factored)
         if (int rc = frontal_factorize(c)) return rc;
@@ -4669,6 +4737,7 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             if (mr_alloc(c)) return 1;
             if (s == "sweeps1") { hipLaunchKernelGGL(k_fill, dim3(vg), dim3(256), 0, c->stream, c->z, 1.0, n); return frontal_solve(c, c->z); }
             const int nr = s == "sweeps2" ? 2 : 4;
+            if (nr > c->fr.multi_nr) return fail(c, "the largest front's sweeps do not fit the LDS with this many interleaved vectors");
             hipLaunchKernelGGL(k_fill, dim3(vec_grid(n * nr)), dim3(256), 0, c->stream, c->mr_v, 1.0, n * nr);
             return nr == 2 ? frontal_solve_multi<2>(c, c->mr_v, c->mr_y) : frontal_solve_multi<4>(c, c->mr_v, c->mr_y);
         }

@@ -236,6 +236,12 @@ int femo_solve_linear(femo_ctx* ctx, const double* rhs, double* x, int32_t* iter
  * of nrhs separate femo_solve_linear calls.  Replaces repeated StateOperation.apply_inverse_jacobian calls (state_operation.py:188-220),
  * forward or reverse (K is symmetric).  Status 4 if any right-hand side stops at maxit short of rtol (option "strict"). */
 int femo_solve_linear_multi(femo_ctx* ctx, int32_t nrhs, const double* rhs, double* x, int32_t* iters, double* relres);
+/* One application of the multifrontal preconditioner, no Krylov iteration: out_r = M^-1 in_r for nrhs host vectors of femo_ndof entries,
+ * one after the other, with M = L L^T the current factorisation (made first if there is none; femo_enable_frontal's plan needed).  The
+ * route is that of the PCG loop: one vector through the context's own sweep (the captured graph of option "sweep_graph", the scaling of
+ * option "equilibrate"); several, when the grouped solves apply, in groups of up to four interleaved vectors as femo_solve_linear_multi
+ * sweeps them.  For checking the factor itself: PCG corrects any error of M^-1, this call does not. */
+int femo_frontal_apply(femo_ctx* ctx, int32_t nrhs, const double* in, double* out);
 
 /* pressure = A^-1 force with A the consistent mass matrix of the pressure space [CG1]^3 (node-major xyz, 3 nn entries) -- replaces
  * csdl.solve_linear(A, force) on the matrix of RMShellPDE.construct_force_to_pressure_map (rm_shell/rm_shell_model.py:414-421,

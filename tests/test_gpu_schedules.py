@@ -10,7 +10,19 @@ from femo_alpha_amd.mesh import plate_mesh, wing_skin_mesh
 pytestmark = pytest.mark.gpu
 
 
-def _solve(m, marker, strong, leaf, pre, post):
+def _reference_K(m, marker, strong):
+    """The oracle's K of the problem _solve sets up."""
+    from oracle.rm_shell_oracle import ShellOracle
+    r = np.random.default_rng(1)
+    o = ShellOracle(m, strong_dofs=m.locate_dofs_geometrical(marker) if strong else None,
+                    penalty_facets=None if strong else m.penalty_facets(marker))
+    o.set_fields(h=0.02 * (1 + 0.3 * r.uniform(-1, 1, m.nn)), E=7e10, nu=0.3, rho=2700.0)
+    return o.assemble_K().tocsr()
+
+
+def _solve(m, marker, strong, leaf, pre, post, K=None):
+    """(iterations, state, gradient) of a cold solve; with the oracle's ``K``, also the backward error omega of one application of the
+    factor to four random vectors (tests/factor_check.py)."""
     from femo_alpha_amd.backend import ShellContext
     c = ShellContext(m)
     r = np.random.default_rng(1)
@@ -31,8 +43,15 @@ def _solve(m, marker, strong, leaf, pre, post):
     it, _ = c.solve_state(True)
     w = c.get_state()
     g, _, _ = c.total_gradient("compliance", "thickness")
+    if K is None:
+        c.close()
+        return it, w, g
+    from factor_check import omega
+    V = np.random.default_rng(0).uniform(-1, 1, (4, m.ndof))
+    om = omega(K, V.T, c.frontal_apply(V).T)
+    assert c.frontal_info()["pivots_repaired"] == 0
     c.close()
-    return it, w, g
+    return it, w, g, om
 
 
 @pytest.mark.parametrize("case,seed", [("plate", 11), ("wing_strong", 12)])
@@ -42,6 +61,7 @@ def test_random_schedules_give_the_same_solution(case, seed):
     else:
         m, marker, strong = wing_skin_mesh(32, 96, shuffle=True).renumbered()[0], (lambda x: np.less(x[1], 1e-9)), True
     it0, w0, g0 = _solve(m, marker, strong, 8, {}, dict(super_panel=0, fused_schur=0, lookahead=0))
+    K = _reference_K(m, marker, strong)
     rng = np.random.default_rng(seed)
     for _ in range(8):
         post = dict(trailing=int(rng.integers(0, 3)), left_min=int(rng.choice([1, 8, 64, 4096])), left_max=int(rng.choice([16, 2048, 100000])),
@@ -53,9 +73,10 @@ def test_random_schedules_give_the_same_solution(case, seed):
         leaf = int(rng.choice([4, 8, 12, 20]))
         what = f"leaf {leaf} {pre} {post}"
         try:
-            it, w, g = _solve(m, marker, strong, leaf, pre, post)
+            it, w, g, om = _solve(m, marker, strong, leaf, pre, post, K)
         except Exception as exc:                         # name the option set that broke the factorisation
             raise AssertionError(f"{what}: {exc}") from exc
+        assert om <= 1e-12, f"{what}: backward error of one application {om:.3e}"      # the factor itself, not what PCG makes of it
         assert it <= it0 + 1, what
         assert np.abs(w - w0).max() < 1e-9 * np.abs(w0).max(), what
         assert np.abs(g - g0).max() < 1e-8 * np.abs(g0).max(), what
