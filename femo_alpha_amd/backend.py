@@ -137,6 +137,31 @@ class ShellContext:
         v = self._vec(clt)
         self._chk(self.lib.femo_set_laminate(self._h, dptr(v), v.size))
 
+    def set_ply_table(self, table=None, npt=None):
+        """Recovery points of the ply failure outputs (femo_set_ply_table; laminate mode): ``table`` is the (nel, npt, 16) array of
+        ``laminate.ply_table`` in solver cell order (or flat, with ``npt`` given); ``None`` removes it.  The factor is kept."""
+        if table is None:
+            self._chk(self.lib.femo_set_ply_table(self._h, None, 0, 0))
+            return
+        a = np.asarray(table, dtype=np.float64)
+        if npt is None:
+            if a.ndim != 3:
+                raise ValueError("set_ply_table: a (nel, npt, 16) array, or npt")
+            npt = a.shape[1]
+        v = self._vec(a)
+        self._chk(self.lib.femo_set_ply_table(self._h, dptr(v), int(npt), v.size))
+
+    def set_ply_failure_params(self, rho=100.0):
+        """Exponent of the "ply_failure" aggregate (femo_set_ply_failure_params)."""
+        self._chk(self.lib.femo_set_ply_failure_params(self._h, float(rho)))
+
+    def ply_failure_field(self):
+        """(nel, npt): the largest failure index over the cell's quadrature points, per recovery point (femo_ply_failure_field)."""
+        n = int(self.lib.femo_field_size(self._h, b"ply_table"))
+        out = np.empty(max(n, 0) // 16)
+        self._chk(self.lib.femo_ply_failure_field(self._h, dptr(out), out.size))
+        return out.reshape(self.mesh.nel, -1)
+
     def set_quadrature(self, nquad):
         """The rule of the static forms (femo_set_quadrature): Gauss points per direction on quadrilaterals, the degree of the symmetric
         rule (4, 6, 9, 12) on triangles."""

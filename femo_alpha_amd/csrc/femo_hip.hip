@@ -9,6 +9,7 @@
 #include "stress_grad.h"
 #include "stress_history.h"
 #include "disp_history.h"
+#include "ply_failure.h"
 #include "csr_map.h"
 #include "hip_handles.h"
 
@@ -121,6 +122,15 @@ struct femo_ctx {
     DevBuf<double> clt;             // as the caller gave them (femo_get_field, the stale_factor snapshot)
     DevBuf<double> clt_sym;         // every block replaced by its symmetric part: what the kernels read (FieldsDev.clt)
     bool laminate = false;
+    // ply failure outputs (femo_set_ply_table; laminate mode only): npt recovery points of PLY_W doubles per cell
+    struct Ply {
+        int npt = 0;                // 0: no table
+        double rho = 100.0;         // femo_set_ply_failure_params
+        DevBuf<double> tab;         // cell-major, as the caller gave it (femo_get_field, the layout of d K / d table)
+        DevBuf<double> tabT;        // entry-major [16 p + k][nel]: what the kernels read
+        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
+        DevBuf<int> eslot;          // slot of every cell in ybuf (the inverse of eorder), built at first use
+    } ply;
     // dirichlet
     int nf = 0;
     struct Facets {
@@ -543,6 +553,8 @@ static FieldsDev fields_dev(const femo_ctx* c) {
     f.clt = c->laminate ? (const double*)c->clt_sym : nullptr;
     return f;
 }
+static MeshDev mesh_dev_all(const femo_ctx* c);
+static int ply_need_table(femo_ctx* c, const char* who);
 static FacetDev facet_dev(const femo_ctx* c) {
     FacetDev fd;
     fd.nf = c->nf; fd.cell = c->fa.cell; fd.ledge = c->fa.ledge; fd.unode = c->fa.unode; fd.vnode = c->fa.vnode;
@@ -601,6 +613,10 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_NU , DERIV_NU
 #define COMMA_LAM , true
 #define COMMA_FALSE_LAM , false, true
+#define COMMA_PF_VALUE , PF_VALUE
+#define COMMA_PF_FIELD , PF_FIELD
+#define COMMA_PF_DW , PF_DW
+#define COMMA_PF_DTABLE , PF_DTABLE
 
 static const int EB = 128;   // element kernels: threads per block (one element per thread)
 
@@ -2227,6 +2243,7 @@ static double* field_ptr(const femo_ctx* c, const char* name, int64_t* n) {
     if (s == "uhat") { *n = 3 * (int64_t)c->nn; return c->uhat; }
     if (s == "dirichlet" && c->gdir) { *n = c->ndof; return c->gdir; }
     if (s == "laminate" && c->laminate) { *n = (int64_t)LAM_W * c->nel; return c->clt; }
+    if (s == "ply_table" && c->ply.npt > 0) { *n = (int64_t)PLY_W * c->ply.npt * c->nel; return c->ply.tab; }
     *n = -1;
     return nullptr;
 }
@@ -2304,6 +2321,11 @@ int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
         if (!v) return fail(c, "null values");
         return femo_set_laminate(c, v, n);
     }
+    if (name && std::string(name) == "ply_table") {
+        if (c->ply.npt == 0) return fail(c, "field 'ply_table' exists once a table is set (femo_set_ply_table)");
+        if (!v) return fail(c, "null values");
+        return femo_set_ply_table(c, v, c->ply.npt, n);
+    }
     if (name && std::string(name) == "dirichlet" && !c->gdir) {
         HIPCHK(c, c->gdir.alloc((size_t)c->ndof));
         HIPCHK(c, hipMemset(c->gdir, 0, (size_t)c->ndof * sizeof(double)));
@@ -2380,6 +2402,7 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
             c->laminate = false;
             c->clt.reset();
             c->clt_sym.reset();
+            c->ply = femo_ctx::Ply();                          // the recovery points belong to the laminate
             operator_changed(c);
             ++c->opt_version;
         }
@@ -2445,6 +2468,66 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
     // which measures the laminate against its snapshot like the other fields)
     operator_changed(c, !entering);
     ++c->opt_version;
+    return 0;
+}
+
+int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!table && n == 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ply = femo_ctx::Ply();
+        return 0;
+    }
+    char buf[240];
+    if (!c->laminate) return fail(c, "ply table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
+    if (npt < 1 || npt > PLY_MAX) {
+        snprintf(buf, sizeof buf, "ply table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
+        return fail(c, buf);
+    }
+    const int64_t len = (int64_t)PLY_W * npt * c->nel;
+    if (!table || n != len) {
+        snprintf(buf, sizeof buf, "ply table: expected %d values per recovery point [G (3x3), z, F1, F2, F11, F22, F66, F12] x %d points x %d cells "
+                                  "= %lld, got %lld%s", PLY_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
+        return fail(c, buf);
+    }
+    const int64_t per = (int64_t)PLY_W * npt;
+    for (int64_t i = 0; i < len; ++i)
+        if (!std::isfinite(table[i])) {
+            const int64_t e = i / per, r = i - e * per;
+            snprintf(buf, sizeof buf, "ply table: value %d of recovery point %d of cell %lld is not finite", (int)(r % PLY_W), (int)(r / PLY_W), (long long)e);
+            return fail(c, buf);
+        }
+    const double rho = c->ply.rho;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->ply.tab.grow((size_t)len));
+    HIPCHK(c, c->ply.tabT.grow((size_t)len));
+    HIPCHK(c, hipMemcpy(c->ply.tab, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ply.tab, c->ply.tabT.get(), c->nel,
+                       (int)per);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ply.npt = npt; c->ply.rho = rho;
+    return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
+}
+
+int femo_set_ply_failure_params(femo_ctx* c, double rho) {
+    if (!(rho > 0.0) || !std::isfinite(rho)) return fail(c, "ply_failure: rho must be finite and > 0");
+    c->ply.rho = rho;
+    return 0;
+}
+
+int femo_ply_failure_field(femo_ctx* c, double* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ply_need_table(c, "femo_ply_failure_field")) return 2;
+    const int64_t len = (int64_t)c->nel * c->ply.npt;
+    if (!out || n != len) return fail(c, "femo_ply_failure_field: the field has nel * npt entries");
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)len));
+    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
+                c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const int*)nullptr, d.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2722,6 +2805,73 @@ static int pnorm_dev(femo_ctx* c, double out2[2]) {
     return 0;
 }
 
+// ---- ply failure aggregate and field (ply_failure.h)
+static int ply_need_table(femo_ctx* c, const char* who) {
+    if (c->ply.npt > 0) return 0;
+    return fail(c, std::string(who) + ": no ply table is set (femo_set_ply_table, laminate mode)");
+}
+
+// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
+static int ply_value_launch(femo_ctx* c) {
+    auto& pl = c->ply;
+    const int g = nblk(c->nel, PLY_BLOCK);
+    HIPCHK(c, pl.part.grow((size_t)3 * g));
+    HIPCHK(c, pl.res.grow(4));
+    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
+                (const double*)c->w, (const double*)nullptr, (const int*)nullptr, pl.part.get());
+    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)pl.part, stress_alpha_ref(c), pl.npt, pl.rho, pl.res.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like pnorm_stress's
+static int ply_value_dev(femo_ctx* c, double out4[4]) {
+    if (ply_need_table(c, "ply_failure")) return 2;
+    if (ply_value_launch(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->ply.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
+    if (!std::isfinite(out4[2])) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "ply_failure: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
+                                  "non-finite state or failure index", out4[0], out4[3], c->ply.rho);
+        return fail(c, msg);
+    }
+    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
+    return 0;
+}
+
+// d K / d w into out (ndof) or d K / d table into out (16 npt nel, cell-major); the shift stays on the device
+static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
+    auto& pl = c->ply;
+    if (ply_value_launch(c)) return 1;
+    const int g = nblk(c->nel, PLY_BLOCK);
+    if (!wrt_state) {
+        ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_DTABLE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
+                    (const double*)c->w, (const double*)pl.res, (const int*)nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    if (!pl.eslot) {
+        std::vector<int> eo((size_t)c->nel), inv((size_t)c->nel);
+        HIPCHK(c, hipMemcpy(eo.data(), c->eorder, eo.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int slot = 0; slot < c->nel; ++slot) inv[eo[slot]] = slot;
+        HIPCHK(c, pl.eslot.alloc(inv.size()));
+        HIPCHK(c, hipMemcpy(pl.eslot, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_DW, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
+                (const double*)c->w, (const double*)pl.res, (const int*)pl.eslot, c->ybuf.get());
+    const int nthreads = c->nP2 + c->nghost;
+#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
+                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
+    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
+    else if (c->quad) GATHER_SUM(9, 4);
+    else GATHER_SUM(6, 3);
+#undef GATHER_SUM
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 int femo_functional(femo_ctx* c, const char* name, double* value) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string s(name ? name : "");
@@ -2751,6 +2901,12 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         double v[2];
         if (pnorm_dev(c, v)) return 1;
         *value = v[0] / stress_alpha_ref(c);
+        return 0;
+    }
+    if (s == "ply_failure") {
+        double v[4];
+        if (int rc = ply_value_dev(c, v)) return rc;
+        *value = v[2];
         return 0;
     }
     if (s.rfind("sum_stress_", 0) == 0) {         // over the selected sub-domain (rm_shell_pde.py:130-150)
@@ -2813,6 +2969,13 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
     const MeshDev m = mesh_dev(c);
     const FieldsDev f = fields_dev(c);
     const int g = nblk(c->nel, EB);
+    if (fn == "ply_failure") {
+        if (ply_need_table(c, "ply_failure")) return 2;
+        if (wrt == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
+        if (wrt == "disp_solid" || wrt == "ply_table") return ply_grad_dev(c, wrt == "disp_solid", out);
+        HIPCHK(c, hipGetLastError());
+        return 0;                                             // laminate, thickness, E, nu, density, F_solid: no explicit dependence
+    }
     if (wrt == "uhat") {
         if (fn == "regularization") return 0;                 // integrates over the reference configuration only
         const int mode = fn == "compliance" ? 1 : fn == "mass" ? 2 : fn == "elastic_energy" ? 3 : fn == "pnorm_stress" ? 4 : -1;
@@ -2869,7 +3032,7 @@ static int dRdarg_T_dev(femo_ctx* c, const std::string& arg, const double* lam, 
     else if (arg == "E") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_E, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "nu") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_NU, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "F_solid") ELEM_LAUNCH(c, k_dRdf_T, NOEXTRA, g, EB, m, f, c->tab, lam, -scale, out);
-    else if (arg == "density") { /* R does not depend on density */ }
+    else if (arg == "density" || arg == "ply_table") { /* R depends on neither */ }
     else if (arg == "uhat") { if (shape_gradient_dev(c, 0, c->w, lam, scale, out)) return 1; }
     else return fail(c, "(dR/d" + arg + ")^T is not implemented in this build");
     HIPCHK(c, hipGetLastError());
@@ -2902,6 +3065,10 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
                         double* relres) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fn(functional ? functional : ""), a(arg ? arg : "");
+    if (fn == "ply_failure") {
+        if (ply_need_table(c, "ply_failure")) return 2;
+        if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
+    }
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     int rc = dfunctional_dev(c, fn, "disp_solid", c->b, c->ndof);          // dJ/dw
@@ -3005,6 +3172,11 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
     const int keep_sel = c->csel;
     for (int i = 0; i < nfun; ++i)
         if (subdomains && (subdomains[i] < -1 || subdomains[i] >= c->ntags)) return fail(c, "unknown sub-domain");
+    for (int i = 0; i < nfun; ++i)
+        if (functionals[i] && std::string(functionals[i]) == "ply_failure") {
+            if (ply_need_table(c, "ply_failure")) return 2;
+            if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
+        }
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;

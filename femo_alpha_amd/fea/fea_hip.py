@@ -21,13 +21,14 @@ from ..mesh_io import readFEAMesh, reconstructFEAMesh            # noqa: F401  (
 
 class FunctionSpace:
     """kind: 'W' (CG2xCG1 state), 'VT' (thickness-like scalars), 'VF' (pressure), 'VU' (mesh motion), 'VL' (the laminate: DG0,
-    32 values per cell, femo_set_laminate)."""
+    32 values per cell, femo_set_laminate), 'VP' (the ply table: DG0, ``width`` = 16 npt values per cell, femo_set_ply_table)."""
 
-    def __init__(self, ctx: ShellContext, kind: str):
+    def __init__(self, ctx: ShellContext, kind: str, width=None):
         self.ctx, self.kind = ctx, kind
         m = ctx.mesh
         self.dim = {"W": m.ndof, "VT": m.nel if ctx.element_wise_material else m.nn,
-                    "VF": 3 * (m.nel if ctx.elementwise_pressure else m.nn), "VU": 3 * m.nn, "VL": 32 * m.nel}[kind]
+                    "VF": 3 * (m.nel if ctx.elementwise_pressure else m.nn), "VU": 3 * m.nn, "VL": 32 * m.nel,
+                    "VP": (width or 0) * m.nel}[kind]
 
 
 class Function:
@@ -108,7 +109,7 @@ class _SubFunction:
 
 
 class Form:
-    """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume'.
+    """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume', 'ply_failure'.
     ``subdomain`` restricts the stress aggregate to one tagged set of cells (the reference's ``dxx(i)`` measure)."""
 
     def __init__(self, ctx, name, subdomain=-1, stress_params=None):

@@ -23,6 +23,7 @@ import numpy as np
 
 K_SHEAR = 0.833          # linear_shell_model.py:146
 LAM_W = 32               # [A (9), B (9), D (9), A_s (4), c_drill] per cell
+PLY_W = 16               # [G (9), z, F1, F2, F11, F22, F66, F12] per recovery point (femo_set_ply_table)
 
 
 def _t_eps(theta_deg):
@@ -85,14 +86,61 @@ def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacob
     if not jacobian:
         return A, B, D, As
     nply = t.shape[1]
-    # dz_i / dt_j = -1/2 + [j < i]
-    dz = -0.5 + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)     # (nply + 1, nply) [i, j]
+    dz = _dz_interfaces(nply)                                                                     # (nply + 1, nply) [i, j]
     dz0, dz1 = dz[:-1], dz[1:]                                                                    # (nply, nply) [k, j]
     dA = np.einsum("kj,ekab->ejab", dz1 - dz0, Qb)
     dB = np.einsum("ek,kj,ekab->ejab", z0, dz0, Qb) - np.einsum("ek,kj,ekab->ejab", z1, dz1, Qb)
     dD = np.einsum("ek,kj,ekab->ejab", z1 ** 2, dz1, Qb) - np.einsum("ek,kj,ekab->ejab", z0 ** 2, dz0, Qb)
     dAs = k_shear * Qs
     return (A, B, D, As), (dA, dB, dD, dAs)
+
+
+def _dz_interfaces(nply):
+    """dz_i / dt_j = -1/2 + [j < i] of the nply + 1 ply interfaces z_i = sum_{j < i} t_j - H / 2, (nply + 1, nply)."""
+    return -0.5 + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)
+
+
+def tsai_wu(Xt, Xc, Yt, Yc, S, f12=-0.5):
+    """The six coefficients (F1, F2, F11, F22, F66, F12) of the Tsai-Wu failure index
+    FI = F1 s1 + F2 s2 + F11 s1^2 + F22 s2^2 + F66 t12^2 + 2 F12 s1 s2 from the ply strengths (all positive: tension / compression
+    along and across the fibres, in-plane shear), F12 = f12 sqrt(F11 F22).  Arguments broadcast; the coefficients are the last axis.
+    Xt = Xc = Yt = Yc = X, S = X / sqrt(3), f12 = -1/2 gives (von Mises / X)^2."""
+    Xt, Xc, Yt, Yc, S, f12 = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (Xt, Xc, Yt, Yc, S, f12)))
+    F11, F22 = 1.0 / (Xt * Xc), 1.0 / (Yt * Yc)
+    return np.stack([1.0 / Xt - 1.0 / Xc, 1.0 / Yt - 1.0 / Yc, F11, F22, 1.0 / S ** 2, f12 * np.sqrt(F11 * F22)], axis=-1)
+
+
+def ply_table(E1, E2, G12, nu12, t, theta, strengths, surfaces=("bot", "top"), jacobian=False):
+    """Recovery points of the ply failure outputs (femo_set_ply_table): (nel, npt, 16) with npt = nply * len(surfaces), per point
+    [G (3x3 row-major), z, F1, F2, F11, F22, F66, F12].  Ply arguments as for ``clt_from_plies``: (nply,) or (nel, nply), plies bottom
+    to top, z from -H/2; ``strengths``: the coefficients of ``tsai_wu``, (6,), (nply, 6) or (nel, nply, 6).  Point order: ply by ply
+    from the bottom, inside a ply the ``surfaces`` as listed ("bot", "mid", "top" of the ply).  G = Q T(theta) maps the frame strains
+    eps - z kappa to the ply-axis stresses (Q: the reduced stiffness in ply axes, T: ``_t_eps``).
+    ``jacobian=True`` also returns dz (npt, nply) = d z_p / d t_j, the same for every cell: z is the only entry of the table that
+    depends on the ply thicknesses."""
+    args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, t, theta)]
+    E1, E2, G12, nu12, t, theta = np.broadcast_arrays(*args)
+    nel, nply = t.shape
+    Q, _ = ply_stiffness(E1, E2, G12, nu12, G12, G12, np.zeros_like(theta))         # theta = 0: Q in ply axes
+    G = np.einsum("ekil,eklj->ekij", Q, _t_eps(theta))
+    F = np.broadcast_to(np.asarray(strengths, dtype=np.float64), (nel, nply, 6))
+    H = t.sum(axis=1, keepdims=True)
+    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H    # (nel, nply + 1) ply interfaces
+    dzi = _dz_interfaces(nply)
+    pick = {"bot": (1.0, 0.0), "mid": (0.5, 0.5), "top": (0.0, 1.0)}
+    ns = len(surfaces)
+    out = np.empty((nel, nply, ns, PLY_W))
+    dz = np.empty((nply, ns, nply))
+    for s, name in enumerate(surfaces):
+        if name not in pick:
+            raise ValueError(f"surfaces: 'bot', 'mid' or 'top', got {name!r}")
+        a, b = pick[name]
+        out[:, :, s, 0:9] = G.reshape(nel, nply, 9)
+        out[:, :, s, 9] = a * z[:, :-1] + b * z[:, 1:]
+        out[:, :, s, 10:16] = F
+        dz[:, s, :] = a * dzi[:-1] + b * dzi[1:]
+    out = out.reshape(nel, nply * ns, PLY_W)
+    return (out, dz.reshape(nply * ns, nply)) if jacobian else out
 
 
 def offset(clt, o):

@@ -67,7 +67,7 @@ def createCustomMeasure(mesh: ShellMesh, dim, SubdomainFunc, measure: str, tag: 
 class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
-                 device=0, renumber=False, nquad=None, laminate=False):
+                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -101,6 +101,11 @@ class RMShellModel:
         # laminate=True: the composite law with a DG0 "laminate" input of (nel, 32) values per cell in caller order
         # ([A, B, D, A_s, c_drill], femo_alpha_amd.laminate.pack), an argument of disp_solid and elastic_energy
         self.laminate = bool(laminate)
+        # ply_failure=npt (with laminate=True): a DG0 "ply_table" input of (nel, npt, 16) values in caller cell order
+        # (femo_alpha_amd.laminate.ply_table) and the output "ply_failure", the KS aggregate of the ply failure index
+        self.ply_failure = None if ply_failure is None else int(ply_failure)
+        if self.ply_failure is not None and not self.laminate:
+            raise ValueError("ply_failure needs laminate=True")
         # n x n Gauss points per quadrilateral for the static forms (2..5).  The reference leaves the degree to UFL's
         # estimate, which on quadrilaterals comes out near 47 (scripts/ufl_degree_estimate.py): exact integration.  Default:
         # what the mesh asks for -- 4 on affine cells (exact there), 5 as soon as one cell is warped (within 1e-9 of the
@@ -145,7 +150,7 @@ class RMShellModel:
         mesh = self.mesh
         shell_pde = self.shell_pde = RMShellPDE(mesh, element_wise_material=self.element_wise_material,
                                                 elementwise_pressure=self.elementwise_pressure, device=self.device,
-                                                nquad=self._nquad_arg, laminate=self.laminate)
+                                                nquad=self._nquad_arg, laminate=self.laminate, ply_failure=self.ply_failure)
         fea = FEA(mesh)
         fea.PDE_SOLVER = "Newton"
         fea.REPORT = False
@@ -185,6 +190,10 @@ class RMShellModel:
         fea.add_output(name="mass", form=mass_form, arguments=["thickness", "density", "uhat"])
         fea.add_output(name="elastic_energy", form=elastic_energy_form, arguments=["thickness", "disp_solid", "E", "uhat"] + lam_args)
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
+        if self.ply_failure is not None:
+            ply = Function(shell_pde.VP).bind("ply_table")
+            fea.add_input("ply_table", ply, init_val=shell_pde.ply_table_init)
+            fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, ply, rho=self.rho), arguments=["disp_solid", "ply_table"])
         if self.mesh_tags is not None:
             self.set_up_subdomains(self.mesh_tags)
             for tag, i in self.association_table.items():
@@ -196,11 +205,15 @@ class RMShellModel:
                              function_space=("DG", 1), record=False, vtk=True)
         self.fea = fea
 
-    def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None):
+    def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None,
+                 ply_table=None):
         """laminate: (nel, 32) per cell in caller order -- required with laminate=True, refused otherwise.  thickness, E, nu and density
-        stay inputs in laminate mode (mass, regularisation, stress outputs)."""
+        stay inputs in laminate mode (mass, regularisation, stress outputs).  ply_table: (nel, npt, 16) per cell in caller order --
+        required with ply_failure=npt, refused otherwise."""
         if self.laminate != (laminate is not None):
             raise ValueError("a laminate is required with laminate=True and refused without it")
+        if (self.ply_failure is not None) != (ply_table is not None):
+            raise ValueError("a ply_table is required with ply_failure=npt and refused without it")
         shell_inputs = csdl.VariableGroup()
         mesh = self.mesh
         # caller order == solver order here; the gathers are kept so that a renumbered mesh object
@@ -232,6 +245,9 @@ class RMShellModel:
         if self.laminate:
             shell_inputs.laminate = laminate[self.cell_of_new].reshape((-1,))      # caller cell order -> solver order
             shell_inputs.laminate.add_name("laminate")
+        if self.ply_failure is not None:
+            shell_inputs.ply_table = ply_table[self.cell_of_new].reshape((-1,))    # caller cell order -> solver order
+            shell_inputs.ply_table.add_name("ply_table")
 
         solid_model = FEAModel(fea=[self.fea], fea_name="rm_shell")
         shell_outputs = solid_model.evaluate(shell_inputs, debug_mode=debug_mode)

@@ -23,7 +23,7 @@ class FacetSet:
 
 class RMShellPDE:
     def __init__(self, mesh, element_wise_material=False, elementwise_pressure=False, nquad=None, device=0, solver="direct",
-                 element_type=None, laminate=False):
+                 element_type=None, laminate=False, ply_failure=None):
         # element_type: 'CG2CG1' (what the reference's RMShellPDE hard-codes, rm_shell_pde.py:27) or 'CG1CG1' (the other quadrilateral /
         # triangle choice of ShellElement.setUpFunctionSpace, linear_shell_model.py:74-79); None: the element the mesh object carries
         if element_type is not None and element_type != mesh.element:
@@ -53,6 +53,16 @@ class RMShellPDE:
             self.VL = FunctionSpace(self.ctx, "VL")
             self.laminate_init = isotropic(np.full(mesh.nel, 1e-3), 1.0, 0.3).ravel()
             self.ctx.set_laminate(self.laminate_init)
+        # ply_failure=npt (laminate mode): the ply failure aggregate over npt recovery points per cell, a DG0 space of 16 npt values per
+        # cell (femo_alpha_amd.laminate.ply_table).  The placeholder table is all zeros (FI = 0) until the model's input replaces it.
+        self.ply_npt = None if ply_failure is None else int(ply_failure)
+        self.VP = None
+        if self.ply_npt is not None:
+            if not self.laminate:
+                raise ValueError("ply_failure needs laminate=True")
+            self.VP = FunctionSpace(self.ctx, "VP", width=16 * self.ply_npt)
+            self.ply_table_init = np.zeros(self.VP.dim)
+            self.ctx.set_ply_table(self.ply_table_init, self.ply_npt)
 
     # ------------------------------------------------------------------ residual
     def pdeRes(self, h, w, uhat, f, E, nu, penalty=False, dss=None, dSS=None, g=None):
@@ -113,6 +123,12 @@ class RMShellPDE:
 
     def elastic_energy(self, w, uhat, h, E):
         return Form(self.ctx, "elastic_energy")
+
+    def ply_failure(self, w, uhat, ply_table, dx=None, rho=100.0):
+        """KS aggregate of the ply failure index over the recovery points of ``ply_table`` (include/femo_hip.h, femo_set_ply_table);
+        ``dx``: None for the whole mesh, or the index of a tagged sub-domain."""
+        self.ctx.set_ply_failure_params(rho)
+        return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
 
     def pnorm_stress(self, w, uhat, h, E, nu, dx=None, m=1e-6, rho=100, alpha=None, regularization=False):
         """1/alpha int (m vm_top)^rho J dx with the degree-4 measure (rm_shell_pde.py:112-128); alpha is the
