@@ -600,6 +600,38 @@ class ShellContext:
         self._chk(self.lib.femo_dRdarg_T(self._h, arg.encode(), dptr(lam), dptr(out), out.size))
         return out
 
+    def dRdarg(self, arg, V):
+        """Forward mode: (dR/d arg) v at the stored state for one direction ``V`` (1-D) or several (rows of a 2-D array; the result
+        has the same number of rows of ndof entries) -- femo_residual_jvp.  Rows of strong Dirichlet DOFs are zero."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        one = V.ndim == 1
+        V = V.reshape(1, -1) if one else V
+        out = np.empty((V.shape[0], self.ndof))
+        self._chk(self.lib.femo_residual_jvp(self._h, arg.encode(), V.shape[0], dptr(V), V.shape[1], dptr(out)))
+        return out[0] if one else out
+
+    def total_jvp(self, arg, V, functionals=(), subdomains=None, want_states=True):
+        """Forward chain (femo_total_jvp): the tangent states dW[k] = -K^-1 (dR/d arg) V[k], their solves grouped four to a pair of
+        sweeps, and dJ[i, k] = d J_i / d arg . V[k] (total) for the named functionals.  A 1-D ``V`` is one direction (dW and the
+        columns of dJ lose that axis).  Returns (dW or None, dJ, iterations, relative residuals)."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        one = V.ndim == 1
+        V = V.reshape(1, -1) if one else V
+        nd = V.shape[0]
+        names = [f.encode() for f in functionals]
+        nf = len(names)
+        arr = (C.c_char_p * max(nf, 1))(*names)
+        dW = np.empty((nd, self.ndof)) if want_states else None
+        dJ = np.zeros((nf, nd))
+        it = np.zeros(nd, dtype=np.int32); rr = np.zeros(nd)
+        sub = None if subdomains is None else np.ascontiguousarray(np.asarray(subdomains, dtype=np.int32))
+        self._chk(self.lib.femo_total_jvp(self._h, arg.encode(), nd, dptr(V), V.shape[1], nf, arr if nf else None,
+                                          None if sub is None else iptr(sub), None if dW is None else dptr(dW),
+                                          dptr(dJ) if nf else None, iptr(it), dptr(rr)))
+        if one:
+            return (None if dW is None else dW[0]), dJ[:, 0], it, rr
+        return dW, dJ, it, rr
+
     def total_gradient(self, functional, arg):
         out = np.empty(self.field_size(arg))
         it = C.c_int32(); rr = C.c_double()

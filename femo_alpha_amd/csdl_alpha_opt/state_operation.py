@@ -6,12 +6,13 @@ stand-in -- drives it unchanged:
 
   solve_residual_equations      forward solve            (reference :86-131)
   apply_inverse_jacobian        K^-1 / K^-T solve        (:188-220)
-  compute_jacvec_product        (dR/d arg)^T lambda      (:134-186)
+  compute_jacvec_product        (dR/d arg)^T lambda in reverse mode, (dR/d arg) v in forward mode      (:134-186)
 
 Differences that are deliberate: the Jacobian-side data are
 matrix-free and always consistent with the current inputs and state (the reference assembles
-them at ``opt_iter == 1`` only, quirk Q2); forward-mode products with dR/d(input) raise
-``NotImplementedError`` where the reference raises ``KeyError`` (quirk Q1).
+them at ``opt_iter == 1`` only, quirk Q2); forward-mode products with dR/d(input) work for every
+registered input (``ShellContext.dRdarg``), where the reference intends them (:159-171) but raises
+``KeyError`` through a wrong dictionary key (quirk Q1).
 """
 from .. import csdl
 from ..fea.fea_hip import (FEA, assembleMatrix, assembleSystem, computeMatVecProductBwd, computeMatVecProductFwd,

@@ -5,6 +5,7 @@
 #include "frontal.h"
 #include "sweeps_multi.h"
 #include "shape_sens.h"
+#include "residual_jvp.h"
 #include "stress.h"
 #include "stress_grad.h"
 #include "stress_history.h"
@@ -140,6 +141,14 @@ struct femo_ctx {
     } fa;
     double beta = 1e15;
     bool penalty_dirty = true;
+    // forward mode (femo_residual_jvp / femo_total_jvp): the state as the residual's operator sees it, and the penalty facets coloured
+    // so that the facets of one launch share no node (built at first use, dropped with the facet list)
+    struct Jvp {
+        DevBuf<double> wm, wg, scal;
+        DevBuf<int> flist;
+        std::vector<int> off;                 // facets of colour k: flist[off[k] .. off[k + 1])
+        bool coloured = false;
+    } jv;
     DevBuf<double> gdir;          // prescribed values g of the penalty term beta/h_E |..| (w - g).v (linear_shell_model.py:323-333); null = zero
     bool has_g = false;
     DevBuf<unsigned char> mask;
@@ -2258,6 +2267,7 @@ int femo_set_penalty_facets(femo_ctx* c, int32_t nf, const int32_t* cl, double b
     HIPCHK(c, hipSetDevice(c->device));
     if (nf < 0 || (nf > 0 && !cl)) return fail(c, "bad facet list");
     c->fa = femo_ctx::Facets();
+    c->jv.coloured = false;
     c->nf = 0;
     c->beta = beta;
     c->penalty_dirty = true;
@@ -3201,6 +3211,205 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
         if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
     }
     return rc;
+}
+
+// ---- forward mode of the static residual (residual_jvp.h)
+static int jvp_colour_facets(femo_ctx* c) {
+    auto& jv = c->jv;
+    if (jv.coloured) return 0;
+    const int nf = c->nf;
+    std::vector<int> un(3 * (size_t)nf), rn((c->cr ? 3 : 2) * (size_t)nf);
+    HIPCHK(c, hipMemcpy(un.data(), c->fa.unode, un.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rn.data(), c->cr ? c->fa.rnode : c->fa.vnode, rn.size() * sizeof(int), hipMemcpyDeviceToHost));
+    // greedy colouring: a facet takes the lowest colour none of its displacement or rotation nodes has seen yet
+    const int nr = c->cr ? 3 : 2;
+    std::vector<unsigned> used_u((size_t)c->nP2, 0u), used_r((size_t)c->nrot, 0u);
+    std::vector<int> colour(nf, 0);
+    int ncol = 0;
+    for (int i = 0; i < nf; ++i) {
+        unsigned busy = 0;
+        for (int a = 0; a < 3; ++a) busy |= used_u[un[3 * i + a]];
+        for (int a = 0; a < nr; ++a) busy |= used_r[rn[nr * i + a]];
+        int k = 0;
+        while (k < 31 && (busy >> k & 1u)) ++k;
+        if (k == 31) return fail(c, "penalty facets: more than 31 facets meet in one node");
+        colour[i] = k;
+        ncol = std::max(ncol, k + 1);
+        for (int a = 0; a < 3; ++a) used_u[un[3 * i + a]] |= 1u << k;
+        for (int a = 0; a < nr; ++a) used_r[rn[nr * i + a]] |= 1u << k;
+    }
+    jv.off.assign(ncol + 1, 0);
+    for (int i = 0; i < nf; ++i) ++jv.off[colour[i] + 1];
+    for (int k = 0; k < ncol; ++k) jv.off[k + 1] += jv.off[k];
+    std::vector<int> at(jv.off.begin(), jv.off.end() - 1), list(std::max(nf, 1));
+    for (int i = 0; i < nf; ++i) list[at[colour[i]]++] = i;
+    HIPCHK(c, jv.flist.alloc(list.size()));
+    HIPCHK(c, hipMemcpy(jv.flist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+    jv.coloured = true;
+    return 0;
+}
+
+// the state as the residual's operator sees it (strong rows zero) in jv.wm; with penalty facets, w - g in jv.wg
+static int jvp_prepare(femo_ctx* c) {
+    const int64_t n = c->ndof;
+    const int vg = vec_grid(n);
+    HIPCHK(c, c->jv.wm.grow((size_t)n));
+    HIPCHK(c, hipMemcpyAsync(c->jv.wm, c->w, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (c->has_mask) hipLaunchKernelGGL(k_mask_zero, dim3(vg), dim3(256), 0, c->stream, c->jv.wm.get(), c->mask, n);
+    if (c->nf > 0 && c->has_g) {
+        HIPCHK(c, c->jv.wg.grow((size_t)n));
+        hipLaunchKernelGGL(k_lincomb3, dim3(vg), dim3(256), 0, c->stream, c->jv.wg.get(), 1.0, (const double*)c->jv.wm, -1.0, (const double*)c->gdir,
+                           0.0, (const double*)nullptr, n);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+static int jvp_check_arg(femo_ctx* c, const std::string& arg, int64_t n) {
+    int64_t len;
+    if (!field_ptr(c, arg.c_str(), &len)) return fail(c, "unknown argument '" + arg + "'");
+    if (len != n) return fail(c, "buffer has the wrong length for '" + arg + "'");
+    if (arg == "dirichlet") return fail(c, "(dR/d" + arg + ") is not implemented in this build");
+    return 0;
+}
+
+// out (ndof) = (dR/d arg) v on device vectors; jvp_prepare and jvp_check_arg have run
+static int residual_jvp_dev(femo_ctx* c, const std::string& arg, const double* v, double* out) {
+    const int64_t n = c->ndof;
+    const int vg = vec_grid(n);
+    const bool lam3 = c->laminate && (arg == "thickness" || arg == "E" || arg == "nu");      // the laminate replaces them inside R
+    if (lam3 || arg == "density" || arg == "ply_table") {
+        hipLaunchKernelGGL(k_fill, dim3(vg), dim3(256), 0, c->stream, out, 0.0, n);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    const MeshDev m = mesh_dev(c);
+    const FieldsDev f = fields_dev(c);
+    const int nb = ((nblk(c->nel, JVP_EPB) + 7) / 8) * 8;                  // multiple of 8 for the XCD-aware block order
+    const double* x = c->jv.wm;
+#define COMMA_JVP_H , JVP_H
+#define COMMA_JVP_E , JVP_E
+#define COMMA_JVP_NU , JVP_NU
+#define COMMA_JVP_LAM , JVP_LAM
+#define COMMA_JVP_LOAD , JVP_LOAD
+#define JVP_SHAPE_LAUNCH(NPC_, NVC_, QUAD_)                                                                                          \
+    do {                                                                                                                             \
+        if (c->laminate) hipLaunchKernelGGL((k_residual_jvp<NPC_, NVC_, QUAD_, true, JVP_SHAPE_LAM>), dim3(nb), dim3(256), 0, c->stream, m, f, \
+                                            c->tab, c->eorder, x, v, c->ybuf.get());                                                 \
+        else hipLaunchKernelGGL((k_residual_jvp<NPC_, NVC_, QUAD_, true, JVP_SHAPE>), dim3(nb), dim3(256), 0, c->stream, m, f, c->tab, \
+                                c->eorder, x, v, c->ybuf.get());                                                                     \
+    } while (0)
+    if (arg == "thickness") ELEM_LAUNCH(c, k_residual_jvp, COMMA_JVP_H, nb, 256, m, f, c->tab, c->eorder, x, v, c->ybuf.get());
+    else if (arg == "E") ELEM_LAUNCH(c, k_residual_jvp, COMMA_JVP_E, nb, 256, m, f, c->tab, c->eorder, x, v, c->ybuf.get());
+    else if (arg == "nu") ELEM_LAUNCH(c, k_residual_jvp, COMMA_JVP_NU, nb, 256, m, f, c->tab, c->eorder, x, v, c->ybuf.get());
+    else if (arg == "laminate") ELEM_LAUNCH(c, k_residual_jvp, COMMA_JVP_LAM, nb, 256, m, f, c->tab, c->eorder, x, v, c->ybuf.get());
+    else if (arg == "F_solid") ELEM_LAUNCH(c, k_residual_jvp, COMMA_JVP_LOAD, nb, 256, m, f, c->tab, c->eorder, x, v, c->ybuf.get());
+    else if (arg == "uhat") {
+        if (c->cg1) { if (c->quad) JVP_SHAPE_LAUNCH(4, 4, true); else JVP_SHAPE_LAUNCH(3, 3, false); }
+        else        { if (c->quad) JVP_SHAPE_LAUNCH(9, 4, true); else JVP_SHAPE_LAUNCH(6, 3, false); }
+    } else return fail(c, "(dR/d" + arg + ") is not implemented in this build");
+#undef JVP_SHAPE_LAUNCH
+    const int nthreads = c->nP2 + c->nghost;
+#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
+                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
+    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
+    else if (c->quad) GATHER_SUM(9, 4);
+    else GATHER_SUM(6, 3);
+#undef GATHER_SUM
+    if (arg == "uhat" && c->nf > 0) {
+        if (jvp_colour_facets(c)) return 2;
+        const double* xp = c->has_g ? c->jv.wg : c->jv.wm;
+        for (size_t k = 0; k + 1 < c->jv.off.size(); ++k) {
+            const int n0 = c->jv.off[k], nl = c->jv.off[k + 1] - n0;
+            if (nl == 0) continue;
+#define JVP_PENALTY(NVC_, QUAD_, CG1_)                                                                                                  \
+    hipLaunchKernelGGL((k_jvp_penalty<NVC_, QUAD_, CG1_>), dim3(nblk(nl, 64)), dim3(64), 0, c->stream, m, f, facet_dev(c), c->beta,       \
+                       (const int*)c->jv.flist + n0, nl, xp, v, out)
+            if (c->cg1) { if (c->quad) JVP_PENALTY(4, true, true); else JVP_PENALTY(3, false, true); }
+            else        { if (c->quad) JVP_PENALTY(4, true, false); else JVP_PENALTY(3, false, false); }
+#undef JVP_PENALTY
+        }
+    }
+    if (c->has_mask) hipLaunchKernelGGL(k_mask_zero, dim3(vg), dim3(256), 0, c->stream, out, c->mask, n);      // R = w - g on strong rows
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int femo_residual_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, int64_t n, double* out) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ndir < 1 || !V || !out) return fail(c, "femo_residual_jvp: ndir >= 1 directions, one after the other");
+    const std::string a(arg ? arg : "");
+    if (int rc = jvp_check_arg(c, a, n)) return rc;
+    const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
+    HIPCHK(c, c->mr_io.grow((size_t)ndir * (nv + nd)));
+    double* Vd = c->mr_io;
+    double* Od = Vd + (size_t)ndir * nv;
+    HIPCHK(c, hipMemcpy(Vd, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (jvp_prepare(c)) return 1;
+    for (int k = 0; k < ndir; ++k)
+        if (int rc = residual_jvp_dev(c, a, Vd + (size_t)k * n, Od + (size_t)k * nd)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, Od, (size_t)ndir * nd * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The forward chain: one tangent solve per direction gives the derivative of every output at once.  The tangent right-hand sides and
+// results live in mr_io (never in the solver's own vectors, which a running factorisation may be sweeping ahead on).
+int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, int64_t n, int32_t nfun, const char* const* functionals,
+                   const int32_t* subdomains, double* dW, double* dJ, int32_t* iters, double* relres) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (ndir < 1 || !V) return fail(c, "femo_total_jvp: ndir >= 1 directions, one after the other");
+    if (nfun < 0 || (nfun > 0 && (!functionals || !dJ))) return fail(c, "femo_total_jvp: nfun >= 0 functional names and room for nfun x ndir values");
+    const std::string a(arg ? arg : "");
+    if (int rc = jvp_check_arg(c, a, n)) return rc;
+    for (int i = 0; i < nfun; ++i)
+        if (subdomains && (subdomains[i] < -1 || subdomains[i] >= c->ntags)) return fail(c, "unknown sub-domain");
+    for (int i = 0; i < nfun; ++i)
+        if (functionals[i] && std::string(functionals[i]) == "ply_failure") {
+            if (ply_need_table(c, "ply_failure")) return 2;
+            if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
+        }
+    const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
+    const int keep_sel = c->csel;
+    // V | B (right-hand sides, overwritten by the solves) | X (tangent states) | dJ/dw | dJ/d arg
+    HIPCHK(c, c->mr_io.grow((size_t)ndir * (nv + 2 * nd) + nd + nv));
+    HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
+    double* Vd = c->mr_io;
+    double *Bd = Vd + (size_t)ndir * nv, *Xd = Bd + (size_t)ndir * nd, *Gw = Xd + (size_t)ndir * nd, *Ga = Gw + nd;
+    std::vector<double*> B(ndir), X(ndir);
+    for (int k = 0; k < ndir; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    HIPCHK(c, hipMemcpy(Vd, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (jvp_prepare(c)) return 1;
+    int rc = 0;
+    for (int k = 0; k < ndir && !rc; ++k) {
+        rc = residual_jvp_dev(c, a, Vd + (size_t)k * n, B[k]);                                          // (dR/d arg) V[k]
+        if (!rc) hipLaunchKernelGGL(k_negate, dim3(vec_grid(nd)), dim3(256), 0, c->stream, B[k], (int64_t)nd);
+    }
+    if (!rc) rc = solve_multi_dev(c, ndir, B.data(), X.data(), iters, relres);                          // dW[k] = -K^-1 (dR/d arg) V[k]
+    const size_t ns = (size_t)nfun * ndir;
+    if (!rc && nfun > 0 && hipMemsetAsync(c->jv.scal, 0, 2 * ns * sizeof(double), c->stream) != hipSuccess) rc = fail(c, "hipMemsetAsync failed");
+    for (int i = 0; i < nfun && !rc; ++i) {
+        c->csel = subdomains ? subdomains[i] : -1;
+        const std::string fn(functionals[i] ? functionals[i] : "");
+        rc = dfunctional_dev(c, fn, "disp_solid", Gw, c->ndof);                                         // dJ_i/dw
+        if (!rc) rc = dfunctional_dev(c, fn, a, Ga, n);                                                 // dJ_i/d arg
+        for (int k = 0; k < ndir && !rc; ++k) {
+            double* s = c->jv.scal + 2 * ((size_t)i * ndir + k);
+            hipLaunchKernelGGL(k_dot, dim3(red_grid(nd)), dim3(256), 0, c->stream, (const double*)Gw, (const double*)X[k], (int64_t)nd, s);
+            hipLaunchKernelGGL(k_dot, dim3(red_grid(n)), dim3(256), 0, c->stream, (const double*)Ga, (const double*)(Vd + (size_t)k * n), n, s + 1);
+        }
+    }
+    c->csel = keep_sel;
+    if (rc) return rc;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && dW) e = hipMemcpy(dW, Xd, (size_t)ndir * nd * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nfun > 0) {
+        std::vector<double> s(2 * ns);
+        e = hipMemcpy(s.data(), c->jv.scal, s.size() * sizeof(double), hipMemcpyDeviceToHost);
+        for (size_t j = 0; j < ns; ++j) dJ[j] = s[2 * j] + s[2 * j + 1];
+    }
+    if (e != hipSuccess) { c->err = hipGetErrorString(e); return 1; }
+    return 0;
 }
 
 int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int32_t* nf, const int32_t* npiv,

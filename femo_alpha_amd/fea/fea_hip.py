@@ -162,10 +162,9 @@ class JacobianOperator:
         self.shape = (self.ctx.ndof, partial.wrt.function_space.dim)
 
     def mult(self, x):
-        if self.wrt != "state":
-            raise NotImplementedError("forward products with dR/d(input) are not provided "
-                                      "(the reference's fwd mode raises KeyError, state_operation.py:167-171)")
-        return self.ctx.apply_K(x)
+        if self.wrt == "state":
+            return self.ctx.apply_K(x)
+        return self.ctx.dRdarg(self.wrt, x)                # forward mode: (dR/d input) x, one direction or several as rows
 
     def multTranspose(self, lam):
         if self.wrt == "state":

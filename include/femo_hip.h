@@ -374,6 +374,21 @@ int femo_dfunctional(femo_ctx* ctx, const char* name, const char* wrt, double* o
  * replaces assembleMatrix(dR/d arg) + computeMatVecProductBwd
  * (csdl_alpha_opt/state_operation.py:174-184,283-286; fea/utils_dolfinx.py:294-306). */
 int femo_dRdarg_T(femo_ctx* ctx, const char* arg, const double* lambda, double* out, int64_t n);
+/* Forward mode of the same operator: out[k] = (dR/d arg) V[k], k < ndir; V: ndir x femo_field_size(arg), out: ndir x ndof, row-major;
+ * n = femo_field_size(arg), the length of ONE direction -- replaces assembleMatrix(dR/d arg) + computeMatVecProductFwd
+ * (csdl_alpha_opt/state_operation.py:159-171; fea/utils_dolfinx.py:275-283).  arg as for femo_dRdarg_T ("laminate" in laminate mode,
+ * where "thickness", "E" and "nu" give exact zeros, as their transposes do).  R is the residual femo_residual returns: rows of
+ * strong Dirichlet DOFs are zero (R = w - g there), and the state enters with those rows zeroed.  Element results are summed in a
+ * fixed order without float atomics: two identical calls return the same bits. */
+int femo_residual_jvp(femo_ctx* ctx, const char* arg, int32_t ndir, const double* V, int64_t n, double* out);
+/* The forward chain on the device: dW[k] = -K^-1 (dR/d arg) V[k] (grouped through femo_solve_linear_multi: four tangents share a
+ * pair of sweeps), dJ[i*ndir + k] = dJ_i/dw . dW[k] + dJ_i/d arg . V[k] for the named functionals (subdomains as in
+ * femo_total_gradients).  dW (ndir x ndof) may be NULL (tangent states not wanted), nfun may be 0; iters, relres: ndir entries or
+ * NULL.  One tangent solve per direction gives the derivative of every output -- what CSDL's forward mode assembles from
+ * StateOperation.compute_jacvec_product('fwd') and apply_inverse_jacobian('fwd') (csdl_alpha_opt/state_operation.py:159-171, 188-220).
+ * Refusals and status 4 (option "strict") as in femo_total_gradients; the state, the factor and the fields are never written. */
+int femo_total_jvp(femo_ctx* ctx, const char* arg, int32_t ndir, const double* V, int64_t n, int32_t nfun, const char* const* functionals,
+                   const int32_t* subdomains, double* dW, double* dJ, int32_t* iters, double* relres);
 
 /* The whole adjoint chain on the device, no host round trips:
  *   lambda = K^-1 dJ/dw ;  out = dJ/d arg - (dR/d arg)^T lambda      (total derivative)
