@@ -88,6 +88,9 @@ SIGNATURES = {
     "femo_functional": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p]),
     "femo_dfunctional": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, _c_double_p, C.c_int64]),
     "femo_dRdarg_T": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, _c_double_p, C.c_int64]),
+    "femo_field_output_jvp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, _c_double_p, C.c_int64, _c_double_p, C.c_int64]),
+    "femo_field_total_jvp": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_char_p, C.c_int32, _c_double_p, C.c_int64,
+                                       _c_double_p, C.c_int64, _c_double_p, _c_int32_p, _c_double_p]),
     "femo_residual_jvp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _c_double_p, C.c_int64, _c_double_p]),
     "femo_total_jvp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _c_double_p, C.c_int64, C.c_int32, C.POINTER(C.c_char_p), _c_int32_p,
                                  _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),

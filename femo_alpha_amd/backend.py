@@ -587,6 +587,51 @@ class ShellContext:
                                                       iptr(it), dptr(rr)))
         return out, it, rr
 
+    def field_size_of(self, name):
+        """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field'."""
+        if name == "ply_failure_field":
+            return max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // 16
+        return self.mesh.nvc * self.mesh.nel
+
+    def field_output_jvp(self, name, wrt, V):
+        """Forward mode, matrix-free: (d field / d wrt) V for the stored state and fields (femo_field_output_jvp).  ``name``: a DG1
+        stress field or 'ply_failure_field' (flat, cell-major like ``ply_failure_field().ravel()``).  A 1-D ``V`` gives a 1-D result,
+        a 2-D ``V`` (directions as rows) gives rows."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        one = V.ndim == 1
+        V = V.reshape(1, -1) if one else V
+        out = np.empty((V.shape[0], self.field_size_of(name)))
+        self._chk(self.lib.femo_field_output_jvp(self._h, name.encode(), wrt.encode(), V.shape[0], dptr(V), V.shape[1], dptr(out),
+                                                 out.shape[1]))
+        return out[0] if one else out
+
+    def field_total_jvp(self, names, arg, V, want_states=False):
+        """The forward chain for fields (femo_field_total_jvp): one tangent solve per direction, then
+        d field[k] = (d field / d w) dW[k] + (d field / d arg) V[k] for every named field, on the device.  Returns
+        (dict name -> tangents, dW or None, iterations, relative residuals); a 1-D ``V`` is one direction (the arrays lose that
+        axis)."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        one = V.ndim == 1
+        V = V.reshape(1, -1) if one else V
+        nd = V.shape[0]
+        names = list(names)
+        enc = [f.encode() for f in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        sizes = [self.field_size_of(f) for f in names]
+        out = np.empty(nd * sum(sizes))
+        dW = np.empty((nd, self.ndof)) if want_states else None
+        it = np.zeros(nd, dtype=np.int32); rr = np.zeros(nd)
+        self._chk(self.lib.femo_field_total_jvp(self._h, len(enc), arr, arg.encode(), nd, dptr(V), V.shape[1], dptr(out), sum(sizes),
+                                                None if dW is None else dptr(dW), iptr(it), dptr(rr)))
+        res, at = {}, 0
+        for f, sz in zip(names, sizes):
+            blk = out[at:at + nd * sz].reshape(nd, sz)
+            res[f] = blk[0] if one else blk
+            at += nd * sz
+        if one and dW is not None:
+            dW = dW[0]
+        return res, dW, it, rr
+
     def arg_size(self, wrt):
         return self.ndof if wrt == "disp_solid" else self.field_size(wrt)
 

@@ -11,6 +11,7 @@
 #include "stress_history.h"
 #include "disp_history.h"
 #include "ply_failure.h"
+#include "field_jvp.h"
 #include "csr_map.h"
 #include "hip_handles.h"
 
@@ -3353,8 +3354,31 @@ int femo_residual_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* 
     return 0;
 }
 
-// The forward chain: one tangent solve per direction gives the derivative of every output at once.  The tangent right-hand sides and
-// results live in mr_io (never in the solver's own vectors, which a running factorisation may be sweeping ahead on).
+// Tangent states of the forward chains (femo_total_jvp, femo_field_total_jvp): X[k] = -K^-1 (dR/d arg) V[k] on the device, the solves
+// grouped by solve_multi_dev.  The directions, right-hand sides and results live in mr_io (never in the solver's own vectors, which a
+// running factorisation may be sweeping ahead on):  V | B (right-hand sides, overwritten by the solves) | X | `extra` doubles for the
+// caller (*Ed).  jvp_check_arg has run.  Returns solve_multi_dev's status (4: option "strict").
+static int tangent_states_dev(femo_ctx* c, const std::string& a, int ndir, const double* V, int64_t n, size_t extra, double** Vd_out,
+                              double** Xd_out, double** Ed, int32_t* iters, double* relres) {
+    const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
+    HIPCHK(c, c->mr_io.grow((size_t)ndir * (nv + 2 * nd) + extra));
+    double* Vd = c->mr_io;
+    double *Bd = Vd + (size_t)ndir * nv, *Xd = Bd + (size_t)ndir * nd;
+    *Vd_out = Vd; *Xd_out = Xd; *Ed = Xd + (size_t)ndir * nd;
+    std::vector<double*> B(ndir), X(ndir);
+    for (int k = 0; k < ndir; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    HIPCHK(c, hipMemcpy(Vd, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (jvp_prepare(c)) return 1;
+    int rc = 0;
+    for (int k = 0; k < ndir && !rc; ++k) {
+        rc = residual_jvp_dev(c, a, Vd + (size_t)k * n, B[k]);                                          // (dR/d arg) V[k]
+        if (!rc) hipLaunchKernelGGL(k_negate, dim3(vec_grid(nd)), dim3(256), 0, c->stream, B[k], (int64_t)nd);
+    }
+    if (!rc) rc = solve_multi_dev(c, ndir, B.data(), X.data(), iters, relres);                          // dW[k] = -K^-1 (dR/d arg) V[k]
+    return rc;
+}
+
+// The forward chain: one tangent solve per direction gives the derivative of every output at once.
 int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, int64_t n, int32_t nfun, const char* const* functionals,
                    const int32_t* subdomains, double* dW, double* dJ, int32_t* iters, double* relres) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -3371,21 +3395,13 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
         }
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     const int keep_sel = c->csel;
-    // V | B (right-hand sides, overwritten by the solves) | X (tangent states) | dJ/dw | dJ/d arg
-    HIPCHK(c, c->mr_io.grow((size_t)ndir * (nv + 2 * nd) + nd + nv));
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
-    double* Vd = c->mr_io;
-    double *Bd = Vd + (size_t)ndir * nv, *Xd = Bd + (size_t)ndir * nd, *Gw = Xd + (size_t)ndir * nd, *Ga = Gw + nd;
-    std::vector<double*> B(ndir), X(ndir);
-    for (int k = 0; k < ndir; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
-    HIPCHK(c, hipMemcpy(Vd, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    if (jvp_prepare(c)) return 1;
-    int rc = 0;
-    for (int k = 0; k < ndir && !rc; ++k) {
-        rc = residual_jvp_dev(c, a, Vd + (size_t)k * n, B[k]);                                          // (dR/d arg) V[k]
-        if (!rc) hipLaunchKernelGGL(k_negate, dim3(vec_grid(nd)), dim3(256), 0, c->stream, B[k], (int64_t)nd);
-    }
-    if (!rc) rc = solve_multi_dev(c, ndir, B.data(), X.data(), iters, relres);                          // dW[k] = -K^-1 (dR/d arg) V[k]
+    double *Vd = nullptr, *Xd = nullptr, *Gw = nullptr;                                                 // behind X: dJ/dw | dJ/d arg
+    int rc = tangent_states_dev(c, a, ndir, V, n, nd + nv, &Vd, &Xd, &Gw, iters, relres);
+    if (rc) return rc;
+    double* Ga = Gw + nd;
+    std::vector<double*> X(ndir);
+    for (int k = 0; k < ndir; ++k) X[k] = Xd + k * nd;
     const size_t ns = (size_t)nfun * ndir;
     if (!rc && nfun > 0 && hipMemsetAsync(c->jv.scal, 0, 2 * ns * sizeof(double), c->stream) != hipSuccess) rc = fail(c, "hipMemsetAsync failed");
     for (int i = 0; i < nfun && !rc; ++i) {
@@ -5086,6 +5102,146 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     return rc;
 }
 #undef FIELD_UHAT_LAUNCH
+
+// ------------------------------------------------------------------------------------------ forward mode of the field outputs (field_jvp.h)
+static const char* const FIELD_NAMES_JVP = "stress, stress_mid, stress_bot, ply_failure_field";
+
+// entries of the field output `name`; -1: unknown name; -2: the ply failure field without a table (the error is set)
+static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
+    double zf;
+    if (field_zf(name, &zf)) return (int64_t)c->nvc * c->nel;
+    if (name != "ply_failure_field") { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
+    if (ply_need_table(c, "ply_failure_field")) return -2;
+    return (int64_t)c->nel * c->ply.npt;
+}
+
+// wrt is an argument the field `name` can be differentiated by, and n its length.  Every input of the model is accepted (zeros
+// where the field does not depend on it); the shape derivative of the ply failure field is refused like the aggregate's.
+static int field_jvp_check_arg(femo_ctx* c, const std::string& name, const std::string& wrt, int64_t n) {
+    int64_t len;
+    if (wrt == "disp_solid") len = c->ndof;
+    else if (!field_ptr(c, wrt.c_str(), &len) || wrt == "dirichlet") return fail(c, "unknown argument '" + wrt + "'");
+    if (name == "ply_failure_field" && wrt == "uhat")
+        return fail(c, "ply_failure_field: the shape derivative (uhat) of this output is not provided");
+    if (len != n) return fail(c, "buffer has the wrong length for '" + wrt + "'");
+    return 0;
+}
+
+#define FIELD_JVP_UHAT_LAUNCH(c, nthreads, ...)                                                                                        \
+    do {                                                                                                                               \
+        const int g_ = nblk(nthreads, 128);                                                                                            \
+        if ((c)->cg1) { if ((c)->quad) hipLaunchKernelGGL((k_field_jvp_uhat<4, 4, true>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); \
+                        else hipLaunchKernelGGL((k_field_jvp_uhat<3, 3, false>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); }  \
+        else { if ((c)->quad) hipLaunchKernelGGL((k_field_jvp_uhat<9, 4, true>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__);     \
+               else hipLaunchKernelGGL((k_field_jvp_uhat<6, 3, false>), dim3(g_), dim3(128), 0, (c)->stream, __VA_ARGS__); }            \
+    } while (0)
+#define COMMA_PFJ_STATE , false
+#define COMMA_PFJ_TABLE , true
+
+// out[k] (device, ndir rows of nout) = (d field / d wrt) V[k] for ndir device directions of n entries; every entry of out is written.
+// tmp: n doubles of device scratch for a table direction (wrt "ply_table" of the ply failure field), else unused.
+static int field_jvp_dev(femo_ctx* c, const std::string& name, const std::string& wrt, int ndir, const double* V, int64_t n, double* out,
+                         int64_t nout, double* tmp) {
+    const MeshDev m = mesh_dev_all(c);
+    const FieldsDev f = fields_dev(c);
+    double zf = 0.0;
+    const bool vm = field_zf(name, &zf);
+    const int mode = wrt == "disp_solid" ? FJ_W : wrt == "thickness" ? FJ_H : wrt == "E" ? FJ_E : wrt == "nu" ? FJ_NU : 0;
+    if (vm && mode && !(mode == FJ_H && zf == 0.0)) {
+        ELEM_LAUNCH(c, k_field_jvp, NOEXTRA, nblk(c->nel, FJ_BLOCK), FJ_BLOCK, m, f, c->tab, (const double*)c->w, zf, mode, ndir, V, n, out, nout);
+    } else if (vm && wrt == "uhat") {
+        FIELD_JVP_UHAT_LAUNCH(c, (int64_t)ndir * c->nel, m, f, c->tab, (const double*)c->w, zf, ndir, V, n, out, nout);
+    } else if (!vm && mode == FJ_W) {
+        ELEM_LAUNCH(c, k_ply_field_jvp, COMMA_PFJ_STATE, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, m, f, c->tab_s, (const double*)c->ply.tabT, c->ply.npt,
+                    (const double*)c->w, ndir, V, n, out, nout);
+    } else if (!vm && wrt == "ply_table") {
+        const int per = PLY_W * c->ply.npt;
+        for (int k = 0; k < ndir; ++k) {                // one direction at a time through the transposed copy: the stream orders them
+            hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, V + (size_t)k * n, tmp, c->nel, per);
+            ELEM_LAUNCH(c, k_ply_field_jvp, COMMA_PFJ_TABLE, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, m, f, c->tab_s, (const double*)c->ply.tabT,
+                        c->ply.npt, (const double*)c->w, 1, (const double*)tmp, n, out + (size_t)k * nout, nout);
+        }
+    } else {                                            // the field does not depend on the argument: exact zeros
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid((int64_t)ndir * nout)), dim3(256), 0, c->stream, out, 0.0, (int64_t)ndir * nout);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int femo_field_output_jvp(femo_ctx* c, const char* name, const char* wrt, int32_t ndir, const double* V, int64_t n, double* out, int64_t nout) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const std::string fname(name ? name : ""), a(wrt ? wrt : "");
+    const int64_t size = field_jvp_size(c, fname);
+    if (size < 0) return size == -1 ? 1 : 2;
+    if (ndir < 1 || !V || !out) return fail(c, "femo_field_output_jvp: ndir >= 1 directions, one after the other");
+    if (int rc = field_jvp_check_arg(c, fname, a, n)) return rc;
+    if (nout != size) return fail(c, fname == "ply_failure_field" ? "femo_field_output_jvp: the ply failure field has nel * npt entries"
+                                                                  : "femo_field_output_jvp: the DG1 stress field has nvc * nel entries");
+    const size_t nv = (size_t)std::max<int64_t>(n, 1);
+    const bool table = fname == "ply_failure_field" && a == "ply_table";
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)ndir * (nv + (size_t)nout) + (table ? nv : 0)));
+    double* o = d + (size_t)ndir * nv;
+    if (hipMemcpy(d, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(c, "copy of the directions failed");
+    if (int rc = field_jvp_dev(c, fname, a, ndir, d, n, o, nout, o + (size_t)ndir * nout)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o, (size_t)ndir * (size_t)nout * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The forward chain for fields: the tangent states of tangent_states_dev (the code path of femo_total_jvp) stay on the device and
+// go through (d field / d w) of every named field; the explicit partial (d field / d arg) V[k] is added where there is one.
+int femo_field_total_jvp(femo_ctx* c, int32_t nnames, const char* const* names, const char* arg, int32_t ndir, const double* V, int64_t n,
+                         double* out, int64_t nout, double* dW, int32_t* iters, double* relres) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nnames < 1 || !names || !out) return fail(c, "femo_field_total_jvp: nnames >= 1 field names and room for their tangents");
+    if (ndir < 1 || !V) return fail(c, "femo_field_total_jvp: ndir >= 1 directions, one after the other");
+    const std::string a(arg ? arg : "");
+    std::vector<std::string> fn(nnames);
+    std::vector<int64_t> size(nnames);
+    int64_t total = 0, largest = 0;
+    for (int i = 0; i < nnames; ++i) {
+        fn[i] = names[i] ? names[i] : "";
+        size[i] = field_jvp_size(c, fn[i]);
+        if (size[i] < 0) return size[i] == -1 ? 1 : 2;
+        total += size[i];
+        largest = std::max(largest, size[i]);
+    }
+    if (a == "disp_solid") return fail(c, "femo_field_total_jvp: the state is not an argument of the total derivative");
+    if (int rc = jvp_check_arg(c, a, n)) return rc;
+    for (int i = 0; i < nnames; ++i)
+        if (int rc = field_jvp_check_arg(c, fn[i], a, n)) return rc;
+    if (nout != total) return fail(c, "femo_field_total_jvp: nout must be the sum of the fields' lengths");
+    const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
+    // behind X: the tangents of all fields | state term and explicit partial of one field | a transposed table direction
+    const bool table = a == "ply_table";
+    double *Vd = nullptr, *Xd = nullptr, *Od = nullptr;
+    if (int rc = tangent_states_dev(c, a, ndir, V, n, (size_t)ndir * ((size_t)total + 2 * (size_t)largest) + (table ? nv : 0), &Vd, &Xd, &Od, iters, relres))
+        return rc;
+    double* Sd = Od + (size_t)ndir * total;
+    double* Pd = Sd + (size_t)ndir * largest;
+    double* Td = Pd + (size_t)ndir * largest;
+    double* o = Od;
+    for (int i = 0; i < nnames; ++i) {
+        const int64_t len = (int64_t)ndir * size[i];
+        // the arguments a field depends on directly; for every other one (F_solid, density, laminate, ...) only the state term remains
+        const bool partial = fn[i] == "ply_failure_field" ? table
+                                                          : ((a == "thickness" && fn[i] != "stress_mid") || a == "E" || a == "nu" || a == "uhat");
+        if (int rc = field_jvp_dev(c, fn[i], "disp_solid", ndir, Xd, c->ndof, partial ? Sd : o, size[i], nullptr)) return rc;      // (d field / d w) dW[k]
+        if (partial) {
+            if (int rc = field_jvp_dev(c, fn[i], a, ndir, Vd, n, Pd, size[i], Td)) return rc;                                      // + (d field / d arg) V[k]
+            hipLaunchKernelGGL(k_lincomb3, dim3(vec_grid(len)), dim3(256), 0, c->stream, o, 1.0, (const double*)Sd, 1.0, (const double*)Pd, 0.0,
+                               (const double*)nullptr, len);
+        }
+        o += len;
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, Od, (size_t)ndir * (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    if (dW) HIPCHK(c, hipMemcpy(dW, Xd, (size_t)ndir * nd * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+#undef FIELD_JVP_UHAT_LAUNCH
 
 int femo_last_timing(const femo_ctx* c, double* out5) {
     for (int i = 0; i < 5; ++i) out5[i] = c->timing[i];

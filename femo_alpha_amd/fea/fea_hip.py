@@ -130,8 +130,10 @@ class Form:
 
 
 class FieldForm:
-    """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1), 'stress_mid', 'stress_bot'.
-    ``assemble(computePartials(field_form, f), dim=2)`` is its sparse partial Jacobian."""
+    """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1), 'stress_mid', 'stress_bot', and in
+    laminate mode with a ply table 'ply_failure_field' ((nel, npt) flattened).  ``assemble(computePartials(field_form, f), dim=2)``
+    is the sparse partial Jacobian of a stress field; ``computeMatVecProductFwd(computePartials(field_form, f), v)`` is the
+    matrix-free tangent of any of them."""
 
     def __init__(self, ctx, name):
         self.ctx, self.name = ctx, name
@@ -254,8 +256,14 @@ def assemble(f, dim=0, bcs=()):
     raise TypeError("Invalid type for assembly.")
 
 
-def computeMatVecProductFwd(A: JacobianOperator, x):
-    return A.mult(x.get() if isinstance(x, Function) else x)
+def computeMatVecProductFwd(A, x):
+    """A x for an assembled operator; the partial of a field output (``computePartials(field_form, f)``) is applied matrix-free on
+    the device (femo_field_output_jvp) -- no CSR is built."""
+    x = x.get() if isinstance(x, Function) else x
+    if isinstance(A, PartialForm) and isinstance(A.form, FieldForm):
+        wrt = "disp_solid" if A.wrt.role == "state" else A.wrt.role
+        return A.form.ctx.field_output_jvp(A.form.name, wrt, x)
+    return A.mult(x)
 
 
 def computeMatVecProductBwd(A: JacobianOperator, R):
@@ -300,6 +308,8 @@ class FEA:
         self.nel = mesh.nel
         self.nn = mesh.nn
         self.last_solve = (0, 0.0)
+        # caller order <-> solver order of a renumbered model (RMShellModel(renumber=True) sets them); None: the same order
+        self.vertex_of_new = self.cell_of_new = None
 
     def add_input(self, name, function: Function, init_val=1.0, record=False):
         if name in self.inputs_dict:
@@ -337,6 +347,35 @@ class FEA:
     def projectFieldOutput(self, form, func):
         """L2 projection of the field form onto its DG1 function (fea_dolfinx.py:205-206)."""
         func.set(form.ctx.field_output(form.name))
+
+    def field_tangents(self, names, arg_name, V, state="disp_solid"):
+        """Total tangents of field outputs along directions of one input: {name: d field / d arg . V[k]} through the solved state,
+        one tangent solve per direction for all the names (femo_field_total_jvp on the context of the state's residual).  Nothing
+        is pushed: the inputs and the state are the ones the context holds.  ``names``: registered field outputs or the backend's
+        own names ('stress', 'stress_mid', 'stress_bot', 'ply_failure_field').  ``V`` (one direction, or several as rows) and the
+        answers are in caller order when the model was renumbered."""
+        ctx = self.states_dict[state]["residual_form"].ctx
+        fn = [self.outputs_field_dict[n]["form"].name if n in self.outputs_field_dict else n for n in names]
+        V = np.asarray(V, dtype=np.float64)
+        one = V.ndim == 1
+        V = V.reshape(1, -1) if one else V.reshape(V.shape[0], -1)
+        space = self.inputs_dict[arg_name]["function_space"]
+        per_cell = space.kind in ("VL", "VP") or (space.kind == "VT" and ctx.element_wise_material) \
+            or (space.kind == "VF" and ctx.elementwise_pressure)
+        idx = self.cell_of_new if per_cell else self.vertex_of_new
+        if idx is not None:
+            V = V.reshape(V.shape[0], len(idx), -1)[:, idx].reshape(V.shape[0], -1)         # caller order -> solver order
+        res, _, its, rrs = ctx.field_total_jvp(fn, arg_name, V)
+        self.last_solve = (int(its.max()), float(rrs.max()))
+        out = {}
+        for n, f in zip(names, fn):
+            t = res[f]
+            if self.cell_of_new is not None:
+                new_of_cell = np.empty(self.nel, dtype=np.int64)
+                new_of_cell[self.cell_of_new] = np.arange(self.nel)
+                t = t.reshape(t.shape[0], self.nel, -1)[:, new_of_cell].reshape(t.shape[0], -1)     # solver order -> caller order
+            out[n] = t[0] if one else t
+        return out
 
     def add_strong_bc(self, ubc, locate_BC_list, function_space=None):
         for dofs in locate_BC_list:

@@ -152,6 +152,8 @@ class RMShellModel:
                                                 elementwise_pressure=self.elementwise_pressure, device=self.device,
                                                 nquad=self._nquad_arg, laminate=self.laminate, ply_failure=self.ply_failure)
         fea = FEA(mesh)
+        if self.caller_mesh is not mesh:                 # renumbered: FEA.field_tangents answers in caller order
+            fea.vertex_of_new, fea.cell_of_new = self.vertex_of_new, self.cell_of_new
         fea.PDE_SOLVER = "Newton"
         fea.REPORT = False
         fea.record = False                    # XDMF recording is out of scope; the flag is accepted and ignored
@@ -203,6 +205,10 @@ class RMShellModel:
                                arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         fea.add_field_output(name="stress", form=stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"],
                              function_space=("DG", 1), record=False, vtk=True)
+        if self.ply_failure is not None:
+            # (nel, npt) flattened; a diagnostic with forward-mode tangents only (FEA.field_tangents), so it is not registered as a
+            # field output of the CSDL model, whose operations differentiate in reverse
+            self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, ply)
         self.fea = fea
 
     def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None,

@@ -130,6 +130,11 @@ class RMShellPDE:
         self.ctx.set_ply_failure_params(rho)
         return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
 
+    def ply_failure_field(self, w, uhat, ply_table):
+        """The (nel, npt) field of the largest ply failure index per cell and recovery point as a field form: its tangents come
+        from ``computeMatVecProductFwd(computePartials(form, f), v)`` and ``FEA.field_tangents`` (forward mode only)."""
+        return FieldForm(self.ctx, "ply_failure_field")
+
     def pnorm_stress(self, w, uhat, h, E, nu, dx=None, m=1e-6, rho=100, alpha=None, regularization=False):
         """1/alpha int (m vm_top)^rho J dx with the degree-4 measure (rm_shell_pde.py:112-128); alpha is the
         reference area, evaluated by the backend on first use."""

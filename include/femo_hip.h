@@ -134,7 +134,10 @@ int femo_set_laminate(femo_ctx* ctx, const double* clt, int64_t n);
  *     ((dR/d ply_table)^T lambda is zero), "F_solid" as for any functional.  wrt / arg "uhat" is refused: the shape derivative of this
  *     output is not provided.  No float atomics and fixed summation orders: two identical calls return the same bits;
  *   - field femo_ply_failure_field: (nel, npt), entry = max over the cell's quadrature points of FI, every cell whatever the selected
- *     sub-domain (a diagnostic -- which ply, where; not differentiated).
+ *     sub-domain (a diagnostic -- which ply, where; differentiated in forward mode only: femo_field_output_jvp and
+ *     femo_field_total_jvp, name "ply_failure_field").  The tangent of an entry is the tangent of FI at the quadrature point that
+ *     attains the maximum; on ties the first point in quadrature order wins -- the point the value's running maximum keeps, which a
+ *     strict > replaces.  It is the one-sided derivative wherever the maximiser is unique.
  * femo_set_ply_table is refused with the cell index for non-finite entries, and when not in laminate mode, for npt out of range or a
  * wrong n.  table == NULL with n == 0 removes the table; leaving laminate mode removes it too.  The operator does not see the table:
  * the factor and the Jacobi diagonal are kept.  With a table "ply_table" is an ordinary field (femo_field_size / femo_set_field /
@@ -357,6 +360,30 @@ int femo_field_output_jacobian(femo_ctx* ctx, const char* name, const char* wrt,
                                int64_t nnz);
 int femo_field_total_gradients(femo_ctx* ctx, const char* name, int32_t nbar, const double* cbar, const char* arg, double* out,
                                int64_t n, int32_t* iters, double* relres);
+/* Forward mode of the field outputs, matrix-free: out[k] = (d field / d wrt) V[k] at the stored state and fields, k < ndir.
+ * V: ndir x n, row-major, n the length of ONE direction (femo_ndof for "disp_solid", else femo_field_size(wrt)); out: ndir x nout,
+ * nout the field's length (checked).
+ *   name "stress" | "stress_mid" | "stress_bot" (layout of femo_field_output): wrt as for femo_field_output_vjp; "F_solid" and
+ *     "density" give exact zeros, "stress_mid" with "thickness" too, and in laminate mode "laminate" and "ply_table" (these fields
+ *     keep the single-layer recovery).  The zero-stress convention is that of the reverse products.
+ *   name "ply_failure_field" (laminate mode with a table; nout = nel * npt, layout of femo_ply_failure_field; the maximiser
+ *     convention is stated at femo_set_ply_table above): wrt "disp_solid" or "ply_table"; "laminate", "thickness", "E", "nu",
+ *     "density" and "F_solid" give exact zeros; "uhat" is refused like the aggregate's shape derivative.
+ * Every cell owns its entries of the output: plain stores, no float atomics, two identical calls return the same bits, and ndir
+ * directions in one call give the bits of ndir single calls.  Refused (nothing is written): an unknown field output, an unknown
+ * argument, a wrong n or nout, no ply table (the message names femo_set_ply_table), ndir < 1.  The state, the fields and the
+ * factor are never written.
+ * femo_field_total_jvp: the forward chain for fields.  dW[k] = -K^-1 (dR/d arg) V[k] by the code path of femo_total_jvp (grouping,
+ * strong-row masking, option "strict" with status 4 and the refusals are the same; arg as there, "F_solid" and "laminate"
+ * included), then for every named field d field[k] = (d field / d w) dW[k] + (d field / d arg) V[k]; the tangent states never
+ * leave the device, and one tangent solve per direction serves every named field.  out holds the fields one after another in the
+ * order of names, each an ndir x size_i block; nout = the sum of the sizes (checked).  Names may mix stress fields and the ply
+ * failure field; "uhat" together with "ply_failure_field" is refused before any solve.  dW (ndir x ndof), iters and relres (ndir
+ * entries) may be NULL. */
+int femo_field_output_jvp(femo_ctx* ctx, const char* name, const char* wrt, int32_t ndir, const double* V, int64_t n, double* out,
+                          int64_t nout);
+int femo_field_total_jvp(femo_ctx* ctx, int32_t nnames, const char* const* names, const char* arg, int32_t ndir, const double* V,
+                         int64_t n, double* out, int64_t nout, double* dW, int32_t* iters, double* relres);
 /* Scalar outputs for the stored state and fields: "compliance", "mass", "elastic_energy", "pnorm_stress", "volume",
  * "regularization" (the thickness term of the compliance, rm_shell_pde.py:64-83), and over the selected sub-domain
  * (femo_select_subdomain; the whole mesh if none) "tip_disp" = 0.5 int u.u J, "area" = int J (rm_shell_pde.py:95-105) and
