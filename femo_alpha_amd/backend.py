@@ -151,6 +151,88 @@ class ShellContext:
         v = self._vec(a)
         self._chk(self.lib.femo_set_ply_table(self._h, dptr(v), int(npt), v.size))
 
+    LAYUP_SURFACES = {"bot": 1, "mid": 2, "top": 4}
+
+    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None):
+        """Layup mode (femo_set_layup): the laminate and the ply table are built on the device from ply thicknesses ``t`` and ply
+        angles ``theta`` (degrees from E0), both (nel, nply) in solver cell order or (nply,) for the same layup in every cell; plies
+        bottom to top.  ``plies``: one dict per ply, or one for all, with E1, E2, G12, nu12, G13, G23 and either the strengths
+        Xt, Xc, Yt, Yc, S (and optionally f12) of ``laminate.tsai_wu`` or its six coefficients as ``F``; or an (nply, 12) array
+        [E1, E2, G12, nu12, G13, G23, F1, F2, F11, F22, F66, F12].  ``surfaces``: recovery points of every ply out of "bot", "mid",
+        "top", in that order; () for none (no ply table).  ``c_drill=None`` takes the reference's 12 max(D) of this initial layup
+        once; the mode then holds it constant.  ``plies=None`` leaves the mode and keeps the laminate and the table as ordinary
+        values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points."""
+        if plies is None:
+            self._chk(self.lib.femo_set_layup(self._h, 0, None, 0, 0.0, None, None))
+            return
+        from . import laminate as lam
+        t = np.asarray(t, dtype=np.float64)
+        theta = np.asarray(theta, dtype=np.float64)
+        nply = t.shape[-1] if t.ndim else 1
+        pc = self._layup_plies(plies, nply)
+        bits = [self.LAYUP_SURFACES.get(s) for s in surfaces]
+        if None in bits or bits != sorted(set(bits)):
+            raise ValueError(f"set_layup: surfaces out of 'bot', 'mid', 'top', each once and in that order, got {tuple(surfaces)!r}")
+        nel = self.mesh.nel
+        t = np.ascontiguousarray(np.broadcast_to(t.reshape(-1, nply), (nel, nply)))
+        theta = np.ascontiguousarray(np.broadcast_to(theta.reshape(-1, nply), (nel, nply)))
+        if c_drill is None:
+            # 12 max(D) over all entries of all cells (laminate.pack); D does not depend on the shear moduli
+            D = lam.clt_from_plies(pc[:, 0], pc[:, 1], pc[:, 2], pc[:, 3], pc[:, 4], pc[:, 5], t, theta)[2]
+            c_drill = 12.0 * float(np.max(D))
+        self._chk(self.lib.femo_set_layup(self._h, int(nply), dptr(pc), int(sum(bits)), float(c_drill), dptr(t), dptr(theta)))
+
+    @staticmethod
+    def _layup_plies(plies, nply):
+        """(nply, 12) per-ply constants of femo_set_layup; strengths go through ``laminate.tsai_wu``."""
+        from .laminate import tsai_wu
+        if isinstance(plies, dict):
+            plies = [plies] * nply
+        if isinstance(plies, (list, tuple)) and plies and isinstance(plies[0], dict):
+            if len(plies) != nply:
+                raise ValueError(f"set_layup: {len(plies)} ply materials for {nply} plies")
+            rows = []
+            for p in plies:
+                F = p["F"] if "F" in p else tsai_wu(p["Xt"], p["Xc"], p["Yt"], p["Yc"], p["S"], p.get("f12", -0.5))
+                rows.append([p["E1"], p["E2"], p["G12"], p["nu12"], p["G13"], p["G23"], *np.asarray(F, dtype=np.float64).ravel()])
+            plies = rows
+        pc = np.ascontiguousarray(np.asarray(plies, dtype=np.float64))
+        if pc.shape != (nply, 12):
+            raise ValueError(f"set_layup: plies must give 12 constants for each of the {nply} plies, got shape {pc.shape}")
+        return pc
+
+    def layup_jvp(self, wrt, V, laminate=True, table=True):
+        """Tangents of the built laminate and table (femo_layup_jvp): ``V`` is (nel, nply) or (ndir, nel, nply), ``wrt``
+        "ply_thickness" or "ply_angle" (per degree).  Returns (dlaminate (.., nel, 32) or None, dtable (.., nel, npt, 16) or None)."""
+        n = self.field_size(wrt)
+        V = np.ascontiguousarray(np.asarray(V, dtype=np.float64))
+        single = V.size == n
+        V = V.reshape(-1, n)
+        nel = self.mesh.nel
+        nt = int(self.lib.femo_field_size(self._h, b"ply_table"))
+        dl = np.empty((V.shape[0], nel, 32)) if laminate else None
+        dt = np.empty((V.shape[0], nel, nt // (16 * nel), 16)) if table and nt > 0 else None
+        self._chk(self.lib.femo_layup_jvp(self._h, wrt.encode(), V.shape[0], dptr(V), n, None if dl is None else dptr(dl),
+                                          None if dt is None else dptr(dt)))
+        if single:
+            dl, dt = (None if a is None else a[0] for a in (dl, dt))
+        return dl, dt
+
+    def layup_vjp(self, wrt, laminate_bar=None, table_bar=None):
+        """(nel, nply): the cotangents of the laminate (nel, 32) and of the table (nel, npt, 16), either may be None, pulled back to
+        the ply thicknesses or angles (femo_layup_vjp)."""
+        n = self.field_size(wrt)
+        lb = None if laminate_bar is None else self._vec(laminate_bar)
+        tb = None if table_bar is None else self._vec(table_bar)
+        if lb is not None and lb.size != 32 * self.mesh.nel:
+            raise ValueError("layup_vjp: laminate_bar has 32 values per cell")
+        if tb is not None and tb.size != max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0):
+            raise ValueError("layup_vjp: table_bar has 16 npt values per cell")
+        out = np.empty(n)
+        self._chk(self.lib.femo_layup_vjp(self._h, wrt.encode(), None if lb is None else dptr(lb), None if tb is None else dptr(tb),
+                                          dptr(out), n))
+        return out.reshape(self.mesh.nel, -1)
+
     def set_ply_failure_params(self, rho=100.0):
         """Exponent of the "ply_failure" aggregate (femo_set_ply_failure_params)."""
         self._chk(self.lib.femo_set_ply_failure_params(self._h, float(rho)))

@@ -12,6 +12,7 @@
 #include "disp_history.h"
 #include "ply_failure.h"
 #include "field_jvp.h"
+#include "layup.h"
 #include "csr_map.h"
 #include "hip_handles.h"
 
@@ -133,6 +134,17 @@ struct femo_ctx {
         DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
         DevBuf<int> eslot;          // slot of every cell in ybuf (the inverse of eorder), built at first use
     } ply;
+    // layup mode (femo_set_layup; layup.h): the laminate and the ply table are built on the device from ply thicknesses and angles
+    struct Layup {
+        bool active = false;
+        int nply = 0, surfaces = 0, npt = 0;
+        double c_drill = 0.0;
+        DevBuf<double> t, th, pc;   // ply-major [k][nel] thicknesses and angles (degrees); LAY_PC constants per ply
+        DevBuf<double> tn, thn;     // the candidates of a set call: adopted once they have passed the check
+        DevBuf<double> stage;       // a cell-major copy on its way in or out
+        DevBuf<double> lbar, tbar;  // laminate / table cotangents (tangents) of the chain rule inside the derivative entry points
+        DevBuf<long long> slots;    // k_layup_check: one slot per block, then the first offending entry
+    } lay;
     // dirichlet
     int nf = 0;
     struct Facets {
@@ -2254,6 +2266,9 @@ static double* field_ptr(const femo_ctx* c, const char* name, int64_t* n) {
     if (s == "dirichlet" && c->gdir) { *n = c->ndof; return c->gdir; }
     if (s == "laminate" && c->laminate) { *n = (int64_t)LAM_W * c->nel; return c->clt; }
     if (s == "ply_table" && c->ply.npt > 0) { *n = (int64_t)PLY_W * c->ply.npt * c->nel; return c->ply.tab; }
+    // layup mode: nel x nply values; the device copies are ply-major ([k][nel]), the ABI's vectors cell-major
+    if (s == "ply_thickness" && c->lay.active) { *n = (int64_t)c->nel * c->lay.nply; return c->lay.t; }
+    if (s == "ply_angle" && c->lay.active) { *n = (int64_t)c->nel * c->lay.nply; return c->lay.th; }
     *n = -1;
     return nullptr;
 }
@@ -2325,8 +2340,18 @@ int femo_set_strong_dofs(femo_ctx* c, int32_t n, const int32_t* dofs) {
     return 0;
 }
 
+static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n);
+static int layup_get_field(femo_ctx* c, bool angle, double* v, int64_t n);
+static const char* const LAYUP_OWNS = ": the laminate and the ply table belong to the active layup (femo_set_layup); set 'ply_thickness' / "
+                                      "'ply_angle', or leave the mode with femo_set_layup(ctx, 0, NULL, ...)";
+
 int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->lay.active && name) {
+        const std::string s(name);
+        if (s == "laminate" || s == "ply_table") return fail(c, "field '" + s + "'" + LAYUP_OWNS);
+        if (s == "ply_thickness" || s == "ply_angle") return layup_set_field(c, s == "ply_angle", v, n);
+    }
     if (name && std::string(name) == "laminate") {
         if (!c->laminate) return fail(c, "field 'laminate' exists in laminate mode only (femo_set_laminate)");
         if (!v) return fail(c, "null values");
@@ -2376,6 +2401,8 @@ int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
 
 int femo_get_field(femo_ctx* c, const char* name, double* v, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->lay.active && name && (std::string(name) == "ply_thickness" || std::string(name) == "ply_angle"))
+        return layup_get_field(c, std::string(name) == "ply_angle", v, n);
     int64_t len;
     double* d = field_ptr(c, name, &len);
     if (!d) return fail(c, "unknown field");
@@ -2414,11 +2441,13 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
             c->clt.reset();
             c->clt_sym.reset();
             c->ply = femo_ctx::Ply();                          // the recovery points belong to the laminate
+            c->lay = femo_ctx::Layup();                        // ... and so does the layup
             operator_changed(c);
             ++c->opt_version;
         }
         return 0;
     }
+    if (c->lay.active) return fail(c, std::string("femo_set_laminate") + LAYUP_OWNS);
     const int64_t len = (int64_t)LAM_W * c->nel;
     if (!clt || n != len) {
         char buf[200];
@@ -2484,6 +2513,7 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
 
 int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->lay.active) return fail(c, std::string("femo_set_ply_table") + LAYUP_OWNS);
     if (!table && n == 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->ply = femo_ctx::Ply();
@@ -2524,6 +2554,234 @@ int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n)
 int femo_set_ply_failure_params(femo_ctx* c, double rho) {
     if (!(rho > 0.0) || !std::isfinite(rho)) return fail(c, "ply_failure: rho must be finite and > 0");
     c->ply.rho = rho;
+    return 0;
+}
+
+// ---- layups (layup.h): the laminate and the ply table built on the device from ply thicknesses and angles
+// 0: not a layup argument (or no layup is active); 1: "ply_thickness"; 2: "ply_angle"
+static int layup_wrt(const femo_ctx* c, const std::string& s) {
+    if (!c->lay.active) return 0;
+    return s == "ply_thickness" ? 1 : s == "ply_angle" ? 2 : 0;
+}
+
+static LayupDev layup_dev(const femo_ctx* c, const double* t, const double* th) {
+    return LayupDev{t, th, c->lay.pc, c->nel, c->lay.nply, c->lay.surfaces, c->lay.npt, c->lay.c_drill};
+}
+
+// host values (nel x nply, cell-major; one value broadcasts) into the ply-major device buffer dst
+static int layup_upload(femo_ctx* c, const double* v, int64_t n, int nply, DevBuf<double>& dst) {
+    const int64_t len = (int64_t)c->nel * nply;
+    HIPCHK(c, dst.grow((size_t)len));
+    HIPCHK(c, c->lay.stage.grow((size_t)len));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n == 1 && len != 1) {
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(len)), dim3(256), 0, c->stream, dst.get(), v[0], len);
+    } else {
+        HIPCHK(c, hipMemcpy(c->lay.stage, v, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->lay.stage, dst.get(), c->nel, nply);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// t > 0 and finite, theta finite, checked on the device: one flag comes back, and the error names the first offending cell and ply
+static int layup_check(femo_ctx* c, const double* t, const double* th, int nply) {
+    const int g = nblk(c->nel, LAY_BLOCK);
+    HIPCHK(c, c->lay.slots.grow((size_t)g + 1));
+    hipLaunchKernelGGL(k_layup_check, dim3(g), dim3(LAY_BLOCK), 0, c->stream, t, th, c->nel, nply, c->lay.slots.get());
+    hipLaunchKernelGGL(k_layup_first, dim3(1), dim3(256), 0, c->stream, (const long long*)c->lay.slots, g, c->lay.slots.get() + g);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    long long code = 0;
+    HIPCHK(c, hipMemcpy(&code, c->lay.slots.get() + g, sizeof code, hipMemcpyDeviceToHost));
+    if (code == LAY_OK) return 0;
+    char buf[200];
+    const long long e = code / (2 * LAY_MAXPLY);
+    const int k = (int)(code / 2 % LAY_MAXPLY);
+    if (code & 1) snprintf(buf, sizeof buf, "layup: the angle of ply %d of cell %lld is not finite", k, e);
+    else snprintf(buf, sizeof buf, "layup: the thickness of ply %d of cell %lld is not positive and finite", k, e);
+    return fail(c, buf);
+}
+
+// the laminate and the table of the layup the context holds, enqueued on the stream
+static int layup_build(femo_ctx* c) {
+    hipLaunchKernelGGL(k_layup_build, dim3(nblk(c->nel, LAY_BLOCK)), dim3(LAY_BLOCK), 0, c->stream, layup_dev(c, c->lay.t, c->lay.th), c->clt.get(),
+                       c->clt_sym.get(), c->ply.tab.get(), c->ply.tabT.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// out (nel nply, cell-major, device) += J^T (lbar, tbar); either cotangent may be null.  wrt: layup_wrt's 1 or 2
+static int layup_vjp_dev(femo_ctx* c, int wrt, const double* lbar, const double* tbar, double* out) {
+    const LayupDev L = layup_dev(c, c->lay.t, c->lay.th);
+    const int g = nblk(c->nel, LAY_BLOCK);
+    if (wrt == 1) hipLaunchKernelGGL((k_layup_vjp<LAY_T>), dim3(g), dim3(LAY_BLOCK), 0, c->stream, L, lbar, tbar, out);
+    else hipLaunchKernelGGL((k_layup_vjp<LAY_THETA>), dim3(g), dim3(LAY_BLOCK), 0, c->stream, L, lbar, tbar, out);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// (dlam, dtab)[k] = J V[k] for ndir device directions (cell-major); either output may be null
+static int layup_jvp_dev(femo_ctx* c, int wrt, int ndir, const double* V, double* dlam, double* dtab) {
+    const LayupDev L = layup_dev(c, c->lay.t, c->lay.th);
+    const dim3 g(nblk(c->nel, LAY_BLOCK), ndir);
+    if (wrt == 1) hipLaunchKernelGGL((k_layup_jvp<LAY_T>), g, dim3(LAY_BLOCK), 0, c->stream, L, V, dlam, dtab);
+    else hipLaunchKernelGGL((k_layup_jvp<LAY_THETA>), g, dim3(LAY_BLOCK), 0, c->stream, L, V, dlam, dtab);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfaces, double c_drill, const double* t, const double* theta) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& lay = c->lay;
+    if (nply == 0 && !plies) {                             // leave the mode: what was built stays as ordinary values
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        lay = femo_ctx::Layup();
+        return 0;
+    }
+    char buf[240];
+    if (nply < 1 || nply > LAY_MAXPLY) {
+        snprintf(buf, sizeof buf, "femo_set_layup: nply must be 1..%d plies, got %d", LAY_MAXPLY, (int)nply);
+        return fail(c, buf);
+    }
+    if (surfaces < 0 || surfaces > 7) return fail(c, "femo_set_layup: surfaces is a mask of 1 (bot), 2 (mid), 4 (top); 0: no recovery points");
+    const int ns = (surfaces & 1) + (surfaces >> 1 & 1) + (surfaces >> 2 & 1), npt = nply * ns;
+    if (npt > PLY_MAX) {
+        snprintf(buf, sizeof buf, "femo_set_layup: %d plies x %d surfaces = %d recovery points per cell, at most %d", (int)nply, ns, npt, PLY_MAX);
+        return fail(c, buf);
+    }
+    if (!plies || !t || !theta) return fail(c, "femo_set_layup: null values (plies: nply x 12, t and theta: nel x nply)");
+    if (c->op_aM != 0.0) return fail(c, "femo_set_layup: the operator has an inertia term (femo_set_operator); transient laminates are not supported");
+    std::vector<double> pc((size_t)nply * LAY_PC);
+    for (int k = 0; k < nply; ++k) {
+        const double* P = plies + 12 * (size_t)k;
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(P[j])) {
+                snprintf(buf, sizeof buf, "femo_set_layup: constant %d of ply %d is not finite", j, k);
+                return fail(c, buf);
+            }
+        const double E1 = P[0], E2 = P[1], G12 = P[2], nu12 = P[3], G13 = P[4], G23 = P[5];
+        if (!(E1 > 0.0 && E2 > 0.0 && G12 > 0.0 && G13 > 0.0 && G23 > 0.0)) {
+            snprintf(buf, sizeof buf, "femo_set_layup: the moduli E1, E2, G12, G13, G23 of ply %d must be positive", k);
+            return fail(c, buf);
+        }
+        const double nu21 = nu12 * E2 / E1, den = 1.0 - nu12 * nu21;           // the order of laminate.ply_stiffness
+        if (!(den > 0.0)) {
+            snprintf(buf, sizeof buf, "femo_set_layup: ply %d has 1 - nu12^2 E2 / E1 <= 0", k);
+            return fail(c, buf);
+        }
+        double* q = pc.data() + (size_t)k * LAY_PC;
+        q[0] = E1 / den; q[1] = E2 / den; q[2] = nu12 * E2 / den; q[3] = G12; q[4] = G13; q[5] = G23;
+        for (int j = 0; j < 6; ++j) q[6 + j] = P[6 + j];
+    }
+    // the candidates pass the device check before anything the context holds is touched
+    if (int rc = layup_upload(c, t, (int64_t)c->nel * nply, nply, lay.tn)) return rc;
+    if (int rc = layup_upload(c, theta, (int64_t)c->nel * nply, nply, lay.thn)) return rc;
+    if (int rc = layup_check(c, lay.tn, lay.thn, nply)) return rc;
+    if (!(c_drill > 0.0) || !std::isfinite(c_drill)) return fail(c, "femo_set_layup: the drilling coefficient c_drill must be finite and > 0");
+    const bool entering = !c->laminate;
+    const int64_t len = (int64_t)LAM_W * c->nel;
+    if (!c->clt) HIPCHK(c, c->clt.alloc((size_t)len));
+    if (!c->clt_sym) HIPCHK(c, c->clt_sym.alloc((size_t)len));
+    if (npt > 0) {
+        HIPCHK(c, c->ply.tab.grow((size_t)PLY_W * npt * c->nel));
+        HIPCHK(c, c->ply.tabT.grow((size_t)PLY_W * npt * c->nel));
+        c->ply.npt = npt;
+    } else {
+        const double rho = c->ply.rho;
+        c->ply = femo_ctx::Ply();
+        c->ply.rho = rho;
+    }
+    HIPCHK(c, lay.pc.grow(pc.size()));
+    HIPCHK(c, hipMemcpy(lay.pc, pc.data(), pc.size() * sizeof(double), hipMemcpyHostToDevice));
+    std::swap(lay.t, lay.tn);
+    std::swap(lay.th, lay.thn);
+    lay.nply = nply; lay.surfaces = surfaces; lay.npt = npt; lay.c_drill = c_drill;
+    lay.active = true;
+    if (int rc = layup_build(c)) return rc;
+    c->laminate = true;
+    operator_changed(c, !entering);
+    ++c->opt_version;
+    return 0;
+}
+
+static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n) {
+    auto& lay = c->lay;
+    const int64_t len = (int64_t)c->nel * lay.nply;
+    if (!v) return fail(c, "null values");
+    if (n != len && n != 1) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "field '%s' has length %lld (nel x nply), got %lld", angle ? "ply_angle" : "ply_thickness", (long long)len, (long long)n);
+        return fail(c, buf);
+    }
+    DevBuf<double>& cand = angle ? lay.thn : lay.tn;
+    if (int rc = layup_upload(c, v, n, lay.nply, cand)) return rc;
+    if (int rc = layup_check(c, angle ? lay.t.get() : cand.get(), angle ? cand.get() : lay.th.get(), lay.nply)) return rc;
+    std::swap(angle ? lay.th : lay.t, cand);
+    if (int rc = layup_build(c)) return rc;
+    operator_changed(c, true);
+    ++c->opt_version;
+    return 0;
+}
+
+static int layup_get_field(femo_ctx* c, bool angle, double* v, int64_t n) {
+    auto& lay = c->lay;
+    const int64_t len = (int64_t)c->nel * lay.nply;
+    if (n != len) return fail(c, "length mismatch");
+    HIPCHK(c, lay.stage.grow((size_t)len));
+    // ply-major [k][nel] -> cell-major [e][k]: the transpose kernel with the roles of the two extents exchanged
+    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)(angle ? lay.th : lay.t), lay.stage.get(),
+                       lay.nply, c->nel);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(v, lay.stage, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int layup_public_arg(femo_ctx* c, const char* who, const char* wrt, int64_t n, int* lw) {
+    if (!c->lay.active) return fail(c, std::string(who) + ": no layup is active (femo_set_layup)");
+    *lw = layup_wrt(c, wrt ? wrt : "");
+    if (!*lw) return fail(c, std::string(who) + ": wrt is 'ply_thickness' or 'ply_angle'");
+    if (n != (int64_t)c->nel * c->lay.nply) return fail(c, std::string(who) + ": a layup vector has nel x nply entries");
+    return 0;
+}
+
+int femo_layup_jvp(femo_ctx* c, const char* wrt, int32_t ndir, const double* V, int64_t n, double* dlaminate, double* dtable) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int lw = 0;
+    if (int rc = layup_public_arg(c, "femo_layup_jvp", wrt, n, &lw)) return rc;
+    if (ndir < 1 || !V) return fail(c, "femo_layup_jvp: ndir >= 1 directions, one after the other");
+    if (dtable && c->lay.npt == 0) return fail(c, "femo_layup_jvp: the layup has no recovery points, hence no table");
+    const size_t nl = (size_t)LAM_W * c->nel, nt = (size_t)PLY_W * c->lay.npt * c->nel;
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)ndir * ((size_t)n + nl + nt)));
+    double* dl = d + (size_t)ndir * n;
+    double* dt = dl + (size_t)ndir * nl;
+    HIPCHK(c, hipMemcpy(d, V, (size_t)ndir * n * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = layup_jvp_dev(c, lw, ndir, d, dlaminate ? dl : nullptr, dtable ? dt : nullptr)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (dlaminate) HIPCHK(c, hipMemcpy(dlaminate, dl, (size_t)ndir * nl * sizeof(double), hipMemcpyDeviceToHost));
+    if (dtable) HIPCHK(c, hipMemcpy(dtable, dt, (size_t)ndir * nt * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int femo_layup_vjp(femo_ctx* c, const char* wrt, const double* laminate_bar, const double* table_bar, double* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int lw = 0;
+    if (int rc = layup_public_arg(c, "femo_layup_vjp", wrt, n, &lw)) return rc;
+    if (!out) return fail(c, "femo_layup_vjp: null output");
+    if (table_bar && c->lay.npt == 0) return fail(c, "femo_layup_vjp: the layup has no recovery points, hence no table");
+    const size_t nl = (size_t)LAM_W * c->nel, nt = (size_t)PLY_W * c->lay.npt * c->nel;
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)n + nl + nt));
+    double* dl = d + (size_t)n;
+    double* dt = dl + nl;
+    if (laminate_bar) HIPCHK(c, hipMemcpy(dl, laminate_bar, nl * sizeof(double), hipMemcpyHostToDevice));
+    if (table_bar) HIPCHK(c, hipMemcpy(dt, table_bar, nt * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, d.get(), 0.0, n);
+    if (int rc = layup_vjp_dev(c, lw, laminate_bar ? dl : nullptr, table_bar ? dt : nullptr, d)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2972,6 +3230,18 @@ static int shape_gradient_dev(femo_ctx* c, int mode, const double* w, const doub
 
 // gradient of a functional into a device buffer `out` (length n, zero-filled here)
 static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string& wrt, double* out, int64_t n) {
+    if (const int lw = layup_wrt(c, wrt)) {
+        // the composition d/dx = (d laminate / dx)^T [d/d laminate] + (d table / dx)^T [d/d ply_table], on device buffers
+        if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
+        const int64_t nl = (int64_t)LAM_W * c->nel, nt = (int64_t)PLY_W * c->lay.npt * c->nel;
+        HIPCHK(c, c->lay.lbar.grow((size_t)nl));
+        HIPCHK(c, c->lay.tbar.grow((size_t)std::max<int64_t>(nt, 1)));
+        if (int rc = dfunctional_dev(c, fn, "laminate", c->lay.lbar, nl)) return rc;
+        if (nt > 0)
+            if (int rc = dfunctional_dev(c, fn, "ply_table", c->lay.tbar, nt)) return rc;
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+        return layup_vjp_dev(c, lw, c->lay.lbar, nt > 0 ? c->lay.tbar.get() : nullptr, out);
+    }
     int64_t len;
     if (wrt == "disp_solid") len = c->ndof;
     else if (!field_ptr(c, wrt.c_str(), &len)) return fail(c, "unknown argument '" + wrt + "'");
@@ -3031,6 +3301,14 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
 }
 
 static int dRdarg_T_dev(femo_ctx* c, const std::string& arg, const double* lam, double scale, double* out, int64_t n) {
+    if (const int lw = layup_wrt(c, arg)) {                     // R sees the layup through the laminate alone
+        if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "buffer has the wrong length for '" + arg + "'");
+        const int64_t nl = (int64_t)LAM_W * c->nel;
+        HIPCHK(c, c->lay.lbar.grow((size_t)nl));
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 0.0, nl);
+        if (int rc = dRdarg_T_dev(c, "laminate", lam, scale, c->lay.lbar, nl)) return rc;
+        return layup_vjp_dev(c, lw, c->lay.lbar, nullptr, out);
+    }
     int64_t len;
     if (!field_ptr(c, arg.c_str(), &len)) return fail(c, "unknown argument '" + arg + "'");
     if (len != n) return fail(c, "buffer has the wrong length for '" + arg + "'");
@@ -3276,6 +3554,11 @@ static int jvp_check_arg(femo_ctx* c, const std::string& arg, int64_t n) {
 
 // out (ndof) = (dR/d arg) v on device vectors; jvp_prepare and jvp_check_arg have run
 static int residual_jvp_dev(femo_ctx* c, const std::string& arg, const double* v, double* out) {
+    if (const int lw = layup_wrt(c, arg)) {                     // (dR / d laminate) (d laminate / d arg) v
+        HIPCHK(c, c->lay.lbar.grow((size_t)LAM_W * c->nel));
+        if (int rc = layup_jvp_dev(c, lw, 1, v, c->lay.lbar, nullptr)) return rc;
+        return residual_jvp_dev(c, "laminate", c->lay.lbar, out);
+    }
     const int64_t n = c->ndof;
     const int vg = vec_grid(n);
     const bool lam3 = c->laminate && (arg == "thickness" || arg == "E" || arg == "nu");      // the laminate replaces them inside R
@@ -3905,6 +4188,7 @@ int femo_field_gradient_vec(femo_ctx* c, const char* functional, const char* arg
     HIPCHK(c, hipSetDevice(c->device));
     double* l = vec_by_id(c, lam);
     if (!l) return fail(c, "bad vector id");
+    if (layup_wrt(c, arg ? arg : "")) return fail(c, std::string("femo_field_gradient_vec: the gradient with respect to the layup ('") + arg + "') is not provided");
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     int rc = dfunctional_dev(c, functional ? functional : "", arg ? arg : "", d, n);
@@ -4069,6 +4353,7 @@ int femo_dist_update(femo_ctx* c, int32_t x) {
 
 // gglob (device, nglob doubles, zeroed by the caller) [sel] = - (dR/d arg)^T lambda + d functional / d arg over this rank's cells
 int femo_dist_gradient(femo_ctx* c, const char* functional, const char* arg, int32_t lam, void* gglob, int64_t nglob) {
+    if (layup_wrt(c, arg ? arg : "")) return fail(c, std::string("femo_dist_gradient: the gradient with respect to the layup ('") + arg + "') is not provided");
     if (c->laminate) return laminate_refused(c, "femo_dist_gradient");
     DIST_READY(c);
     auto& d = c->di;
@@ -4959,7 +5244,14 @@ static int field_jac_width(const femo_ctx* c, const std::string& wrt) {
     return -1;
 }
 
+// the field outputs' derivatives with respect to the layup are not provided (zeros would be wrong for the ply failure field)
+static int layup_field_refused(femo_ctx* c, const std::string& wrt) {
+    if (!layup_wrt(c, wrt)) return 0;
+    return fail(c, "the derivatives of the field outputs with respect to the layup ('" + wrt + "') are not provided");
+}
+
 static int field_arg_len(femo_ctx* c, const std::string& wrt, int64_t n) {
+    if (int rc = layup_field_refused(c, wrt)) return rc;
     int64_t len;
     if (wrt == "disp_solid") len = c->ndof;
     else if (!field_ptr(c, wrt.c_str(), &len) || field_jac_width(c, wrt) < 0) return fail(c, "unknown argument '" + wrt + "'");
@@ -5029,6 +5321,7 @@ int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wr
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
     if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
     if (wd < 0) return fail(c, "unknown argument '" + a + "'");
     if (!nnz) return fail(c, "null nnz");
@@ -5118,6 +5411,7 @@ static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
 // wrt is an argument the field `name` can be differentiated by, and n its length.  Every input of the model is accepted (zeros
 // where the field does not depend on it); the shape derivative of the ply failure field is refused like the aggregate's.
 static int field_jvp_check_arg(femo_ctx* c, const std::string& name, const std::string& wrt, int64_t n) {
+    if (int rc = layup_field_refused(c, wrt)) return rc;
     int64_t len;
     if (wrt == "disp_solid") len = c->ndof;
     else if (!field_ptr(c, wrt.c_str(), &len) || wrt == "dirichlet") return fail(c, "unknown argument '" + wrt + "'");
@@ -5267,6 +5561,19 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             if (c->laminate) ELEM_LAUNCH(c, k_diag, COMMA_LAM, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->tmp);
             else ELEM_LAUNCH(c, k_diag, NOEXTRA, nblk(c->nel, EB), EB, mesh_dev(c), fields_dev(c), c->tab, c->tmp);
             return 0;
+        }
+        // the layup kernels alone (layup.h): the build, and the pull-back of a laminate and a table cotangent to the ply thicknesses / angles
+        if (s == "layup_build" || s == "layup_vjp" || s == "layup_vjp_angle") {
+            if (!c->lay.active) return fail(c, "no layup is active (femo_set_layup)");
+            if (s == "layup_build") return layup_build(c);
+            const size_t nl = (size_t)LAM_W * c->nel, nt = (size_t)PLY_W * c->lay.npt * c->nel, nv = (size_t)c->nel * c->lay.nply;
+            if (c->lay.lbar.size() < nl || c->lay.tbar.size() < std::max<size_t>(nt, 1) || c->lay.stage.size() < nv) {
+                HIPCHK(c, c->lay.lbar.grow(nl)); HIPCHK(c, c->lay.tbar.grow(std::max<size_t>(nt, 1))); HIPCHK(c, c->lay.stage.grow(nv));
+                hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 1.0, (int64_t)nl);
+                hipLaunchKernelGGL(k_fill, dim3(vec_grid(nt)), dim3(256), 0, c->stream, c->lay.tbar.get(), 1.0, (int64_t)nt);
+            }
+            hipLaunchKernelGGL(k_fill, dim3(vec_grid(nv)), dim3(256), 0, c->stream, c->lay.stage.get(), 0.0, (int64_t)nv);
+            return layup_vjp_dev(c, s == "layup_vjp" ? 1 : 2, c->lay.lbar, nt > 0 ? c->lay.tbar.get() : nullptr, c->lay.stage);
         }
         // one application of the factor to 1 / 2 / 4 vectors (the sweeps alone: no interleaving copies); needs a factorisation
         if (s == "sweeps1" || s == "sweeps2" || s == "sweeps4") {

@@ -1,0 +1,420 @@
+// Layups on the device (include/femo_hip.h: femo_set_layup): the laminate and the ply table of every cell from ply thicknesses and
+// ply angles, with the chain rule forward and back, gfx950, fp64.
+//
+// Conventions of femo_alpha_amd/laminate.py (clt_from_plies, ply_table), followed operation by operation:
+//   plies bottom to top, interfaces z_i = sum_{j<i} t_j - H / 2, H = sum t;  angles in degrees from E0;
+//   T(theta): the strain transformation (_t_eps),  G = Q T,  Qbar = T^T Q T = T^T G,  Qsbar = R^T diag(G13, G23) R;
+//   A = sum (z1 - z0) Qbar,  B = -1/2 sum (z1^2 - z0^2) Qbar,  D = 1/3 sum (z1^3 - z0^3) Qbar,  A_s = K_SHEAR sum t Qsbar;
+//   recovery points ply by ply from the bottom, inside a ply the surfaces bot, mid, top: z_p = z0, (z0 + z1) / 2, z1.
+// Qbar and Qsbar are formed on their upper triangles and mirrored, so clt and clt_sym receive the same values.
+//
+// One thread per cell, one wave per block; no atomics -- every cell owns its outputs, so results repeat bit for bit.  The device
+// copies of t and theta are ply-major ([k][nel], as tabT, xyz and cells are stored): the 64 cells of a wave read 512 contiguous bytes
+// per ply.  The per-ply constants are the same for every cell and come through the scalar path.  Nothing is indexed by a runtime ply
+// number in registers: a first pass over the plies forms H (and its tangent), a second one everything else, and the pull-back to the
+// thicknesses runs top to bottom with a running suffix sum (d z_i / d t_j = -1/2 + [j < i]).  Vectors of the ABI (directions,
+// gradients, laminate cotangents) are cell-major; a block moves its slab of them through LDS (odd row stride), so that global
+// memory sees contiguous runs on both sides.
+#pragma once
+#include "shell_device.h"
+#include "ply_failure.h"
+
+namespace femo {
+
+constexpr int LAY_MAXPLY = 32;
+constexpr int LAY_BLOCK = 64;
+constexpr int LAY_PC = 12;                              // per ply: Q11, Q22, Q12, Q66, G13, G23, F1, F2, F11, F22, F66, F12
+constexpr int LAY_LD = 33;                              // LDS row stride (doubles) of a cell's slab: odd, >= LAY_MAXPLY and >= LAM_W
+constexpr double LAY_RAD = 0.017453292519943295;        // pi / 180 (numpy.deg2rad multiplies by this double)
+enum { LAY_T = 0, LAY_THETA = 1 };
+
+struct LayupDev {
+    const double* t;        // [nply][nel]
+    const double* th;       // [nply][nel]
+    const double* pc;       // [nply][LAY_PC]
+    int nel, nply, surfaces, npt;
+    double c_drill;
+};
+
+// upper triangle of a symmetric 3 x 3 block: 00 01 02 11 12 22
+__device__ __forceinline__ constexpr int lay_sym(int i, int j) { return i <= j ? (i == 0 ? j : i == 1 ? j + 2 : 5) : lay_sym(j, i); }
+
+__device__ __forceinline__ void lay_T(double mm, double nn, double mn, double T[3][3]) {
+    T[0][0] = mm; T[0][1] = nn; T[0][2] = mn;
+    T[1][0] = nn; T[1][1] = mm; T[1][2] = -mn;
+    T[2][0] = -2.0 * mn; T[2][1] = 2.0 * mn; T[2][2] = mm - nn;
+}
+
+// d T / d theta (per radian): d mm = -2 mn, d nn = 2 mn, d mn = mm - nn
+__device__ __forceinline__ void lay_dT(double mm, double nn, double mn, double T[3][3]) {
+    const double c2 = mm - nn, s2 = 2.0 * mn;
+    T[0][0] = -s2; T[0][1] = s2; T[0][2] = c2;
+    T[1][0] = s2; T[1][1] = -s2; T[1][2] = -c2;
+    T[2][0] = -2.0 * c2; T[2][1] = 2.0 * c2; T[2][2] = -2.0 * s2;
+}
+
+// G = Q T with Q = [[Q11, Q12, 0], [Q12, Q22, 0], [0, 0, Q66]]
+__device__ __forceinline__ void lay_QT(const double* __restrict__ pc, const double T[3][3], double G[3][3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        G[0][j] = pc[0] * T[0][j] + pc[2] * T[1][j];
+        G[1][j] = pc[2] * T[0][j] + pc[1] * T[1][j];
+        G[2][j] = pc[3] * T[2][j];
+    }
+}
+
+// upper triangle of X^T Y (+= when ADD)
+template <bool ADD>
+__device__ __forceinline__ void lay_XtY(const double X[3][3], const double Y[3][3], double U[6]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double v = X[0][i] * Y[0][j] + X[1][i] * Y[1][j] + X[2][i] * Y[2][j];
+            if (ADD) U[lay_sym(i, j)] += v; else U[lay_sym(i, j)] = v;
+        }
+}
+
+struct LayPly {
+    double mm, nn, mn;
+    double G[3][3];         // Q T
+    double Qb[6];           // T^T Q T, upper triangle
+    double Qs[3];           // R^T diag(G13, G23) R: 00 01 11
+};
+
+__device__ __forceinline__ void lay_ply(const double* __restrict__ pc, double theta, LayPly& P) {
+    double s, c;
+    sincos(theta * LAY_RAD, &s, &c);
+    P.mm = c * c; P.nn = s * s; P.mn = c * s;
+    double T[3][3];
+    lay_T(P.mm, P.nn, P.mn, T);
+    lay_QT(pc, T, P.G);
+    lay_XtY<false>(T, P.G, P.Qb);
+    P.Qs[0] = P.mm * pc[4] + P.nn * pc[5];
+    P.Qs[1] = P.mn * pc[4] - P.mn * pc[5];
+    P.Qs[2] = P.nn * pc[4] + P.mm * pc[5];
+}
+
+// derivatives per radian of G, Qbar (upper triangle) and Qsbar of a ply lay_ply has formed
+__device__ __forceinline__ void lay_dply(const double* __restrict__ pc, const LayPly& P, double dG[3][3], double dQb[6], double dQs[3]) {
+    double T[3][3], dT[3][3];
+    lay_T(P.mm, P.nn, P.mn, T);
+    lay_dT(P.mm, P.nn, P.mn, dT);
+    lay_QT(pc, dT, dG);
+    lay_XtY<false>(dT, P.G, dQb);
+    lay_XtY<true>(T, dG, dQb);
+    const double c2 = P.mm - P.nn, s2 = 2.0 * P.mn, dg = pc[4] - pc[5];
+    dQs[0] = -s2 * dg;
+    dQs[1] = c2 * dg;
+    dQs[2] = s2 * dg;
+}
+
+// weights (a, b) of z_p = a z0 + b z1 for the surface bit 1 (bot), 2 (mid), 4 (top)
+__device__ __forceinline__ double lay_wa(int bit) { return bit == 1 ? 1.0 : bit == 2 ? 0.5 : 0.0; }
+__device__ __forceinline__ double lay_wb(int bit) { return bit == 1 ? 0.0 : bit == 2 ? 0.5 : 1.0; }
+
+// a block's slab of a cell-major vector (w entries per cell) into / out of LDS rows of stride LAY_LD
+__device__ __forceinline__ void lay_slab_in(double* __restrict__ sh, const double* __restrict__ src, int nel, int w) {
+    const int e0 = blockIdx.x * LAY_BLOCK;
+    const int cnt = min(LAY_BLOCK, nel - e0) * w;
+    const double* s = src + (size_t)e0 * w;
+    for (int i = threadIdx.x; i < cnt; i += LAY_BLOCK) sh[(i / w) * LAY_LD + i % w] = s[i];
+}
+
+__device__ __forceinline__ void lay_slab_add(const double* __restrict__ sh, double* __restrict__ dst, int nel, int w) {
+    const int e0 = blockIdx.x * LAY_BLOCK;
+    const int cnt = min(LAY_BLOCK, nel - e0) * w;
+    double* d = dst + (size_t)e0 * w;
+    for (int i = threadIdx.x; i < cnt; i += LAY_BLOCK) d[i] += sh[(i / w) * LAY_LD + i % w];
+}
+
+__device__ __forceinline__ void lay_slab_out(const double* __restrict__ sh, double* __restrict__ dst, int nel, int w) {
+    const int e0 = blockIdx.x * LAY_BLOCK;
+    const int cnt = min(LAY_BLOCK, nel - e0) * w;
+    double* d = dst + (size_t)e0 * w;
+    for (int i = threadIdx.x; i < cnt; i += LAY_BLOCK) d[i] = sh[(i / w) * LAY_LD + i % w];
+}
+
+// first offending (cell, ply, which) of a layup, encoded (cell * LAY_MAXPLY + ply) * 2 + (0: thickness, 1: angle); one slot per block
+constexpr long long LAY_OK = 0x7fffffffffffffffLL;
+
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_check(const double* __restrict__ t, const double* __restrict__ th, int nel, int nply, long long* __restrict__ slots) {
+    __shared__ long long s[LAY_BLOCK];
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    long long code = LAY_OK;
+    if (e < nel)
+        for (int k = nply - 1; k >= 0; --k) {
+            const double tk = t[(size_t)k * nel + e], ak = th[(size_t)k * nel + e];
+            if (!isfinite(ak)) code = ((long long)e * LAY_MAXPLY + k) * 2 + 1;
+            if (!(tk > 0.0) || !isfinite(tk)) code = ((long long)e * LAY_MAXPLY + k) * 2;
+        }
+    s[threadIdx.x] = code;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < LAY_BLOCK; ++i) code = s[i] < code ? s[i] : code;
+        slots[blockIdx.x] = code;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_layup_first(const long long* __restrict__ slots, int n, long long* __restrict__ out) {
+    __shared__ long long s[256];
+    long long code = LAY_OK;
+    for (int i = threadIdx.x; i < n; i += 256) code = slots[i] < code ? slots[i] : code;
+    s[threadIdx.x] = code;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w && s[threadIdx.x + w] < s[threadIdx.x]) s[threadIdx.x] = s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = s[0];
+}
+
+// laminate (clt and clt_sym, cell-major LAM_W) and, with recovery points, the table (tab cell-major, tabT entry-major)
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_build(LayupDev L, double* __restrict__ clt, double* __restrict__ clt_sym, double* __restrict__ tab, double* __restrict__ tabT) {
+    __shared__ double sh[LAY_BLOCK * LAY_LD];
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    const size_t nel = (size_t)L.nel;
+    if (e < L.nel) {
+        double H = 0.0;
+        for (int k = 0; k < L.nply; ++k) H += L.t[k * nel + e];
+        double A[6], B[6], D[6], S[3];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) A[i] = B[i] = D[i] = 0.0;
+        S[0] = S[1] = S[2] = 0.0;
+        double cs = 0.0, z0 = -0.5 * H;
+        int p = 0;
+        for (int k = 0; k < L.nply; ++k) {
+            const double* pc = L.pc + k * LAY_PC;
+            const double tk = L.t[k * nel + e];
+            LayPly P;
+            lay_ply(pc, L.th[k * nel + e], P);
+            cs += tk;
+            const double z1 = cs - 0.5 * H;
+            const double a = z1 - z0, b = -0.5 * (z1 * z1 - z0 * z0), d = (z1 * z1 * z1 - z0 * z0 * z0) / 3.0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) { A[i] += a * P.Qb[i]; B[i] += b * P.Qb[i]; D[i] += d * P.Qb[i]; }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) S[i] += K_SHEAR * tk * P.Qs[i];
+            for (int bit = 1; bit <= 4; bit <<= 1) {
+                if (!(L.surfaces & bit)) continue;
+                const double zp = lay_wa(bit) * z0 + lay_wb(bit) * z1;
+                double* row = tab + ((size_t)e * L.npt + p) * PLY_W;
+                double* col = tabT + (size_t)p * PLY_W * nel + e;
+#pragma unroll
+                for (int j = 0; j < PLY_W; ++j) {
+                    const double v = j < 9 ? P.G[j / 3][j % 3] : j == 9 ? zp : pc[6 + (j - 10)];
+                    row[j] = v;
+                    col[j * nel] = v;
+                }
+                ++p;
+            }
+            z0 = z1;
+        }
+        double* r = sh + threadIdx.x * LAY_LD;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                r[3 * i + j] = A[lay_sym(i, j)];
+                r[9 + 3 * i + j] = B[lay_sym(i, j)];
+                r[18 + 3 * i + j] = D[lay_sym(i, j)];
+            }
+        r[27] = S[0]; r[28] = S[1]; r[29] = S[1]; r[30] = S[2];
+        r[31] = L.c_drill;
+    }
+    __syncthreads();
+    lay_slab_out(sh, clt, L.nel, LAM_W);
+    lay_slab_out(sh, clt_sym, L.nel, LAM_W);
+}
+
+// Directions to tangents: V (ndir x nel nply, cell-major; direction blockIdx.y) -> dlam (ndir x LAM_W nel) and dtab (ndir x 16 npt nel,
+// cell-major); either output may be null.  Angle directions are per degree; c_drill is a constant (entry 31: zero).
+template <int WRT>
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_jvp(LayupDev L, const double* __restrict__ V, double* __restrict__ dlam, double* __restrict__ dtab) {
+    __shared__ double sh[LAY_BLOCK * LAY_LD];
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    const size_t nel = (size_t)L.nel;
+    const size_t dir = blockIdx.y;
+    lay_slab_in(sh, V + dir * nel * L.nply, L.nel, L.nply);
+    __syncthreads();
+    double A[6], B[6], D[6], S[3];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) A[i] = B[i] = D[i] = 0.0;
+    S[0] = S[1] = S[2] = 0.0;
+    if (e < L.nel) {
+        const double* v = sh + threadIdx.x * LAY_LD;
+        double* dt_row = dtab ? dtab + (dir * nel + e) * (size_t)L.npt * PLY_W : nullptr;
+        double H = 0.0, dH = 0.0;
+        for (int k = 0; k < L.nply; ++k) { H += L.t[k * nel + e]; dH += v[k]; }
+        double cs = 0.0, dcs = 0.0, z0 = -0.5 * H, dz0 = -0.5 * dH;
+        int p = 0;
+        for (int k = 0; k < L.nply; ++k) {
+            const double* pc = L.pc + k * LAY_PC;
+            const double tk = L.t[k * nel + e];
+            LayPly P;
+            lay_ply(pc, L.th[k * nel + e], P);
+            cs += tk;
+            const double z1 = cs - 0.5 * H;
+            if (WRT == LAY_T) {
+                dcs += v[k];
+                const double dz1 = dcs - 0.5 * dH;
+                const double a = dz1 - dz0, b = -(z1 * dz1 - z0 * dz0), d = z1 * z1 * dz1 - z0 * z0 * dz0;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { A[i] += a * P.Qb[i]; B[i] += b * P.Qb[i]; D[i] += d * P.Qb[i]; }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) S[i] += K_SHEAR * v[k] * P.Qs[i];
+                for (int bit = 1; bit <= 4; bit <<= 1) {
+                    if (!(L.surfaces & bit)) continue;
+                    if (dt_row) {
+#pragma unroll
+                        for (int j = 0; j < PLY_W; ++j) dt_row[p * PLY_W + j] = j == 9 ? lay_wa(bit) * dz0 + lay_wb(bit) * dz1 : 0.0;
+                    }
+                    ++p;
+                }
+                dz0 = dz1;
+            } else {
+                double dG[3][3], dQb[6], dQs[3];
+                lay_dply(pc, P, dG, dQb, dQs);
+                const double r = LAY_RAD * v[k];
+                const double a = (z1 - z0) * r, b = -0.5 * (z1 * z1 - z0 * z0) * r, d = (z1 * z1 * z1 - z0 * z0 * z0) / 3.0 * r;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { A[i] += a * dQb[i]; B[i] += b * dQb[i]; D[i] += d * dQb[i]; }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) S[i] += K_SHEAR * tk * r * dQs[i];
+                for (int bit = 1; bit <= 4; bit <<= 1) {
+                    if (!(L.surfaces & bit)) continue;
+                    if (dt_row) {
+#pragma unroll
+                        for (int j = 0; j < PLY_W; ++j) dt_row[p * PLY_W + j] = j < 9 ? r * dG[j / 3][j % 3] : 0.0;
+                    }
+                    ++p;
+                }
+            }
+            z0 = z1;
+        }
+    }
+    if (!dlam) return;
+    __syncthreads();                                     // the directions have been read: the slab now carries the laminate tangents
+    if (e < L.nel) {
+        double* r = sh + threadIdx.x * LAY_LD;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                r[3 * i + j] = A[lay_sym(i, j)];
+                r[9 + 3 * i + j] = B[lay_sym(i, j)];
+                r[18 + 3 * i + j] = D[lay_sym(i, j)];
+            }
+        r[27] = S[0]; r[28] = S[1]; r[29] = S[1]; r[30] = S[2];
+        r[31] = 0.0;
+    }
+    __syncthreads();
+    lay_slab_out(sh, dlam + dir * nel * LAM_W, L.nel, LAM_W);
+}
+
+// Cotangents back: out (nel nply, cell-major) += J^T (lbar, tbar); lbar (LAM_W nel) and tbar (16 npt nel), cell-major, either may be
+// null.  Angle gradients are per degree.
+template <int WRT>
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_vjp(LayupDev L, const double* __restrict__ lbar, const double* __restrict__ tbar, double* __restrict__ out) {
+    __shared__ double sh[LAY_BLOCK * LAY_LD];
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    const size_t nel = (size_t)L.nel;
+    // the cotangents of the symmetric blocks folded onto their upper triangles
+    double Ab[6], Bb[6], Db[6], Sb[3];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Ab[i] = Bb[i] = Db[i] = 0.0;
+    Sb[0] = Sb[1] = Sb[2] = 0.0;
+    if (lbar) {
+        lay_slab_in(sh, lbar, L.nel, LAM_W);
+        __syncthreads();
+        const double* r = sh + threadIdx.x * LAY_LD;
+        if (e < L.nel) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    Ab[lay_sym(i, j)] += r[3 * i + j];
+                    Bb[lay_sym(i, j)] += r[9 + 3 * i + j];
+                    Db[lay_sym(i, j)] += r[18 + 3 * i + j];
+                }
+            Sb[0] = r[27]; Sb[1] = r[28] + r[29]; Sb[2] = r[30];
+        }
+        __syncthreads();                                 // the slab now collects the cell's gradient
+    }
+    if (e < L.nel) {
+        double* g = sh + threadIdx.x * LAY_LD;
+        const double* tb = tbar && L.npt > 0 ? tbar + (size_t)e * L.npt * PLY_W : nullptr;
+        const int ns = L.npt / L.nply;
+        double H = 0.0;
+        for (int k = 0; k < L.nply; ++k) H += L.t[k * nel + e];
+        if (WRT == LAY_T) {
+            // top to bottom: sfx = sum of the interface cotangents above the ply's own thickness, d z_i / d t_j = -1/2 + [j < i]
+            double cs = H, sfx = 0.0;
+            for (int k = L.nply - 1; k >= 0; --k) {
+                const double* pc = L.pc + k * LAY_PC;
+                const double tk = L.t[k * nel + e];
+                LayPly P;
+                lay_ply(pc, L.th[k * nel + e], P);
+                const double z1 = cs - 0.5 * H;
+                cs -= tk;
+                const double z0 = (k == 0 ? 0.0 : cs) - 0.5 * H;
+                double a = 0.0, b = 0.0, d = 0.0;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { a += Ab[i] * P.Qb[i]; b += Bb[i] * P.Qb[i]; d += Db[i] * P.Qb[i]; }
+                const double s = Sb[0] * P.Qs[0] + Sb[1] * P.Qs[1] + Sb[2] * P.Qs[2];
+                double up = a - z1 * b + z1 * z1 * d, lo = -a + z0 * b - z0 * z0 * d;
+                if (tb) {
+                    int p = k * ns;
+                    for (int bit = 1; bit <= 4; bit <<= 1) {
+                        if (!(L.surfaces & bit)) continue;
+                        const double zb = tb[p * PLY_W + 9];
+                        lo += lay_wa(bit) * zb;
+                        up += lay_wb(bit) * zb;
+                        ++p;
+                    }
+                }
+                sfx += up;
+                g[k] = sfx + K_SHEAR * s;
+                sfx += lo;
+            }
+            for (int k = 0; k < L.nply; ++k) g[k] -= 0.5 * sfx;       // sfx: the sum over every interface
+        } else {
+            double cs = 0.0, z0 = -0.5 * H;
+            int p = 0;
+            for (int k = 0; k < L.nply; ++k) {
+                const double* pc = L.pc + k * LAY_PC;
+                const double tk = L.t[k * nel + e];
+                LayPly P;
+                lay_ply(pc, L.th[k * nel + e], P);
+                double dG[3][3], dQb[6], dQs[3];
+                lay_dply(pc, P, dG, dQb, dQs);
+                cs += tk;
+                const double z1 = cs - 0.5 * H;
+                double a = 0.0, b = 0.0, d = 0.0;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { a += Ab[i] * dQb[i]; b += Bb[i] * dQb[i]; d += Db[i] * dQb[i]; }
+                const double s = Sb[0] * dQs[0] + Sb[1] * dQs[1] + Sb[2] * dQs[2];
+                double acc = (z1 - z0) * a - 0.5 * (z1 * z1 - z0 * z0) * b + (z1 * z1 * z1 - z0 * z0 * z0) / 3.0 * d + K_SHEAR * tk * s;
+                for (int bit = 1; bit <= 4; bit <<= 1) {
+                    if (!(L.surfaces & bit)) continue;
+                    if (tb) {
+#pragma unroll
+                        for (int j = 0; j < 9; ++j) acc += tb[p * PLY_W + j] * dG[j / 3][j % 3];
+                    }
+                    ++p;
+                }
+                g[k] = LAY_RAD * acc;
+                z0 = z1;
+            }
+        }
+    }
+    __syncthreads();
+    lay_slab_add(sh, out, L.nel, L.nply);
+}
+
+}  // namespace femo

@@ -21,14 +21,15 @@ from ..mesh_io import readFEAMesh, reconstructFEAMesh            # noqa: F401  (
 
 class FunctionSpace:
     """kind: 'W' (CG2xCG1 state), 'VT' (thickness-like scalars), 'VF' (pressure), 'VU' (mesh motion), 'VL' (the laminate: DG0,
-    32 values per cell, femo_set_laminate), 'VP' (the ply table: DG0, ``width`` = 16 npt values per cell, femo_set_ply_table)."""
+    32 values per cell, femo_set_laminate), 'VP' (the ply table: DG0, ``width`` = 16 npt values per cell, femo_set_ply_table), 'VY' (a
+    layup input, ply thicknesses or ply angles: DG0, ``width`` = nply values per cell, femo_set_layup)."""
 
     def __init__(self, ctx: ShellContext, kind: str, width=None):
         self.ctx, self.kind = ctx, kind
         m = ctx.mesh
         self.dim = {"W": m.ndof, "VT": m.nel if ctx.element_wise_material else m.nn,
                     "VF": 3 * (m.nel if ctx.elementwise_pressure else m.nn), "VU": 3 * m.nn, "VL": 32 * m.nel,
-                    "VP": (width or 0) * m.nel}[kind]
+                    "VP": (width or 0) * m.nel, "VY": (width or 0) * m.nel}[kind]
 
 
 class Function:
@@ -360,7 +361,7 @@ class FEA:
         one = V.ndim == 1
         V = V.reshape(1, -1) if one else V.reshape(V.shape[0], -1)
         space = self.inputs_dict[arg_name]["function_space"]
-        per_cell = space.kind in ("VL", "VP") or (space.kind == "VT" and ctx.element_wise_material) \
+        per_cell = space.kind in ("VL", "VP", "VY") or (space.kind == "VT" and ctx.element_wise_material) \
             or (space.kind == "VF" and ctx.elementwise_pressure)
         idx = self.cell_of_new if per_cell else self.vertex_of_new
         if idx is not None:

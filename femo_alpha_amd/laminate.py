@@ -100,6 +100,57 @@ def _dz_interfaces(nply):
     return -0.5 + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)
 
 
+def _dt_eps(theta_deg):
+    """d T / d theta of ``_t_eps``, per radian, (..., 3, 3)."""
+    th = np.deg2rad(np.asarray(theta_deg, dtype=np.float64))
+    c2, s2 = np.cos(2 * th), np.sin(2 * th)
+    dT = np.empty(th.shape + (3, 3))
+    dT[..., 0, 0], dT[..., 0, 1], dT[..., 0, 2] = -s2, s2, c2
+    dT[..., 1, 0], dT[..., 1, 1], dT[..., 1, 2] = s2, -s2, -c2
+    dT[..., 2, 0], dT[..., 2, 1], dT[..., 2, 2] = -2 * c2, 2 * c2, -2 * s2
+    return dT
+
+
+def ply_stiffness_dtheta(E1, E2, G12, nu12, G13, G23, theta):
+    """d Qbar / d theta (..., 3, 3) and d Qsbar / d theta (..., 2, 2) of ``ply_stiffness``, per degree."""
+    E1, E2, G12, nu12, G13, G23 = (np.asarray(x, dtype=np.float64) for x in (E1, E2, G12, nu12, G13, G23))
+    shape = np.broadcast(E1, E2, G12, nu12, G13, G23, np.asarray(theta)).shape
+    Q, Qs = ply_stiffness(E1, E2, G12, nu12, G13, G23, np.zeros(shape))          # theta = 0: the ply-axis stiffnesses
+    T = np.broadcast_to(_t_eps(theta), shape + (3, 3))
+    dT = np.broadcast_to(_dt_eps(theta), shape + (3, 3))
+    th = np.broadcast_to(np.deg2rad(np.asarray(theta, dtype=np.float64)), shape)
+    m, n = np.cos(th), np.sin(th)
+    R = np.broadcast_to(_r_shear(theta), shape + (2, 2))
+    dR = np.empty(shape + (2, 2))
+    dR[..., 0, 0], dR[..., 0, 1], dR[..., 1, 0], dR[..., 1, 1] = -n, m, -m, -n
+    dQb = np.einsum("...ki,...kl,...lj->...ij", dT, Q, T) + np.einsum("...ki,...kl,...lj->...ij", T, Q, dT)
+    dQs = np.einsum("...ki,...kl,...lj->...ij", dR, Qs, R) + np.einsum("...ki,...kl,...lj->...ij", R, Qs, dR)
+    return np.deg2rad(1.0) * dQb, np.deg2rad(1.0) * dQs
+
+
+def clt_dtheta(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR):
+    """(dA, dB, dD, dA_s): the derivatives of ``clt_from_plies`` with respect to the ply angles, per degree, shapes
+    (nel, nply, 3, 3) x 3 and (nel, nply, 2, 2) -- entry [e, k] is the derivative with respect to the angle of ply k of cell e.
+    Arguments as for ``clt_from_plies``."""
+    args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, G13, G23, t, theta)]
+    E1, E2, G12, nu12, G13, G23, t, theta = np.broadcast_arrays(*args)
+    dQb, dQs = ply_stiffness_dtheta(E1, E2, G12, nu12, G13, G23, theta)
+    H = t.sum(axis=1, keepdims=True)
+    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H
+    z0, z1 = z[:, :-1], z[:, 1:]
+    w = lambda x: x[:, :, None, None]
+    return w(z1 - z0) * dQb, -0.5 * w(z1 ** 2 - z0 ** 2) * dQb, w(z1 ** 3 - z0 ** 3) * dQb / 3.0, k_shear * w(t) * dQs
+
+
+def ply_table_dtheta(E1, E2, G12, nu12, theta):
+    """d G / d theta (nel, nply, 3, 3), per degree, of the G = Q T(theta) that ``ply_table`` stores at every recovery point of a
+    ply: the only entries of the table that depend on the ply angles.  Ply arguments as for ``ply_table``."""
+    args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, theta)]
+    E1, E2, G12, nu12, theta = np.broadcast_arrays(*args)
+    Q, _ = ply_stiffness(E1, E2, G12, nu12, G12, G12, np.zeros_like(theta))
+    return np.deg2rad(1.0) * np.einsum("ekil,eklj->ekij", Q, _dt_eps(theta))
+
+
 def tsai_wu(Xt, Xc, Yt, Yc, S, f12=-0.5):
     """The six coefficients (F1, F2, F11, F22, F66, F12) of the Tsai-Wu failure index
     FI = F1 s1 + F2 s2 + F11 s1^2 + F22 s2^2 + F66 t12^2 + 2 F12 s1 s2 from the ply strengths (all positive: tension / compression

@@ -67,7 +67,7 @@ def createCustomMeasure(mesh: ShellMesh, dim, SubdomainFunc, measure: str, tag: 
 class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
-                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None):
+                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -106,6 +106,20 @@ class RMShellModel:
         self.ply_failure = None if ply_failure is None else int(ply_failure)
         if self.ply_failure is not None and not self.laminate:
             raise ValueError("ply_failure needs laminate=True")
+        # layup=dict(plies, t, theta[, surfaces, c_drill]) (with laminate=True; ShellContext.set_layup): the design variables of the
+        # laminate are the inputs "ply_thickness" and "ply_angle", (nel, nply) in caller cell order, and the laminate and the ply table
+        # are built from them on the device.  t and theta give the initial layup ((nply,) or (nel, nply) in caller cell order); with
+        # recovery points (surfaces, default bot / top of every ply) the output "ply_failure" exists.  They take the place of the
+        # laminate= and ply_table= arguments of evaluate and of ply_failure=npt here.
+        self.layup = None
+        if layup is not None:
+            if not self.laminate or self.ply_failure is not None:
+                raise ValueError("layup needs laminate=True, and its surfaces take the place of ply_failure=npt")
+            t, theta = (np.asarray(layup[k], dtype=np.float64) for k in ("t", "theta"))
+            nply = t.shape[-1] if t.ndim else 1
+            to_solver = lambda a: np.broadcast_to(a.reshape(-1, nply), (mesh.nel, nply))[self.cell_of_new]
+            self.layup = dict(layup, t=to_solver(t), theta=to_solver(theta))
+            self.nply = nply
         # n x n Gauss points per quadrilateral for the static forms (2..5).  The reference leaves the degree to UFL's
         # estimate, which on quadrilaterals comes out near 47 (scripts/ufl_degree_estimate.py): exact integration.  Default:
         # what the mesh asks for -- 4 on affine cells (exact there), 5 as soon as one cell is warped (within 1e-9 of the
@@ -150,7 +164,8 @@ class RMShellModel:
         mesh = self.mesh
         shell_pde = self.shell_pde = RMShellPDE(mesh, element_wise_material=self.element_wise_material,
                                                 elementwise_pressure=self.elementwise_pressure, device=self.device,
-                                                nquad=self._nquad_arg, laminate=self.laminate, ply_failure=self.ply_failure)
+                                                nquad=self._nquad_arg, laminate=self.laminate, ply_failure=self.ply_failure,
+                                                layup=self.layup)
         fea = FEA(mesh)
         if self.caller_mesh is not mesh:                 # renumbered: FEA.field_tangents answers in caller order
             fea.vertex_of_new, fea.cell_of_new = self.vertex_of_new, self.cell_of_new
@@ -182,7 +197,13 @@ class RMShellModel:
         fea.add_input("density", density, init_val=1.0)
         fea.add_input("uhat", uhat, init_val=0.0)
         lam_args = []
-        if self.laminate:
+        if self.layup is not None:
+            ply_t = Function(shell_pde.VY).bind("ply_thickness")
+            ply_a = Function(shell_pde.VY).bind("ply_angle")
+            fea.add_input("ply_thickness", ply_t, init_val=shell_pde.ply_thickness_init)
+            fea.add_input("ply_angle", ply_a, init_val=shell_pde.ply_angle_init)
+            lam_args = ["ply_thickness", "ply_angle"]
+        elif self.laminate:
             lam = Function(shell_pde.VL).bind("laminate")
             fea.add_input("laminate", lam, init_val=shell_pde.laminate_init)
             lam_args = ["laminate"]
@@ -192,6 +213,8 @@ class RMShellModel:
         fea.add_output(name="mass", form=mass_form, arguments=["thickness", "density", "uhat"])
         fea.add_output(name="elastic_energy", form=elastic_energy_form, arguments=["thickness", "disp_solid", "E", "uhat"] + lam_args)
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
+        if self.layup is not None and shell_pde.ply_npt:
+            fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, None, rho=self.rho), arguments=["disp_solid"] + lam_args)
         if self.ply_failure is not None:
             ply = Function(shell_pde.VP).bind("ply_table")
             fea.add_input("ply_table", ply, init_val=shell_pde.ply_table_init)
@@ -205,6 +228,8 @@ class RMShellModel:
                                arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         fea.add_field_output(name="stress", form=stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"],
                              function_space=("DG", 1), record=False, vtk=True)
+        if self.layup is not None and shell_pde.ply_npt:
+            self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, None)
         if self.ply_failure is not None:
             # (nel, npt) flattened; a diagnostic with forward-mode tangents only (FEA.field_tangents), so it is not registered as a
             # field output of the CSDL model, whose operations differentiate in reverse
@@ -212,11 +237,17 @@ class RMShellModel:
         self.fea = fea
 
     def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None,
-                 ply_table=None):
+                 ply_table=None, ply_thickness=None, ply_angle=None):
         """laminate: (nel, 32) per cell in caller order -- required with laminate=True, refused otherwise.  thickness, E, nu and density
         stay inputs in laminate mode (mass, regularisation, stress outputs).  ply_table: (nel, npt, 16) per cell in caller order --
-        required with ply_failure=npt, refused otherwise."""
-        if self.laminate != (laminate is not None):
+        required with ply_failure=npt, refused otherwise.  With layup=...: ply_thickness and ply_angle, (nel, nply) in caller cell
+        order, are required, and laminate / ply_table are refused."""
+        if (self.layup is not None) != (ply_thickness is not None and ply_angle is not None) or \
+                (self.layup is None and (ply_thickness is not None or ply_angle is not None)):
+            raise ValueError("ply_thickness and ply_angle are required with layup=... and refused without it")
+        if self.layup is not None and (laminate is not None or ply_table is not None):
+            raise ValueError("with layup=... the laminate and the ply table are built from ply_thickness and ply_angle")
+        if self.layup is None and self.laminate != (laminate is not None):
             raise ValueError("a laminate is required with laminate=True and refused without it")
         if (self.ply_failure is not None) != (ply_table is not None):
             raise ValueError("a ply_table is required with ply_failure=npt and refused without it")
@@ -248,7 +279,12 @@ class RMShellModel:
         shell_inputs.uhat = reshaped_node_disp
         for n in ("thickness", "E", "nu", "density"):
             getattr(shell_inputs, n).add_name(n)
-        if self.laminate:
+        if self.layup is not None:
+            shell_inputs.ply_thickness = ply_thickness[self.cell_of_new].reshape((-1,))      # caller cell order -> solver order
+            shell_inputs.ply_thickness.add_name("ply_thickness")
+            shell_inputs.ply_angle = ply_angle[self.cell_of_new].reshape((-1,))
+            shell_inputs.ply_angle.add_name("ply_angle")
+        elif self.laminate:
             shell_inputs.laminate = laminate[self.cell_of_new].reshape((-1,))      # caller cell order -> solver order
             shell_inputs.laminate.add_name("laminate")
         if self.ply_failure is not None:

@@ -23,7 +23,7 @@ class FacetSet:
 
 class RMShellPDE:
     def __init__(self, mesh, element_wise_material=False, elementwise_pressure=False, nquad=None, device=0, solver="direct",
-                 element_type=None, laminate=False, ply_failure=None):
+                 element_type=None, laminate=False, ply_failure=None, layup=None):
         # element_type: 'CG2CG1' (what the reference's RMShellPDE hard-codes, rm_shell_pde.py:27) or 'CG1CG1' (the other quadrilateral /
         # triangle choice of ShellElement.setUpFunctionSpace, linear_shell_model.py:74-79); None: the element the mesh object carries
         if element_type is not None and element_type != mesh.element:
@@ -48,6 +48,24 @@ class RMShellPDE:
         # one-ply placeholder (1 mm of a unit-modulus isotropic ply) that the model's "laminate" input replaces.
         self.laminate = bool(laminate)
         self.VL = None
+        # layup=dict(plies, t, theta[, surfaces, c_drill]) (laminate mode; ShellContext.set_layup, solver cell order): the laminate and
+        # the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the recovery
+        # points, hence "ply_failure", follow from the layup's surfaces
+        self.layup = layup
+        self.VY = None
+        if layup is not None:
+            if not self.laminate or ply_failure is not None:
+                raise ValueError("layup needs laminate=True, and its surfaces take the place of ply_failure=npt")
+            t = np.asarray(layup["t"], dtype=np.float64)
+            nply = t.shape[-1] if t.ndim else 1
+            surfaces = tuple(layup.get("surfaces", ("bot", "top")))
+            self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"))
+            self.VY = FunctionSpace(self.ctx, "VY", width=nply)
+            self.ply_thickness_init = self.ctx.get_field("ply_thickness")
+            self.ply_angle_init = self.ctx.get_field("ply_angle")
+            self.ply_npt = nply * len(surfaces) or None
+            self.VP = None
+            return
         if self.laminate:
             from ..laminate import isotropic
             self.VL = FunctionSpace(self.ctx, "VL")

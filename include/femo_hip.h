@@ -68,7 +68,8 @@ void femo_destroy(femo_ctx* ctx);
 
 int64_t femo_ndof(const femo_ctx* ctx);
 /* Length of an input field: "thickness","E","nu","density" (nn or nel), "F_solid" (3*nn or 3*nel), "uhat" (3*nn),
- * "laminate" (32*nel, laminate mode only; -1 otherwise), "ply_table" (16*npt*nel once femo_set_ply_table has set one; -1 otherwise). */
+ * "laminate" (32*nel, laminate mode only; -1 otherwise), "ply_table" (16*npt*nel once femo_set_ply_table has set one; -1 otherwise),
+ * "ply_thickness", "ply_angle" (nel*nply while a layup is active, femo_set_layup; -1 otherwise). */
 int64_t femo_field_size(const femo_ctx* ctx, const char* name);
 
 /* Dirichlet data.
@@ -146,6 +147,41 @@ int femo_set_laminate(femo_ctx* ctx, const double* clt, int64_t n);
 int femo_set_ply_table(femo_ctx* ctx, const double* table, int32_t npt, int64_t n);
 int femo_set_ply_failure_params(femo_ctx* ctx, double rho);
 int femo_ply_failure_field(femo_ctx* ctx, double* out, int64_t n);
+
+/* Layups: the laminate and the ply table built on the device from the design variables of a laminate, ply thicknesses and ply angles
+ * (femo_alpha_amd/csrc/layup.h) -- new; the conventions are those of femo_alpha_amd/laminate.py (clt_from_plies, ply_table):
+ *   - nply plies (1..32), listed bottom to top along the cell normal, the same materials in every cell: plies is nply x 12,
+ *     [E1, E2, G12, nu12, G13, G23, F1, F2, F11, F22, F66, F12] (F*: the Tsai-Wu coefficients of laminate.tsai_wu);
+ *   - t and theta: nel x nply, cell-major; interfaces z_i = sum_{j<i} t_j - H / 2; angles in degrees from E0 toward E1;
+ *   - A = sum (z1 - z0) Qbar, B = -1/2 sum (z1^2 - z0^2) Qbar, D = 1/3 sum (z1^3 - z0^3) Qbar, A_s = 0.833 sum t Qsbar, and
+ *     c_drill (> 0), a constant of the mode that every derivative holds fixed;
+ *   - surfaces: a mask of 1 (bot), 2 (mid), 4 (top) of every ply; the recovery points run ply by ply from the bottom, inside a ply in
+ *     the order bot, mid, top, G = Q T(theta); nply x popcount(surfaces) <= 32.  0: no recovery points -- no ply table, and
+ *     "ply_failure" answers as it does without one.
+ * femo_set_layup enters laminate mode if needed (transient operators are refused as by femo_set_laminate).  The per-ply constants are
+ * checked on the host (finite, moduli > 0, 1 - nu12^2 E2 / E1 > 0), t > 0 and finite values on the device: the error names the first
+ * offending cell and ply.  A refused call changes nothing.  Valid plies give a positive definite laminate, so no block is factorised.
+ * While a layup is active:
+ *   - "ply_thickness" and "ply_angle" are fields of nel x nply values (femo_field_size, femo_set_field, femo_get_field; cell-major);
+ *     setting either rebuilds the laminate and the table on the stream, and the next solve re-factorises.  femo_device_ptr returns the
+ *     device copies, which are ply-major ([k][nel]).  Outside the mode both names are unknown (femo_field_size: -1);
+ *   - femo_get_field "laminate" / "ply_table" return what was built (symmetric blocks); femo_set_laminate with values, femo_set_ply_table
+ *     and femo_set_field of "laminate" / "ply_table" are refused with a message that names femo_set_layup;
+ *   - both names are arguments of femo_dfunctional, femo_dRdarg_T, femo_residual_jvp, femo_total_gradient(s) and femo_total_jvp, by
+ *     d/dx = (d laminate/dx)^T [d/d laminate] + (d table/dx)^T [d/d ply_table] (or its forward counterpart), composed on the device.
+ *     Angle derivatives are per degree;
+ *   - not provided: the derivatives of the field outputs with respect to the layup (femo_field_output_vjp / _jvp / _jacobian,
+ *     femo_field_total_gradients / _jvp, femo_field_gradient_vec and femo_dist_gradient refuse both names), mass and regularisation
+ *     from the layup (they keep the "thickness" and "density" fields), per-cell ply materials, the multi-GPU driver and transient
+ *     laminates.
+ * femo_set_layup(ctx, 0, NULL, 0, 0, NULL, NULL) leaves the mode and keeps the last laminate and table as ordinary values;
+ * femo_set_laminate(ctx, NULL, 0) drops the layup together with the laminate.
+ * femo_layup_jvp: ndir directions V (ndir x n, n = nel nply) -> dlaminate (ndir x 32 nel) and dtable (ndir x 16 npt nel); either may be
+ * NULL.  femo_layup_vjp: out (n) = J^T (laminate_bar, table_bar); either may be NULL.  One thread per cell and no atomics: two identical
+ * calls return the same bits. */
+int femo_set_layup(femo_ctx* ctx, int32_t nply, const double* plies, int32_t surfaces, double c_drill, const double* t, const double* theta);
+int femo_layup_jvp(femo_ctx* ctx, const char* wrt, int32_t ndir, const double* V, int64_t n, double* dlaminate, double* dtable);
+int femo_layup_vjp(femo_ctx* ctx, const char* wrt, const double* laminate_bar, const double* table_bar, double* out, int64_t n);
 
 /* State access -- replaces getFuncArray / setFuncArray on the state Function
  * (fea/utils_dolfinx.py:174-186). */
