@@ -153,7 +153,7 @@ class ShellContext:
 
     LAYUP_SURFACES = {"bot": 1, "mid": 2, "top": 4}
 
-    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None):
+    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None):
         """Layup mode (femo_set_layup): the laminate and the ply table are built on the device from ply thicknesses ``t`` and ply
         angles ``theta`` (degrees from E0), both (nel, nply) in solver cell order or (nply,) for the same layup in every cell; plies
         bottom to top.  ``plies``: one dict per ply, or one for all, with E1, E2, G12, nu12, G13, G23 and either the strengths
@@ -161,7 +161,9 @@ class ShellContext:
         [E1, E2, G12, nu12, G13, G23, F1, F2, F11, F22, F66, F12].  ``surfaces``: recovery points of every ply out of "bot", "mid",
         "top", in that order; () for none (no ply table).  ``c_drill=None`` takes the reference's 12 max(D) of this initial layup
         once; the mode then holds it constant.  ``plies=None`` leaves the mode and keeps the laminate and the table as ordinary
-        values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points."""
+        values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points.
+        ``density``: the (nply,) ply densities of the functional "layup_mass" (``set_layup_density``); None leaves whatever densities
+        the context holds (a layup of another ply count drops them)."""
         if plies is None:
             self._chk(self.lib.femo_set_layup(self._h, 0, None, 0, 0.0, None, None))
             return
@@ -181,6 +183,18 @@ class ShellContext:
             D = lam.clt_from_plies(pc[:, 0], pc[:, 1], pc[:, 2], pc[:, 3], pc[:, 4], pc[:, 5], t, theta)[2]
             c_drill = 12.0 * float(np.max(D))
         self._chk(self.lib.femo_set_layup(self._h, int(nply), dptr(pc), int(sum(bits)), float(c_drill), dptr(t), dptr(theta)))
+        if density is not None:
+            self.set_layup_density(density)
+
+    def set_layup_density(self, rho=None):
+        """Ply densities of the functional "layup_mass" (femo_set_layup_density): (nply,) values, finite and >= 0, the same in every
+        cell; ``None`` removes them.  They live with the layup: setting "ply_thickness" / "ply_angle" and a ``set_layup`` of the same
+        ply count keep them.  The factor is kept.  "layup_volume" needs none."""
+        if rho is None:
+            self._chk(self.lib.femo_set_layup_density(self._h, 0, None))
+            return
+        r = self._vec(rho)
+        self._chk(self.lib.femo_set_layup_density(self._h, r.size, dptr(r)))
 
     @staticmethod
     def _layup_plies(plies, nply):

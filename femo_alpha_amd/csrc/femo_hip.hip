@@ -13,6 +13,7 @@
 #include "ply_failure.h"
 #include "field_jvp.h"
 #include "layup.h"
+#include "layup_mass.h"
 #include "csr_map.h"
 #include "hip_handles.h"
 
@@ -144,6 +145,10 @@ struct femo_ctx {
         DevBuf<double> stage;       // a cell-major copy on its way in or out
         DevBuf<double> lbar, tbar;  // laminate / table cotangents (tangents) of the chain rule inside the derivative entry points
         DevBuf<long long> slots;    // k_layup_check: one slot per block, then the first offending entry
+        // per-ply densities of "layup_mass" (femo_set_layup_density; layup_mass.h): they live and leave with the layup
+        bool has_rho = false;
+        DevBuf<double> rho;         // nply values
+        DevBuf<double> mpart, mres; // block slots of the value pass; { layup_mass, layup_volume } of k_layup_mass_combine
     } lay;
     // dirichlet
     int nf = 0;
@@ -2696,6 +2701,7 @@ int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfa
     HIPCHK(c, hipMemcpy(lay.pc, pc.data(), pc.size() * sizeof(double), hipMemcpyHostToDevice));
     std::swap(lay.t, lay.tn);
     std::swap(lay.th, lay.thn);
+    if (lay.nply != nply) lay.has_rho = false;             // the densities belong to the plies they were given for
     lay.nply = nply; lay.surfaces = surfaces; lay.npt = npt; lay.c_drill = c_drill;
     lay.active = true;
     if (int rc = layup_build(c)) return rc;
@@ -2703,6 +2709,32 @@ int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfa
     operator_changed(c, !entering);
     ++c->opt_version;
     return 0;
+}
+
+int femo_set_layup_density(femo_ctx* c, int32_t nply, const double* rho) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& lay = c->lay;
+    if (!lay.active) return fail(c, "femo_set_layup_density: no layup is active (femo_set_layup)");
+    if (nply == 0 && !rho) {                               // remove the densities
+        lay.has_rho = false;
+        return 0;
+    }
+    char buf[200];
+    if (nply != lay.nply) {
+        snprintf(buf, sizeof buf, "femo_set_layup_density: the layup has %d plies, got %d densities", lay.nply, (int)nply);
+        return fail(c, buf);
+    }
+    if (!rho) return fail(c, "femo_set_layup_density: null values (rho: nply)");
+    for (int k = 0; k < nply; ++k)
+        if (!std::isfinite(rho[k]) || !(rho[k] >= 0.0)) {
+            snprintf(buf, sizeof buf, "femo_set_layup_density: the density of ply %d is not finite and >= 0", k);
+            return fail(c, buf);
+        }
+    HIPCHK(c, lay.rho.grow((size_t)nply));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(lay.rho, rho, (size_t)nply * sizeof(double), hipMemcpyHostToDevice));
+    lay.has_rho = true;
+    return 0;                                              // the operator does not see the densities: factor and Jacobi diagonal stay
 }
 
 static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n) {
@@ -3141,9 +3173,84 @@ static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
     return 0;
 }
 
+// ---- mass and volume from the layup (layup_mass.h): outputs of the layup itself, not of the laminate, and independent of the state
+static bool layup_mass_name(const femo_ctx* c, const std::string& fn) {
+    return c->lay.active && (fn == "layup_mass" || fn == "layup_volume");
+}
+
+// the densities "layup_mass" needs (null for "layup_volume"); "layup_mass" without densities is an error
+static int layup_mass_rho(femo_ctx* c, const std::string& fn, const double** rho) {
+    *rho = nullptr;
+    if (fn != "layup_mass") return 0;
+    if (!c->lay.has_rho) return fail(c, "layup_mass: no ply densities are set (femo_set_layup_density)");
+    *rho = c->lay.rho;
+    return 0;
+}
+
+// out2 = { layup_mass (0 without densities), layup_volume } over the selected sub-domain: one pass, slots merged in block order
+static int layup_mass_value_dev(femo_ctx* c, double out2[2]) {
+    auto& lay = c->lay;
+    const int g = nblk(c->nel, LAY_BLOCK);
+    HIPCHK(c, lay.mpart.grow((size_t)2 * g));
+    HIPCHK(c, lay.mres.grow(2));
+    ELEM_LAUNCH(c, k_layup_mass_value, NOEXTRA, g, LAY_BLOCK, mesh_dev(c), fields_dev(c), c->tab, (const double*)lay.t,
+                lay.has_rho ? (const double*)lay.rho : (const double*)nullptr, lay.nply, lay.mpart.get());
+    hipLaunchKernelGGL(k_layup_mass_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)lay.mpart, lay.mres.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, lay.mres, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out2[0] = c->scal_host[0]; out2[1] = c->scal_host[1];
+    return 0;
+}
+
+// gradient of "layup_mass" / "layup_volume" into the device buffer out (length n, zero-filled here): "ply_thickness" and "uhat" are
+// the two arguments they depend on, every other known argument gives exact zeros
+static int layup_mass_grad_dev(femo_ctx* c, const std::string& fn, const std::string& wrt, double* out, int64_t n) {
+    auto& lay = c->lay;
+    int64_t len;
+    if (wrt == "disp_solid") len = c->ndof;
+    else if (layup_wrt(c, wrt)) len = (int64_t)c->nel * lay.nply;
+    else if (!field_ptr(c, wrt.c_str(), &len)) return fail(c, "unknown argument '" + wrt + "'");
+    if (len != n) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
+    const double* rho;
+    if (int rc = layup_mass_rho(c, fn, &rho)) return rc;
+    hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    const MeshDev m = mesh_dev(c);
+    const FieldsDev f = fields_dev(c);
+    if (wrt == "ply_thickness") {
+        ELEM_LAUNCH(c, k_layup_mass_dt, NOEXTRA, nblk(c->nel, LAY_BLOCK), LAY_BLOCK, m, f, c->tab, rho, lay.nply, out);
+    } else if (wrt == "uhat") {
+        const int nthreads = c->nel * 3 * c->nvc;
+        if (c->quad) hipLaunchKernelGGL((k_layup_mass_shape<4, true>), dim3(nblk(nthreads, 128)), dim3(128), 0, c->stream, m, f, c->tab,
+                                        (const double*)lay.t, rho, lay.nply, out);
+        else hipLaunchKernelGGL((k_layup_mass_shape<3, false>), dim3(nblk(nthreads, 128)), dim3(128), 0, c->stream, m, f, c->tab,
+                                (const double*)lay.t, rho, lay.nply, out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// the arguments of the total derivatives, checked as dRdarg_T_dev checks them, for calls that never reach it (no adjoint to contract)
+static int total_arg_check(femo_ctx* c, const std::string& arg, int64_t n) {
+    int64_t len;
+    if (layup_wrt(c, arg)) len = (int64_t)c->nel * c->lay.nply;
+    else if (!field_ptr(c, arg.c_str(), &len)) return fail(c, "unknown argument '" + arg + "'");
+    if (len != n) return fail(c, "buffer has the wrong length for '" + arg + "'");
+    if (arg == "dirichlet") return fail(c, "(dR/d" + arg + ")^T is not implemented in this build");
+    return 0;
+}
+
 int femo_functional(femo_ctx* c, const char* name, double* value) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string s(name ? name : "");
+    if (layup_mass_name(c, s)) {
+        const double* rho;
+        if (int rc = layup_mass_rho(c, s, &rho)) return rc;
+        double v[2];
+        if (int rc = layup_mass_value_dev(c, v)) return rc;
+        *value = s == "layup_mass" ? v[0] : v[1];
+        return 0;
+    }
     if (s == "compliance" || s == "mass" || s == "volume" || s == "regularization") {
         double v[4];
         if (functionals_dev(c, v, 4)) return 1;
@@ -3230,6 +3337,8 @@ static int shape_gradient_dev(femo_ctx* c, int mode, const double* w, const doub
 
 // gradient of a functional into a device buffer `out` (length n, zero-filled here)
 static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string& wrt, double* out, int64_t n) {
+    // the layup's own outputs first: the composition below reaches the layup through the laminate and the table, which these never see
+    if (layup_mass_name(c, fn)) return layup_mass_grad_dev(c, fn, wrt, out, n);
     if (const int lw = layup_wrt(c, wrt)) {
         // the composition d/dx = (d laminate / dx)^T [d/d laminate] + (d table / dx)^T [d/d ply_table], on device buffers
         if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
@@ -3360,6 +3469,15 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
     }
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
+    if (layup_mass_name(c, fn)) {                                           // no state dependence: lambda = 0, the total is the partial
+        if (int rc = total_arg_check(c, a, n)) return rc;
+        if (int rc = dfunctional_dev(c, fn, a, d, n)) return rc;
+        if (iters) *iters = 0;
+        if (relres) *relres = 0.0;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    }
     int rc = dfunctional_dev(c, fn, "disp_solid", c->b, c->ndof);          // dJ/dw
     if (!rc) rc = solve_dispatch(c, c->b, c->lam, true, iters, relres);     // lambda = K^-1 dJ/dw
     if (!rc) rc = dfunctional_dev(c, fn, a, d, n);                          // dJ/d arg (zero-fills d)
@@ -3469,19 +3587,35 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
-    std::vector<double*> B(nfun), X(nfun);
-    for (int i = 0; i < nfun; ++i) { B[i] = Bd + i * nd; X[i] = Xd + i * nd; }
-    int rc = 0;
-    for (int i = 0; i < nfun && !rc; ++i) {
-        c->csel = subdomains ? subdomains[i] : -1;
-        rc = dfunctional_dev(c, functionals[i] ? functionals[i] : "", "disp_solid", B[i], c->ndof);      // dJ_i/dw
+    // the outputs of the layup itself (layup_mass.h) do not depend on the state: their adjoints are zero, and their columns stay out of
+    // the grouped sweeps.  solve[j]: the j-th functional that has an adjoint
+    std::vector<int> solve;
+    for (int i = 0; i < nfun; ++i)
+        if (!layup_mass_name(c, functionals[i] ? functionals[i] : "")) solve.push_back(i);
+    const int ns = (int)solve.size();
+    std::vector<double*> B(std::max(ns, 1)), X(std::max(ns, 1)), lam(nfun, nullptr);
+    for (int j = 0; j < ns; ++j) { B[j] = Bd + j * nd; X[j] = lam[solve[j]] = Xd + j * nd; }
+    std::vector<int32_t> it(std::max(ns, 1), 0);
+    std::vector<double> rr(std::max(ns, 1), 0.0);
+    int rc = ns == 0 ? total_arg_check(c, a, n) : 0;
+    for (int j = 0; j < ns && !rc; ++j) {
+        c->csel = subdomains ? subdomains[solve[j]] : -1;
+        rc = dfunctional_dev(c, functionals[solve[j]] ? functionals[solve[j]] : "", "disp_solid", B[j], c->ndof);      // dJ_i/dw
     }
-    if (!rc) { rc = solve_multi_dev(c, nfun, B.data(), X.data(), iters, relres); }                       // lambda_i = K^-1 dJ_i/dw
+    if (!rc && ns > 0) rc = solve_multi_dev(c, ns, B.data(), X.data(), it.data(), rr.data());            // lambda_i = K^-1 dJ_i/dw
+    for (int i = 0; i < nfun; ++i) {
+        if (iters) iters[i] = 0;
+        if (relres) relres[i] = 0.0;
+    }
+    for (int j = 0; j < ns; ++j) {
+        if (iters) iters[solve[j]] = it[j];
+        if (relres) relres[solve[j]] = rr[j];
+    }
     for (int i = 0; i < nfun && !rc; ++i) {
         c->csel = subdomains ? subdomains[i] : -1;
         double* g = Gd + (size_t)i * n;
-        rc = dfunctional_dev(c, functionals[i], a, g, n);                                                // dJ_i/d arg (zero-fills g)
-        if (!rc) rc = dRdarg_T_dev(c, a, X[i], -1.0, g, n);                                              // - (dR/d arg)^T lambda_i
+        rc = dfunctional_dev(c, functionals[i] ? functionals[i] : "", a, g, n);                          // dJ_i/d arg (zero-fills g)
+        if (!rc && lam[i]) rc = dRdarg_T_dev(c, a, lam[i], -1.0, g, n);                                  // - (dR/d arg)^T lambda_i
     }
     c->csel = keep_sel;
     if (!rc) {
@@ -3640,9 +3774,10 @@ int femo_residual_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* 
 // Tangent states of the forward chains (femo_total_jvp, femo_field_total_jvp): X[k] = -K^-1 (dR/d arg) V[k] on the device, the solves
 // grouped by solve_multi_dev.  The directions, right-hand sides and results live in mr_io (never in the solver's own vectors, which a
 // running factorisation may be sweeping ahead on):  V | B (right-hand sides, overwritten by the solves) | X | `extra` doubles for the
-// caller (*Ed).  jvp_check_arg has run.  Returns solve_multi_dev's status (4: option "strict").
+// caller (*Ed).  jvp_check_arg has run.  Returns solve_multi_dev's status (4: option "strict").  solve = false: the directions are
+// uploaded and nothing else happens -- for callers none of whose outputs depends on the state (iters and relres come back zero).
 static int tangent_states_dev(femo_ctx* c, const std::string& a, int ndir, const double* V, int64_t n, size_t extra, double** Vd_out,
-                              double** Xd_out, double** Ed, int32_t* iters, double* relres) {
+                              double** Xd_out, double** Ed, int32_t* iters, double* relres, bool solve = true) {
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     HIPCHK(c, c->mr_io.grow((size_t)ndir * (nv + 2 * nd) + extra));
     double* Vd = c->mr_io;
@@ -3651,6 +3786,13 @@ static int tangent_states_dev(femo_ctx* c, const std::string& a, int ndir, const
     std::vector<double*> B(ndir), X(ndir);
     for (int k = 0; k < ndir; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
     HIPCHK(c, hipMemcpy(Vd, V, (size_t)ndir * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (!solve) {
+        for (int k = 0; k < ndir; ++k) {
+            if (iters) iters[k] = 0;
+            if (relres) relres[k] = 0.0;
+        }
+        return 0;
+    }
     if (jvp_prepare(c)) return 1;
     int rc = 0;
     for (int k = 0; k < ndir && !rc; ++k) {
@@ -3680,7 +3822,10 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
     const int keep_sel = c->csel;
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
     double *Vd = nullptr, *Xd = nullptr, *Gw = nullptr;                                                 // behind X: dJ/dw | dJ/d arg
-    int rc = tangent_states_dev(c, a, ndir, V, n, nd + nv, &Vd, &Xd, &Gw, iters, relres);
+    // the outputs of the layup itself (layup_mass.h) have no state dependence: a call that asks for nothing else solves nothing
+    bool need_states = dW != nullptr || nfun == 0;
+    for (int i = 0; i < nfun; ++i) need_states = need_states || !layup_mass_name(c, functionals[i] ? functionals[i] : "");
+    int rc = tangent_states_dev(c, a, ndir, V, n, nd + nv, &Vd, &Xd, &Gw, iters, relres, need_states);
     if (rc) return rc;
     double* Ga = Gw + nd;
     std::vector<double*> X(ndir);
@@ -3690,10 +3835,12 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
     for (int i = 0; i < nfun && !rc; ++i) {
         c->csel = subdomains ? subdomains[i] : -1;
         const std::string fn(functionals[i] ? functionals[i] : "");
-        rc = dfunctional_dev(c, fn, "disp_solid", Gw, c->ndof);                                         // dJ_i/dw
+        const bool state_free = layup_mass_name(c, fn);                                                 // dJ_i/dw = 0: its slot keeps the memset's zero
+        if (!state_free) rc = dfunctional_dev(c, fn, "disp_solid", Gw, c->ndof);                        // dJ_i/dw
         if (!rc) rc = dfunctional_dev(c, fn, a, Ga, n);                                                 // dJ_i/d arg
         for (int k = 0; k < ndir && !rc; ++k) {
             double* s = c->jv.scal + 2 * ((size_t)i * ndir + k);
+            if (!state_free)
             hipLaunchKernelGGL(k_dot, dim3(red_grid(nd)), dim3(256), 0, c->stream, (const double*)Gw, (const double*)X[k], (int64_t)nd, s);
             hipLaunchKernelGGL(k_dot, dim3(red_grid(n)), dim3(256), 0, c->stream, (const double*)Ga, (const double*)(Vd + (size_t)k * n), n, s + 1);
         }

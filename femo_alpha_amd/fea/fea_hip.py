@@ -110,7 +110,8 @@ class _SubFunction:
 
 
 class Form:
-    """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume', 'ply_failure'.
+    """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume', 'ply_failure', and in
+    layup mode 'layup_mass' and 'layup_volume'.
     ``subdomain`` restricts the stress aggregate to one tagged set of cells (the reference's ``dxx(i)`` measure)."""
 
     def __init__(self, ctx, name, subdomain=-1, stress_params=None):

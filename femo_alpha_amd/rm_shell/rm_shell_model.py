@@ -106,11 +106,12 @@ class RMShellModel:
         self.ply_failure = None if ply_failure is None else int(ply_failure)
         if self.ply_failure is not None and not self.laminate:
             raise ValueError("ply_failure needs laminate=True")
-        # layup=dict(plies, t, theta[, surfaces, c_drill]) (with laminate=True; ShellContext.set_layup): the design variables of the
+        # layup=dict(plies, t, theta[, surfaces, c_drill, density]) (with laminate=True; ShellContext.set_layup): the design variables of the
         # laminate are the inputs "ply_thickness" and "ply_angle", (nel, nply) in caller cell order, and the laminate and the ply table
         # are built from them on the device.  t and theta give the initial layup ((nply,) or (nel, nply) in caller cell order); with
         # recovery points (surfaces, default bot / top of every ply) the output "ply_failure" exists.  They take the place of the
-        # laminate= and ply_table= arguments of evaluate and of ply_failure=npt here.
+        # laminate= and ply_table= arguments of evaluate and of ply_failure=npt here.  The outputs "layup_volume" and, with the (nply,)
+        # ply densities density=[...], "layup_mass" are functions of "ply_thickness" and "uhat" alone.
         self.layup = None
         if layup is not None:
             if not self.laminate or self.ply_failure is not None:
@@ -215,6 +216,10 @@ class RMShellModel:
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         if self.layup is not None and shell_pde.ply_npt:
             fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, None, rho=self.rho), arguments=["disp_solid"] + lam_args)
+        if self.layup is not None:
+            if shell_pde.layup_density:
+                fea.add_output(name="layup_mass", form=shell_pde.layup_mass(uhat, ply_t), arguments=["ply_thickness", "uhat"])
+            fea.add_output(name="layup_volume", form=shell_pde.layup_volume(uhat, ply_t), arguments=["ply_thickness", "uhat"])
         if self.ply_failure is not None:
             ply = Function(shell_pde.VP).bind("ply_table")
             fea.add_input("ply_table", ply, init_val=shell_pde.ply_table_init)

@@ -48,9 +48,9 @@ class RMShellPDE:
         # one-ply placeholder (1 mm of a unit-modulus isotropic ply) that the model's "laminate" input replaces.
         self.laminate = bool(laminate)
         self.VL = None
-        # layup=dict(plies, t, theta[, surfaces, c_drill]) (laminate mode; ShellContext.set_layup, solver cell order): the laminate and
-        # the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the recovery
-        # points, hence "ply_failure", follow from the layup's surfaces
+        # layup=dict(plies, t, theta[, surfaces, c_drill, density]) (laminate mode; ShellContext.set_layup, solver cell order): the
+        # laminate and the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the
+        # recovery points, hence "ply_failure", follow from the layup's surfaces, and "layup_mass" from its (nply,) ply densities
         self.layup = layup
         self.VY = None
         if layup is not None:
@@ -59,7 +59,8 @@ class RMShellPDE:
             t = np.asarray(layup["t"], dtype=np.float64)
             nply = t.shape[-1] if t.ndim else 1
             surfaces = tuple(layup.get("surfaces", ("bot", "top")))
-            self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"))
+            self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"), density=layup.get("density"))
+            self.layup_density = layup.get("density") is not None
             self.VY = FunctionSpace(self.ctx, "VY", width=nply)
             self.ply_thickness_init = self.ctx.get_field("ply_thickness")
             self.ply_angle_init = self.ctx.get_field("ply_angle")
@@ -147,6 +148,15 @@ class RMShellPDE:
         ``dx``: None for the whole mesh, or the index of a tagged sub-domain."""
         self.ctx.set_ply_failure_params(rho)
         return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
+
+    def layup_mass(self, uhat, ply_thickness, dx=None):
+        """sum_e (sum_k rho_k t_ek) int_e J dx from the ply thicknesses and the ply densities of the layup (include/femo_hip.h,
+        femo_set_layup_density); ``dx``: None for the whole mesh, or the index of a tagged sub-domain."""
+        return Form(self.ctx, "layup_mass", subdomain=-1 if dx is None else int(dx))
+
+    def layup_volume(self, uhat, ply_thickness, dx=None):
+        """sum_e (sum_k t_ek) int_e J dx from the ply thicknesses of the layup; ``dx`` as for ``layup_mass``."""
+        return Form(self.ctx, "layup_volume", subdomain=-1 if dx is None else int(dx))
 
     def ply_failure_field(self, w, uhat, ply_table):
         """The (nel, npt) field of the largest ply failure index per cell and recovery point as a field form: its tangents come

@@ -171,15 +171,35 @@ int femo_ply_failure_field(femo_ctx* ctx, double* out, int64_t n);
  *     d/dx = (d laminate/dx)^T [d/d laminate] + (d table/dx)^T [d/d ply_table] (or its forward counterpart), composed on the device.
  *     Angle derivatives are per degree;
  *   - not provided: the derivatives of the field outputs with respect to the layup (femo_field_output_vjp / _jvp / _jacobian,
- *     femo_field_total_gradients / _jvp, femo_field_gradient_vec and femo_dist_gradient refuse both names), mass and regularisation
- *     from the layup (they keep the "thickness" and "density" fields), per-cell ply materials, the multi-GPU driver and transient
- *     laminates.
+ *     femo_field_total_gradients / _jvp, femo_field_gradient_vec and femo_dist_gradient refuse both names), the regularisation
+ *     from the layup (it keeps the "thickness" field, as "mass" and "volume" keep "thickness" and "density"), per-cell ply
+ *     materials, the multi-GPU driver and transient laminates.
+ * Mass and volume from the layup (femo_alpha_amd/csrc/layup_mass.h) -- new: two functionals of the layup itself, over the selected
+ * sub-domain (femo_select_subdomain; "mass" and "volume" integrate the whole mesh), on the quadrature tables "mass" uses:
+ *     "layup_mass"   = sum_e (sum_k rho_k t_ek) sum_q w_q det_q J_q(uhat)
+ *     "layup_volume" = sum_e (sum_k t_ek)       sum_q w_q det_q J_q(uhat)
+ *   - femo_set_layup_density: nply densities rho_k, the same in every cell like the other per-ply constants.  A layup must be active
+ *     and nply must be its ply count; values finite and >= 0, the error names the first offending ply; rho == NULL with nply == 0
+ *     removes them.  A refused call changes nothing.  The densities live with the layup: a later femo_set_layup with the same nply
+ *     and femo_set_field of "ply_thickness" / "ply_angle" keep them, another nply drops them, leaving the mode drops them.  The
+ *     operator does not see them: the factor and the Jacobi diagonal are kept;
+ *   - "layup_mass" without densities fails with a message that names femo_set_layup_density; "layup_volume" needs none.  Outside a
+ *     layup both names are unknown functionals;
+ *   - femo_dfunctional: wrt "ply_thickness" is rho_k (or 1) times the cell's integrated w det J, zero outside the selection; wrt
+ *     "uhat" the shape derivative; exact zeros for "ply_angle", "disp_solid", "laminate", "ply_table", "thickness", "E", "nu",
+ *     "density" and "F_solid".  These outputs see the layup directly, never through the laminate;
+ *   - femo_total_gradient(s) and femo_total_jvp accept both names with every argument: neither depends on the state, so the total is
+ *     the explicit partial, a call that names only these outputs solves and factorises nothing and reports iters = 0, relres = 0
+ *     (femo_total_jvp: unless dW is asked for), and in a grouped call their columns stay out of the grouped sweeps;
+ *   - the value and the thickness gradient use no atomics and fixed summation orders: two identical calls return the same bits.  The
+ *     shape derivative accumulates on the vertices with the atomics of the other outputs' shape derivatives.
  * femo_set_layup(ctx, 0, NULL, 0, 0, NULL, NULL) leaves the mode and keeps the last laminate and table as ordinary values;
  * femo_set_laminate(ctx, NULL, 0) drops the layup together with the laminate.
  * femo_layup_jvp: ndir directions V (ndir x n, n = nel nply) -> dlaminate (ndir x 32 nel) and dtable (ndir x 16 npt nel); either may be
  * NULL.  femo_layup_vjp: out (n) = J^T (laminate_bar, table_bar); either may be NULL.  One thread per cell and no atomics: two identical
  * calls return the same bits. */
 int femo_set_layup(femo_ctx* ctx, int32_t nply, const double* plies, int32_t surfaces, double c_drill, const double* t, const double* theta);
+int femo_set_layup_density(femo_ctx* ctx, int32_t nply, const double* rho);
 int femo_layup_jvp(femo_ctx* ctx, const char* wrt, int32_t ndir, const double* V, int64_t n, double* dlaminate, double* dtable);
 int femo_layup_vjp(femo_ctx* ctx, const char* wrt, const double* laminate_bar, const double* table_bar, double* out, int64_t n);
 
