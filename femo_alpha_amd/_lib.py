@@ -82,6 +82,7 @@ SIGNATURES = {
     "femo_set_stress_alpha": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "femo_set_cell_tags": (C.c_int, [C.c_void_p, _c_int32_p, C.c_int64, C.c_int32]),
     "femo_select_subdomain": (C.c_int, [C.c_void_p, C.c_int32]),
+    "femo_set_disp_aggregate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, _c_double_p, C.c_int32]),
     "femo_field_output": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, C.c_int64]),
     "femo_field_output_vjp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64]),
     "femo_field_output_jacobian_nnz": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]),

@@ -640,6 +640,23 @@ class ShellContext:
     def select_subdomain(self, sel=-1):
         self._chk(self.lib.femo_select_subdomain(self._h, int(sel)))
 
+    def set_disp_aggregate(self, slot=0, rho=100.0, scaler=1.0, direction=None, nodes="vertices"):
+        """Parameters of one of the four max-displacement aggregates 'max_disp', 'max_disp1', 'max_disp2', 'max_disp3'
+        (femo_set_disp_aggregate): M = KS_rho(scaler |u_i|) / scaler over the selected nodes, or with ``direction`` d (3 values, used as
+        given) KS_rho(scaler d.u_i) / scaler, where scaler < 0 gives a smooth minimum of d.u.  ``nodes``: 'vertices' (what
+        ``disp_extracted`` holds) or 'all' (every displacement node)."""
+        kinds = {"vertices": 0, "all": 1}
+        if nodes not in kinds:
+            raise ValueError("nodes must be 'vertices' or 'all'")
+        self._disp_params = None               # whatever a Form cached as "the parameters the context holds" is void now
+        d = None
+        if direction is not None:
+            d = np.ascontiguousarray(np.asarray(direction, dtype=np.float64).ravel())
+            if d.size != 3:
+                raise ValueError("direction has 3 values")
+        self._chk(self.lib.femo_set_disp_aggregate(self._h, int(slot), float(rho), float(scaler), None if d is None else dptr(d),
+                                                   kinds[nodes]))
+
     def field_output(self, name="stress"):
         """DG1 projection of the von Mises stress: 'stress' (top surface), 'stress_mid', 'stress_bot'."""
         out = np.empty(self.mesh.nvc * self.mesh.nel)

@@ -14,6 +14,7 @@
 #include "field_jvp.h"
 #include "layup.h"
 #include "layup_mass.h"
+#include "disp_aggregate.h"
 #include "csr_map.h"
 #include "hip_handles.h"
 
@@ -150,6 +151,23 @@ struct femo_ctx {
         DevBuf<double> rho;         // nply values
         DevBuf<double> mpart, mres; // block slots of the value pass; { layup_mass, layup_volume } of k_layup_mass_combine
     } lay;
+    // max-displacement aggregates of the static state (femo_set_disp_aggregate; disp_aggregate.h): four parameter slots, and the node
+    // mask of every selection that has been asked for, kept until the cell tags change
+    struct DispAgg {
+        struct Slot {
+            double rho = 100.0, s = 1.0, d[3] = {0.0, 0.0, 0.0};
+            bool dir = false;
+            int nodes = 0;              // 0: mesh vertices, 1: every displacement node
+        } slot[4];
+        struct Mask {
+            DevBuf<unsigned char> m;    // nP2 flags: the node belongs to a cell of the selection
+            int nv = 0, na = 0;         // selected vertices, selected nodes
+            bool ready = false;
+        };
+        std::vector<Mask> masks;        // by selection + 1
+        DevBuf<int> cnt;
+        DevBuf<double> part, res;       // block slots of the value pass; { S, M, N, non-finite nodes } of k_da_combine
+    } da;
     // dirichlet
     int nf = 0;
     struct Facets {
@@ -3230,6 +3248,117 @@ static int layup_mass_grad_dev(femo_ctx* c, const std::string& fn, const std::st
     return 0;
 }
 
+// ---- max-displacement aggregates of the static state (disp_aggregate.h): "max_disp", "max_disp1", "max_disp2", "max_disp3"
+static int disp_agg_slot(const std::string& fn) {
+    if (fn == "max_disp") return 0;
+    if (fn.size() == 9 && fn.compare(0, 8, "max_disp") == 0 && fn[8] >= '1' && fn[8] <= '3') return fn[8] - '0';
+    return -1;
+}
+
+// the name of the selected sub-domain for messages
+static std::string disp_agg_where(const femo_ctx* c) {
+    return c->csel < 0 ? std::string("the whole mesh") : "sub-domain " + std::to_string(c->csel);
+}
+
+// the node mask of the selected sub-domain, built at first use and kept until the cell tags change; an empty selection is an error
+static int disp_agg_mask(femo_ctx* c, const std::string& fn, int nodes, const unsigned char** mask) {
+    auto& da = c->da;
+    if (c->nghost > 0)
+        return fail(c, fn + ": the max-displacement aggregate is not provided on a context with ghost entries (replicated separator "
+                         "nodes would be counted once per partition)");
+    if (c->di.ready)
+        return fail(c, fn + ": the max-displacement aggregate is not provided after femo_dist_setup (replicated separator nodes would "
+                         "be counted once per partition)");
+    if ((int)da.masks.size() != c->ntags + 1) { da.masks.clear(); da.masks.resize((size_t)c->ntags + 1); }
+    auto& mk = da.masks[(size_t)(c->csel + 1)];
+    if (!mk.ready) {
+        HIPCHK(c, mk.m.grow((size_t)c->nP2));
+        HIPCHK(c, da.cnt.grow(2));
+        HIPCHK(c, hipMemsetAsync(mk.m, 0, (size_t)c->nP2, c->stream));
+        HIPCHK(c, hipMemsetAsync(da.cnt, 0, 2 * sizeof(int), c->stream));
+        hipLaunchKernelGGL(k_da_mask, dim3(nblk(c->nel, 256)), dim3(256), 0, c->stream, c->nel, c->npc, c->nP2, (const int*)c->cellp2,
+                           (const int*)c->ctag, c->csel, mk.m.get());
+        hipLaunchKernelGGL(k_da_count, dim3(nblk(c->nP2, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, (const unsigned char*)mk.m, da.cnt.get());
+        HIPCHK(c, hipGetLastError());
+        int cnt[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(cnt, da.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        mk.nv = cnt[0]; mk.na = cnt[1];
+        mk.ready = true;
+    }
+    if ((nodes ? mk.na : mk.nv) == 0) return fail(c, fn + ": " + disp_agg_where(c) + " selects no displacement node (it has no cells)");
+    *mask = mk.m;
+    return 0;
+}
+
+static DispAggDev disp_agg_params(const femo_ctx* c, int slot) {
+    const auto& sl = c->da.slot[slot];
+    DispAggDev p;
+    p.rho = sl.rho; p.s = sl.s;
+    for (int k = 0; k < 3; ++k) p.d[k] = sl.d[k];
+    p.dir = sl.dir ? 1 : 0;
+    p.nlim = sl.nodes ? c->nP2 : c->nn;
+    return p;
+}
+
+// value pass of one slot over the selected sub-domain, enqueued only: block slots, then res = { S, M, N, non-finite nodes } on the device
+static int disp_agg_launch(femo_ctx* c, const std::string& fn, int slot, const unsigned char** mask) {
+    auto& da = c->da;
+    if (int rc = disp_agg_mask(c, fn, da.slot[slot].nodes, mask)) return rc;
+    const int g = nblk(c->nP2, DA_BLOCK);
+    HIPCHK(c, da.part.grow((size_t)4 * g));
+    HIPCHK(c, da.res.grow(4));
+    const DispAggDev p = disp_agg_params(c, slot);
+    hipLaunchKernelGGL(k_da_value, dim3(g), dim3(DA_BLOCK), 0, c->stream, c->nP2, p, *mask, (const double*)c->w, da.part.get());
+    hipLaunchKernelGGL(k_da_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)da.part, p.rho, p.s, da.res.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, M, N, non-finite nodes }; a non-finite translation at a selected node is an error
+static int disp_agg_value_dev(femo_ctx* c, const std::string& fn, int slot, double out4[4]) {
+    const unsigned char* mask;
+    if (int rc = disp_agg_launch(c, fn, slot, &mask)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->da.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
+    if (out4[3] > 0.0 || !std::isfinite(out4[1])) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: the aggregate is not finite: %.0f of the %.0f selected nodes of %s have a non-finite translation "
+                                  "(M = %g, rho = %g, scaler = %g)", fn.c_str(), out4[3], out4[2], disp_agg_where(c).c_str(), out4[1],
+                 c->da.slot[slot].rho, c->da.slot[slot].s);
+        return fail(c, msg);
+    }
+    return 0;
+}
+
+// d M / d w into out (ndof, zero-filled by the caller): the selected nodes write their three entries, the shift stays on the device
+static int disp_agg_grad_dev(femo_ctx* c, const std::string& fn, int slot, double* out) {
+    const unsigned char* mask;
+    if (int rc = disp_agg_launch(c, fn, slot, &mask)) return rc;
+    hipLaunchKernelGGL(k_da_grad, dim3(nblk(c->nP2, DA_BLOCK)), dim3(DA_BLOCK), 0, c->stream, c->nP2, disp_agg_params(c, slot), mask,
+                       (const double*)c->w, (const double*)c->da.res, out);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int femo_set_disp_aggregate(femo_ctx* c, int32_t slot, double rho, double scaler, const double* direction, int32_t nodes) {
+    if (slot < 0 || slot > 3) return fail(c, "femo_set_disp_aggregate: slot must be 0..3");
+    if (!(rho > 0.0) || !std::isfinite(rho)) return fail(c, "femo_set_disp_aggregate: rho must be finite and > 0");
+    if (scaler == 0.0 || !std::isfinite(scaler)) return fail(c, "femo_set_disp_aggregate: scaler must be finite and non-zero");
+    if (scaler < 0.0 && !direction) return fail(c, "femo_set_disp_aggregate: a negative scaler needs a direction (norm mode takes scaler > 0)");
+    if (direction) {
+        bool finite = true, zero = true;
+        for (int k = 0; k < 3; ++k) { finite = finite && std::isfinite(direction[k]); zero = zero && direction[k] == 0.0; }
+        if (!finite || zero) return fail(c, "femo_set_disp_aggregate: the direction must be finite and not zero");
+    }
+    if (nodes != 0 && nodes != 1) return fail(c, "femo_set_disp_aggregate: nodes must be 0 (mesh vertices) or 1 (every displacement node)");
+    auto& sl = c->da.slot[slot];
+    sl.rho = rho; sl.s = scaler; sl.nodes = nodes; sl.dir = direction != nullptr;
+    for (int k = 0; k < 3; ++k) sl.d[k] = direction ? direction[k] : 0.0;
+    return 0;
+}
+
 // the arguments of the total derivatives, checked as dRdarg_T_dev checks them, for calls that never reach it (no adjoint to contract)
 static int total_arg_check(femo_ctx* c, const std::string& arg, int64_t n) {
     int64_t len;
@@ -3283,6 +3412,12 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         double v[4];
         if (int rc = ply_value_dev(c, v)) return rc;
         *value = v[2];
+        return 0;
+    }
+    if (const int slot = disp_agg_slot(s); slot >= 0) {
+        double v[4];
+        if (int rc = disp_agg_value_dev(c, s, slot, v)) return rc;
+        *value = v[1];
         return 0;
     }
     if (s.rfind("sum_stress_", 0) == 0) {         // over the selected sub-domain (rm_shell_pde.py:130-150)
@@ -3365,6 +3500,13 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
         if (wrt == "disp_solid" || wrt == "ply_table") return ply_grad_dev(c, wrt == "disp_solid", out);
         HIPCHK(c, hipGetLastError());
         return 0;                                             // laminate, thickness, E, nu, density, F_solid: no explicit dependence
+    }
+    if (const int slot = disp_agg_slot(fn); slot >= 0) {      // nodal values, not integrals: the state is the only argument they see
+        if (wrt == "disp_solid") return disp_agg_grad_dev(c, fn, slot, out);
+        const unsigned char* mask;
+        if (int rc = disp_agg_mask(c, fn, c->da.slot[slot].nodes, &mask)) return rc;      // the refusals of the value, zeros otherwise
+        HIPCHK(c, hipGetLastError());
+        return 0;
     }
     if (wrt == "uhat") {
         if (fn == "regularization") return 0;                 // integrates over the reference configuration only
@@ -5348,6 +5490,7 @@ int femo_set_cell_tags(femo_ctx* c, const int32_t* tags, int64_t n, int32_t ntag
     HIPCHK(c, hipMemcpy(c->ctag, tags, (size_t)c->nel * sizeof(int), hipMemcpyHostToDevice));
     c->ntags = ntags; c->csel = -1;
     c->alpha_tag.assign(ntags, -1.0);
+    c->da.masks.clear();                            // node masks of the max-displacement aggregates: one per selection of the old tags
     return 0;
 }
 
@@ -5721,6 +5864,17 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             }
             hipLaunchKernelGGL(k_fill, dim3(vec_grid(nv)), dim3(256), 0, c->stream, c->lay.stage.get(), 0.0, (int64_t)nv);
             return layup_vjp_dev(c, s == "layup_vjp" ? 1 : 2, c->lay.lbar, nt > 0 ? c->lay.tbar.get() : nullptr, c->lay.stage);
+        }
+        // the max-displacement aggregate of slot 0 over the selected sub-domain (disp_aggregate.h): the value pass with its combine, and
+        // the gradient kernel alone (into c->tmp, the shift of the last value pass)
+        if (s == "disp_agg_value" || s == "disp_agg_grad") {
+            const unsigned char* mask;
+            if (s == "disp_agg_value") return disp_agg_launch(c, "max_disp", 0, &mask);
+            if (int rc = disp_agg_mask(c, "max_disp", c->da.slot[0].nodes, &mask)) return rc;
+            if (!c->da.res) return fail(c, "disp_agg_grad: time disp_agg_value first (it leaves the shift)");
+            hipLaunchKernelGGL(k_da_grad, dim3(nblk(c->nP2, DA_BLOCK)), dim3(DA_BLOCK), 0, c->stream, c->nP2, disp_agg_params(c, 0), mask,
+                               (const double*)c->w, (const double*)c->da.res, c->tmp.get());
+            return 0;
         }
         // one application of the factor to 1 / 2 / 4 vectors (the sweeps alone: no interleaving copies); needs a factorisation
         if (s == "sweeps1" || s == "sweeps2" || s == "sweeps4") {

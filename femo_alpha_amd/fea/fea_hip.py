@@ -111,11 +111,14 @@ class _SubFunction:
 
 class Form:
     """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume', 'ply_failure', and in
-    layup mode 'layup_mass' and 'layup_volume'.
+    layup mode 'layup_mass' and 'layup_volume', and the max-displacement aggregates 'max_disp', 'max_disp1', 'max_disp2', 'max_disp3'.
     ``subdomain`` restricts the stress aggregate to one tagged set of cells (the reference's ``dxx(i)`` measure)."""
 
-    def __init__(self, ctx, name, subdomain=-1, stress_params=None):
+    def __init__(self, ctx, name, subdomain=-1, stress_params=None, disp_params=None):
         self.ctx, self.name, self.subdomain = ctx, name, subdomain
+        # (slot, rho, scaler, direction or None, nodes) of a max-displacement form: they travel with the form like stress_params, and
+        # forms on different slots coexist
+        self.disp_params = disp_params
         # (m, rho, regularisation coefficient) of a p-norm stress form: every form keeps its own, as every UFL expression of the
         # reference does (rm_shell_pde.py:112-128), and hands them to the context right before it is evaluated
         self.stress_params = stress_params
@@ -129,6 +132,15 @@ class Form:
             self.ctx.set_option("stress_regularization", regc)
             self.ctx.set_stress_params(m, rho)
             self.ctx._stress_params = self.stress_params
+        if self.disp_params is not None:
+            slot = self.disp_params[0]
+            held = getattr(self.ctx, "_disp_params", None) or {}
+            if held.get(slot) != self.disp_params:
+                _, rho, scaler, direction, nodes = self.disp_params
+                self.ctx.set_disp_aggregate(slot, rho, scaler, direction, nodes)       # forgets what the context was known to hold
+                held = dict(held)
+                held[slot] = self.disp_params
+                self.ctx._disp_params = held
 
 
 class FieldForm:

@@ -67,7 +67,7 @@ def createCustomMeasure(mesh: ShellMesh, dim, SubdomainFunc, measure: str, tag: 
 class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
-                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None):
+                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None, max_disp=None):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -121,6 +121,26 @@ class RMShellModel:
             to_solver = lambda a: np.broadcast_to(a.reshape(-1, nply), (mesh.nel, nply))[self.cell_of_new]
             self.layup = dict(layup, t=to_solver(t), theta=to_solver(theta))
             self.nply = nply
+        # max_disp=dict(...) or a list of up to four: one max-displacement output per dict (RMShellPDE.max_disp) with the keys rho,
+        # scaler, direction, nodes, name (default "max_disp", "max_disp1", ...) and tag (a key of mesh_tags; none: the whole mesh).  The
+        # slot is the position in the list.
+        self.max_disp = None
+        if max_disp is not None:
+            specs = [dict(max_disp)] if isinstance(max_disp, dict) else [dict(d) for d in max_disp]
+            if not 1 <= len(specs) <= 4:
+                raise ValueError("max_disp: one to four outputs")
+            known = {"rho", "scaler", "direction", "nodes", "name", "tag"}
+            names = set()
+            for i, d in enumerate(specs):
+                if set(d) - known:
+                    raise ValueError(f"max_disp: unknown keys {sorted(set(d) - known)}")
+                d.setdefault("name", "max_disp" + (str(i) if i else ""))
+                if d.get("tag") is not None and (mesh_tags is None or d["tag"] not in mesh_tags):
+                    raise ValueError(f"max_disp: tag '{d['tag']}' is not a key of mesh_tags")
+                if d["name"] in names:
+                    raise ValueError(f"max_disp: the name '{d['name']}' is used twice")
+                names.add(d["name"])
+            self.max_disp = specs
         # n x n Gauss points per quadrilateral for the static forms (2..5).  The reference leaves the degree to UFL's
         # estimate, which on quadrilaterals comes out near 47 (scripts/ufl_degree_estimate.py): exact integration.  Default:
         # what the mesh asks for -- 4 on affine cells (exact there), 5 as soon as one cell is warped (within 1e-9 of the
@@ -231,6 +251,13 @@ class RMShellModel:
                 form_i = shell_pde.pnorm_stress(w, uhat, h, E, nu, i, m=self.m, rho=self.rho, alpha=None, regularization=False)
                 fea.add_output(name="pnorm_stress_" + str(tag), form=form_i,
                                arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
+        for i, d in enumerate(self.max_disp or ()):
+            if d["name"] in fea.outputs_dict or d["name"] in fea.inputs_dict or d["name"] in fea.states_dict:
+                raise ValueError(f"max_disp: the name '{d['name']}' is taken")
+            dx = None if d.get("tag") is None else self.association_table[d["tag"]]
+            form_i = shell_pde.max_disp(w, dx, slot=i, rho=d.get("rho", 100.0), scaler=d.get("scaler", 1.0),
+                                        direction=d.get("direction"), nodes=d.get("nodes", "vertices"))
+            fea.add_output(name=d["name"], form=form_i, arguments=["disp_solid"])
         fea.add_field_output(name="stress", form=stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"],
                              function_space=("DG", 1), record=False, vtk=True)
         if self.layup is not None and shell_pde.ply_npt:

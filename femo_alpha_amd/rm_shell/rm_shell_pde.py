@@ -149,6 +149,19 @@ class RMShellPDE:
         self.ctx.set_ply_failure_params(rho)
         return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
 
+    def max_disp(self, w, dx=None, slot=0, rho=100.0, scaler=1.0, direction=None, nodes="vertices"):
+        """Smooth maximum over the selected nodes of scaler |u_i| (or, with ``direction`` d, of scaler d.u_i; scaler < 0: a smooth minimum
+        of d.u), divided by scaler (include/femo_hip.h, femo_set_disp_aggregate) -- the static examples' ``tip_displacement =
+        csdl.maximum(csdl.norm(disp_extracted, axes=(1,)))`` as an output of the library.  ``dx``: None for the whole mesh, or the index
+        of a tagged sub-domain; ``slot`` 0..3 names the functional ('max_disp', 'max_disp1', ...) and keeps the parameters of up to four
+        such forms apart; ``nodes``: 'vertices' or 'all'."""
+        slot = int(slot)
+        if not 0 <= slot <= 3:
+            raise ValueError("max_disp: slot must be 0..3")
+        d = None if direction is None else tuple(float(x) for x in np.asarray(direction, dtype=np.float64).ravel())
+        return Form(self.ctx, "max_disp" + (str(slot) if slot else ""), subdomain=-1 if dx is None else int(dx),
+                    disp_params=(slot, float(rho), float(scaler), d, str(nodes)))
+
     def layup_mass(self, uhat, ply_thickness, dx=None):
         """sum_e (sum_k rho_k t_ek) int_e J dx from the ply thicknesses and the ply densities of the layup (include/femo_hip.h,
         femo_set_layup_density); ``dx``: None for the whole mesh, or the index of a tagged sub-domain."""

@@ -387,6 +387,40 @@ int femo_set_stress_alpha(femo_ctx* ctx, int32_t sel, double alpha);
  * cells of sub-domain sel, normalised by that sub-domain's reference area; sel = -1 selects the whole mesh again. */
 int femo_set_cell_tags(femo_ctx* ctx, const int32_t* tags, int64_t n, int32_t ntags);
 int femo_select_subdomain(femo_ctx* ctx, int32_t sel);
+/* Max-displacement aggregates of the static state (femo_alpha_amd/csrc/disp_aggregate.h) -- new: the smooth maximum the reference's
+ * static sizing examples build on the host, tip_displacement = csdl.maximum(csdl.norm(disp_extracted, axes=(1,)))
+ * (ex_lpc_shell_w_caddee.py:752, ex_tiltrotor_shell.py:398), as functionals of the library.  The contract is the project's own
+ * (csdl_alpha's maximum / norm are not checked against it); tests/disp_aggregate_ref.py restates it.
+ *   - displacement nodes are the nodes whose three translations are w[3 i .. 3 i + 2]: the P2 nodes, the mesh vertices being the first
+ *     nn of them.  A node is selected when it belongs to at least one cell of the selected sub-domain (femo_select_subdomain; -1: every
+ *     cell) and its kind is asked for: nodes = 0 the mesh vertices only (what disp_extracted holds), nodes = 1 every displacement node
+ *     (the same set on CG1CG1).  N is the number of selected nodes;
+ *   - four parameter slots, so that several constraints (an upper limit, a lower limit, a magnitude) share one grouped adjoint call:
+ *     the functionals "max_disp" (slot 0), "max_disp1", "max_disp2", "max_disp3".  Per slot rho > 0, a scaler s, an optional direction
+ *     d (3 values, used as given, not normalised) and nodes; before any call rho = 100, s = 1, no direction, nodes = 0;
+ *   - norm mode (no direction): x_i = s |u_i|, s > 0, |u| the plain sqrt(ux^2 + uy^2 + uz^2).  Direction mode: x_i = s (d . u_i),
+ *     s != 0; s < 0 gives a smooth minimum of d . u;
+ *   - S = x_max + (1/rho) log sum_i exp(rho (x_i - x_max)) and M = S / s: every exponent is <= 0, any finite rho x is safe;
+ *     p_i = exp(rho (x_i - S)), sum_i p_i = 1; dM/du_i = p_i u_i / |u_i| in norm mode (exactly 0 where |u_i| = 0, a subgradient as for
+ *     "pnorm_stress" at zero stress) and p_i d in direction mode; rotations and unselected nodes get exact zeros;
+ *   - bounds: s > 0: max_i x_i / s <= M <= max_i x_i / s + log N / (rho s);  s < 0: min_i d.u_i - log N / (rho |s|) <= M <= min_i d.u_i.
+ *     With w = 0 in norm mode M = log N / (rho s) and the gradient is all zeros;
+ *   - M does not depend on uhat, thickness, E, nu, density, F_solid, the laminate, the ply table or the layup (nodal values are not
+ *     integrals): femo_dfunctional gives exact zeros for these arguments (the layup names through the composition) and refuses unknown
+ *     arguments as for every functional;
+ *   - the four names are legal in femo_functional, femo_dfunctional, femo_dfunctional_vec, femo_total_gradient(s) and femo_total_jvp, in
+ *     any mix with the other functionals; subdomains[i] applies per functional;
+ *   - femo_set_disp_aggregate refuses, changing nothing: a slot outside 0..3, rho <= 0 or not finite, a scaler that is zero or not
+ *     finite, a scaler < 0 without a direction, a direction that is zero or not finite, nodes not 0 or 1.  direction = NULL: norm mode.
+ *     The operator does not see these parameters: the factor and the Jacobi diagonal are kept;
+ *   - errors: a selection without nodes (N = 0; the message names the sub-domain); a non-finite translation at a selected node (the
+ *     value call fails with a message); not provided, with that wording: a context with ghost entries (femo_create_ghost /
+ *     femo_create_element with nghost > 0) and a context after femo_dist_setup, where replicated separator nodes would be counted once
+ *     per partition;
+ *   - no float atomics: block results are merged in a fixed order, and the value, the gradient and the grouped totals of two identical
+ *     calls have the same bits.  The node mask of a selection is built at first use and kept until femo_set_cell_tags; results do not
+ *     depend on whether it was kept.  The state, the fields and the factor are never written. */
+int femo_set_disp_aggregate(femo_ctx* ctx, int32_t slot, double rho, double scaler, const double* direction, int32_t nodes);
 /* Field outputs "stress" (top surface, xi2 = h/2), "stress_mid" (xi2 = 0), "stress_bot" (xi2 = -h/2): von Mises stress
  * (RMShellPDE.von_Mises_stress(surface=...), rm_shell/rm_shell_pde.py:153-165) L2-projected onto DG1, nvc*nel values
  * (cell-major, the cell's vertices in connectivity order) -- replaces FEA.projectFieldOutput (fea/fea_dolfinx.py:205-206,
@@ -444,7 +478,8 @@ int femo_field_total_jvp(femo_ctx* ctx, int32_t nnames, const char* const* names
  * "regularization" (the thickness term of the compliance, rm_shell_pde.py:64-83), and over the selected sub-domain
  * (femo_select_subdomain; the whole mesh if none) "tip_disp" = 0.5 int u.u J, "area" = int J (rm_shell_pde.py:95-105) and
  * "sum_stress_x|y|z|xy|xz|yz" = int sigma_ij J dx of the top-surface in-plane stress (sum_stress_subdomain, :130-150), and in laminate
- * mode with a ply table "ply_failure" (femo_set_ply_table) --
+ * mode with a ply table "ply_failure" (femo_set_ply_table), and over the selected nodes "max_disp", "max_disp1", "max_disp2", "max_disp3"
+ * (femo_set_disp_aggregate) --
  * replaces assemble_scalar(form(c)) (csdl_alpha_opt/output_operation.py:51-56; forms at
  * rm_shell/rm_shell_pde.py:64-110). */
 int femo_functional(femo_ctx* ctx, const char* name, double* value);
