@@ -990,6 +990,8 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             }
             const int nt = (max_nb + TS - 1) / TS;
             const dim3 grid(nt * (nt + 1) / 2, cnt);
+            // (a level whose fronts are all empty -- the root above two components that share no node -- gathers nothing)
+            if (nt > 0)
             { ProfScope ps(c, 3);
               FOR_FRONT_CHUNKS(cnt, off, n)
                   hipLaunchKernelGGL(k_extend_gather, dim3(grid.x, n), dim3(256), 0, c->stream, fd, lev, off, mask, fused_schur ? 1 : 0); }

@@ -1697,12 +1697,21 @@ __global__ void k_penalty_setup(MeshDev m, FieldsDev f, FacetDev fd, double beta
             for (int b = 0; b < 3; ++b) M2[3 * a + b] += wq * U3[a] * U3[b];
         for (int a = 0; a < 2; ++a)
             for (int b = 0; b < 2; ++b) M1[2 * a + b] += wq * L1[a] * L1[b];
-        if (fd.MR) {
-            double R[3];
-            R[k % 3] = 1.0; R[(k + 1) % 3] = s; R[(k + 2) % 3] = -s;
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) MR[3 * a + b] += wq * R[a] * R[b];
-        }
+        // CG2CR1: R = (1, s, -s) on the slots (k, k + 1, k + 2).  Only the three moments of s are summed, and the block is filled from
+        // them below: formed entry by entry, (a, b) and (b, a), and the (k, k + 1) / (k, k + 2) pair -- zero but for rounding without
+        // mesh motion -- each kept a rounding residue of its own (1e-17 of the block), so the block was not exactly symmetric and the
+        // fronts, which keep one triangle of it, did not factorise the operator's matrix.  The pair must cancel on the mode the
+        // penalty leaves free (equal rotations on the two other edges), whose stiffness is 1e-8 of the penalty.
+        if (fd.MR) { MR[0] += wq; MR[1] += wq * s; MR[2] += wq * s * s; }
+    }
+    if (fd.MR) {
+        const double m0 = MR[0], m1 = MR[1], m2 = MR[2];
+        const int k0 = k % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+        MR[3 * k0 + k0] = m0;
+        MR[3 * k0 + k1] = MR[3 * k1 + k0] = m1;
+        MR[3 * k0 + k2] = MR[3 * k2 + k0] = -m1;
+        MR[3 * k1 + k1] = MR[3 * k2 + k2] = m2;
+        MR[3 * k1 + k2] = MR[3 * k2 + k1] = -m2;
     }
     for (int a = 0; a < 9; ++a) fd.M2[9 * i + a] = M2[a];
     for (int a = 0; a < 4; ++a) fd.M1[4 * i + a] = M1[a];

@@ -44,11 +44,25 @@ def _mesh(name):
         return tee_beam_mesh(nw=8, nh=4, nl=40)
     if name == "wing_mid":
         return wing_skin_mesh(12, 36)
+    import topology_meshes as tm
+    if tm.base(name) in tm.MESHES:            # disjoint, holed, high-valence and branched meshes (tests/test_gpu_topology.py)
+        return tm.mesh(tm.base(name))
     raise KeyError(name)
 
 
 def _strong(name):
+    import topology_meshes as tm
+    if tm.base(name) in tm.MESHES:
+        return name.endswith("_strong")
     return not name.startswith("plate")
+
+
+def _marker(name, strong):
+    """The clamped set: the root section (strong DOFs) or the x = 0 edge (penalty facets); the topology meshes bring their own."""
+    import topology_meshes as tm
+    if tm.base(name) in tm.MESHES:
+        return tm.clamp(tm.base(name))
+    return ROOT if strong else CLAMP
 
 
 def _fields(m, ewm=False):
@@ -67,8 +81,8 @@ def _problem(name, ewm=False, uhat=False, nred=0, laminate=False, operator=None)
         f = _fields(m, ewm)
         uh = 0.02 * np.random.default_rng(2).uniform(-1, 1, (m.nn, 3)) if uhat else None
         strong = _strong(name)
-        sd = m.locate_dofs_geometrical(ROOT) if strong else None
-        pf = None if strong else m.penalty_facets(CLAMP)
+        sd = m.locate_dofs_geometrical(_marker(name, strong)) if strong else None
+        pf = None if strong else m.penalty_facets(_marker(name, strong))
         clt = None
         if laminate:
             from laminate_ref import LaminateOracle
@@ -248,7 +262,11 @@ def test_sweep_forms(name):
 def test_several_vectors_column_by_column(name, post):
     """nrhs = 1 .. 6 through femo_frontal_apply: groups of up to four interleaved vectors (3 ride as 4, 5 = 4 + 1, 6 = 4 + 2), or one
     at a time where the grouped sweeps do not apply; every column against K and against the one-vector application."""
-    m, K, c = _context(name, post=post)
+    _several_vectors(name, post=post)
+
+
+def _several_vectors(name, leaf=8, pre=None, post=None):
+    m, K, c = _context(name, leaf, pre=pre, post=post)
     try:
         V = _probes(m.ndof, 6, seed=7)
         Z1 = np.stack([c.frontal_apply(v) for v in V])
@@ -259,7 +277,7 @@ def test_several_vectors_column_by_column(name, post):
                 w = omega(K, V[j], Z[j])
                 assert w <= BOUND, (k, j, w)
                 assert np.abs(Z[j] - Z1[j]).max() <= 1e-12 * np.abs(Z1[j]).max(), (k, j)
-        print(f"omega {name} nrhs 1..6 {post} {omega(K, V.T, Z.T):.3e}")
+        print(f"omega {name} nrhs 1..6 {pre or ''} {post} {omega(K, V.T, Z.T):.3e}")
         assert c.frontal_info()["pivots_repaired"] == 0
     finally:
         c.close()
@@ -353,11 +371,18 @@ def test_schur_blocks_level_by_level(name, sched):
     """After femo_factorize_range(l, l + 1) the Schur block of every front of level l is D - B A^-1 B^T of its subtree's own matrix
     (the element matrices of the subtree's cells; strong-BC rows and columns emptied, a unit diagonal where a constrained DOF is
     eliminated inside the subtree), in the scaled metric |S - S_ref|_ij / sqrt(S_ii S_jj).  A failure names the level and the front."""
+    _schur_blocks_level_by_level(name, sched)
+
+
+def _schur_blocks_level_by_level(name, sched, leaf=8):
+    """Returns the number of fronts compared that have no pivots (their block is the plain sum of their children's blocks, or of
+    their own cells' matrices: nothing is eliminated in them)."""
     import scipy.sparse.linalg as spla
     import torch
     from oracle.rm_shell_oracle import ShellOracle
     post = {"default": {}, "trailing 2 super_panel 256": dict(trailing=2, super_panel=256, super_panel_cnt=100000), "diag_t 1": dict(diag_t=1)}[sched]
-    m, K, c = _context(name, post=post)
+    m, K, c = _context(name, leaf, post=post)
+    pivot_free = 0
     try:
         _, _, d = _problem(name)
         o = ShellOracle(m, penalty_facets=d["pf"], strong_dofs=d["sd"])
@@ -407,7 +432,9 @@ def test_schur_blocks_level_by_level(name, sched):
                 unit = np.zeros(m.ndof); unit[interior[masked[interior]]] = 1.0
                 Ks = (keep @ Ks @ keep + sp.diags(unit)).tocsr()
                 A = Ks[interior][:, interior].tocsc(); B = Ks[bnd][:, interior]; D = Ks[bnd][:, bnd].toarray()
-                S_ref = D - B @ spla.splu(A).solve(B.T.toarray())
+                # (a subtree that eliminates nothing -- a pivot-free leaf -- has no A: its block is D itself)
+                S_ref = D - B @ spla.splu(A).solve(B.T.toarray()) if interior.size else D
+                pivot_free += npv == 0
                 S = torch.empty(nb * nb, dtype=torch.float64, device="cuda")
                 c.front_schur_get(int(t), S)
                 S = S.cpu().numpy().reshape(nb, nb).T              # column-major on the device; the lower triangle is maintained
@@ -424,3 +451,4 @@ def test_schur_blocks_level_by_level(name, sched):
         assert w <= BOUND
     finally:
         c.close()
+    return pivot_free

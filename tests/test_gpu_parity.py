@@ -34,7 +34,17 @@ def _mesh(kind):
     if kind == "tee":                # branching surface: flange + web, edges shared by three cells
         from femo_alpha_amd.mesh import tee_beam_mesh
         return tee_beam_mesh(1.0, 0.5, 5.0, 4, 2, 10)
+    import topology_meshes as tm
+    if kind in tm.MESHES:            # disjoint, holed, high-valence and branched meshes (tests/test_gpu_topology.py)
+        return tm.mesh(kind)
     raise ValueError(kind)
+
+
+def _marker(kind):
+    import topology_meshes as tm
+    if kind in tm.MESHES:
+        return tm.clamp(kind)
+    return CLAMP if kind.startswith("plate") or kind == "tee" else (lambda x: np.less(x[1], 1e-12))
 
 
 def _pair(kind, ewm=False, ewp=False, uhat=False, bc="penalty", beta=1e15, seed=0):
@@ -49,7 +59,7 @@ def _pair(kind, ewm=False, ewp=False, uhat=False, bc="penalty", beta=1e15, seed=
                   F_solid=rng.uniform(-1, 1, (nF, 3)))
     if uhat:
         fields["uhat"] = 0.02 * rng.uniform(-1, 1, (m.nn, 3))
-    marker = CLAMP if kind.startswith("plate") or kind == "tee" else (lambda x: np.less(x[1], 1e-12))
+    marker = _marker(kind)
     pf = m.penalty_facets(marker) if bc == "penalty" else None
     sd = m.locate_dofs_geometrical(marker) if bc == "strong" else None
     o = ShellOracle(m, element_wise_material=ewm, elementwise_pressure=ewp, penalty_facets=pf, strong_dofs=sd, beta=beta)
@@ -307,6 +317,11 @@ def test_bicgstab_matches_conjugate_gradients(kind, bc, precond):
 def test_shape_sensitivities_vs_oracle_finite_differences(kind, bc):
     """d/d uhat of the outputs and (dR/d uhat)^T lambda: dual-number kernels against central finite
     differences of the CPU oracle (which evaluates F = I + grad(uhat), gradx and J in the primal)."""
+    _shape_sensitivities(kind, bc)
+
+
+def _shape_sensitivities(kind, bc, vertices=(), nrandom=3):
+    """``vertices``: checked in addition to the ``nrandom`` drawn at random."""
     m, o, c, rng = _pair(kind, uhat=True, bc=bc, beta=1e6)
     w = rng.uniform(-1, 1, m.ndof) * 1e-3
     lam = rng.uniform(-1, 1, m.ndof)
@@ -325,7 +340,7 @@ def test_shape_sensitivities_vs_oracle_finite_differences(kind, bc):
         return (o.compliance(w), o.mass(), o.elastic_energy(w), lam @ (K() @ w - o.load_vector()))
 
     step = 1e-6
-    for v in rng.choice(m.nn, 3, replace=False):
+    for v in list(rng.choice(m.nn, nrandom, replace=False)) + list(vertices):
         for comp in range(3):
             up = u0.copy(); up[v, comp] += step
             um = u0.copy(); um[v, comp] -= step
