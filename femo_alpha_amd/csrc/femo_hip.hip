@@ -236,16 +236,6 @@ struct femo_ctx {
         int strict = 1;               // a Krylov solve that stops at maxit without reaching rtol is an error
         int allow_pivot_repair = 0;   // non-positive pivots: 0 = the factorisation fails, 1 = replace and count
         int profile_verbose = 0;
-        // 128 x 128 tiles for the triangular-grid rank-k updates when a launch has at least big_min_wg of them.  Built, validated (schedule
-        // fuzz) and measured SLOWER than the 64 x 64 kernel on every level at 1M DOF (rank-k updates 11.6 against 9.2 ms; levels 6-11:
-        // 26-38 against 33-43 TFLOP/s): two waves per SIMD instead of four hide the stage barriers worse, and diagonal / edge tiles waste
-        // twice as much.  Off by default.
-        int big_tiles = 0, big_min_wg = 512;
-        // rank-k updates with K <= strip_kmax on levels of at least strip_cnt fronts: k_schur_strip (a workgroup per 64-row strip of a front,
-        // panel rows, maps and metadata once per strip, the next block's operands and child entries in flight behind the current one)
-        // Measured (profiles/r5_strip_ab.txt): parity on the leaves, 1.4-1.7 x SLOWER than the tile kernel on the gathering levels 1-5, and more
-        // look-ahead makes it worse -- off by default (strip_cnt 0), kept as a validated alternative schedule
-        int strip_cnt = 0, strip_kmax = STRIP_KMAX, strip_depth = 1;     // strip_depth: blocks the children's entries are requested ahead (1..2)
         int diag_v1 = 0;              // diagonal-block kernel: 0 auto (see the launch), 1 round-2 kernel (sequential phases), 2 overlapped kernel
         int swork_slots = 8192;       // cap of the diagonal-block scratch (1 GB); larger levels are factorised in chunks (read at plan upload)
         int xinv_small_cnt = 32;      // inversion of L11: levels with at most this many fronts use 64 x 32 tiles
@@ -253,13 +243,6 @@ struct femo_ctx {
         // Measured at 1M DOF: one workgroup per 32 columns wins on every level (43-57 us against 49-115), so the default is never
         int bnd_tiled_nb = 1 << 30;
         int sweep_butterfly = 3;              // backward sweep column sums in one butterfly: bit 0 k_front_bwd_small, bit 1 k_sweep_bnd_cols
-        // wide levels: every run of consecutive wide levels is ONE launch per sweep direction, tiles ordered by per-front counters
-        // instead of launch boundaries (k_sweep_wide_fwd / k_sweep_wide_bwd).  Measured at 1 M DOF (profiles/r5_sweep_fuse_ab.txt): the ten
-        // wide levels take 517-546 us forward and 437-492 us backward in one launch each against 397 / 380 us as twenty launches -- what a
-        // launch boundary costs (~10 us per level and phase) is less than what replaces it: every tile waits for the acknowledgement of its
-        // own atomics before it may signal, and a tile in flight holds one of 512 slots for ~17 us instead of ~9.  Off; kept as a validated
-        // alternative schedule (schedule fuzz)
-        int sweep_fuse = 0;
         // wide levels: W = L21 X takes the place of L21 in the factor store (k_w_inplace, on stream3 behind the inversion of L11), and a
         // wide level is ONE launch per sweep direction: both of its products read the same input (k_sweep_fwd_w / k_sweep_bwd_w).
         // Measured at 1 M DOF (profiles/r5_sweep_w_ab.txt): an application of the preconditioner 1.459 ms against 1.520 -- inside the
@@ -280,14 +263,12 @@ struct femo_ctx {
         // the sweep of the top levels.  0 = off.
         int sweep_ahead = 2;
         int apply_lanes = 0;      // lanes per element of the matrix-free operator (k_apply4): 0 / 4 = a DPP quad; 5 = twelve elements on 60 lanes (25 points: 5 each instead of 7 + 6 + 6 + 6): measured SLOWER, 118.6 against 103.5 us (profiles/r6_apply_lanes.txt)
-        int diag_t = 0;           // 1 / 2: classes of fewer than four sub-blocks take k_diag_block_t (LDL / Cholesky elimination): measured slower / equal (profiles/r6_diag_ab.txt)
         int multi_rhs = 1;        // femo_solve_linear_multi / femo_total_gradients: 1 = right-hand sides share the sweeps in groups of up to 4; 0 = one at a time
         int stale_factor = 0;
         // ... and only while no field has moved further than this from the factor's design (relative L2 norm).  Measured at 1 M DOF
         // (profiles/r5_stale_factor.txt): forward + adjoint with the kept factor 12.8 / 15.7 / 18.7 / 24.7 ms at a relative nodal change of
         // 1e-4 / 1e-3 / 3e-3 / 1e-2 (L2: 0.58 of that) against 20.0 ms re-factorised -- the break-even sits at ~2.5e-3
         double stale_rel = 2e-3;
-        int sweep_read_mode = 0;              // how a fused sweep reads what other workgroups of the launch wrote: 0 returning atomic, 1 agent-scope load, 2 plain (experiment)
         int sh_levels_per_thread = 0;         // femo_newmark_stress_history*: levels one thread evaluates (0: enough level groups for ~2048 workgroups)
         int sh_chunk = 0;                     // ... levels whose per-cell element vectors share the scratch at a time (0: as many as fit in 128 MB)
         int dh_chunk = 0;                     // femo_newmark_disp_aggregate_grad: levels staged at a time for a host G (0: as many as fit in 128 MB)
@@ -315,14 +296,8 @@ struct femo_ctx {
         DevBuf<int> nf, npiv, dofs, upmap, parent, left, right, level_nodes, elem_front, elem_map, info, cinv0, cinv1;
         DevBuf<long long> poff, soff, doff, linvoff, xoff;
         DevBuf<double> P, S, Linv, X, Xtmp, Swork;
-        // fused sweeps of the wide levels (option "sweep_fuse"): tiles as tasks of one launch per run of consecutive wide levels
-        DevBuf<int> slot_of;                  // position of every front in level_nodes
         DevBuf<int> fel_off, fel;                    // elements of every level-0 front, by position in the level (front-centric assembly)
         bool fc_ok = false;                   // every element belongs to a level-0 front
-        DevBuf<int> sweep_cnt;                // two counters per position (k_sweep_wide_fwd / _bwd)
-        DevBuf<SweepTask> ftasks, btasks;
-        std::vector<long long> h_ft_off;      // forward table (levels ascending): tasks of level L at [h_ft_off[L], h_ft_off[L + 1])
-        std::vector<long long> h_bt_begin, h_bt_end;   // backward table (levels descending): tasks of level L at [begin, end)
         GraphExec sweep_graph;                // one preconditioner application on c->z, captured (option "sweep_graph")
         long long sweep_graph_key = -1;       // options version the graph was captured under
         std::vector<long long> h_soff;        // host copy of the Schur offsets (femo_front_schur_get / block_set)
@@ -1068,47 +1043,15 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             }
             return (need + TS - 1) / TS;
         };
-        // Triangular-grid updates (schur 1, 2, 5): 128 x 128 tiles where that still fills the chip (at least "big_min_wg" workgroups
-        // over the launch), 64 x 64 tiles otherwise.  `ntr`: 64-row tiles the launch needs (trail_tiles).
+        // Triangular-grid updates (schur 1, 2, 5) on 64 x 64 tiles.  `ntr`: 64-row tiles the launch needs (trail_tiles).
         auto launch_tri = [&](bool gather, int ntr, int off, int n, int C0_, int mode, int K0_, int KW_, hipStream_t st) {
-            // levels of many small fronts with a short K range (HBM-bound updates): one workgroup per 64-row strip of a front
-            // (k_schur_strip; option "strip_cnt": levels of at least that many fronts, 0 = never)
-            if (c->opt.strip_cnt > 0 && cnt_level >= c->opt.strip_cnt) {
-                int kmax = 0, gx = 0;
-                for (int i = b; i < e; ++i) {
-                    const int t = fr.h_level_nodes[i], nf = fr.h_nf[t];
-                    const TrailRange tr = trail_range(mode, C0_, K0_, KW_, fr.h_npiv[t], nf);
-                    if (tr.kw <= 0 || tr.col_lo >= tr.col_hi) continue;
-                    kmax = std::max(kmax, tr.kw);
-                    const int anchor = tr.col_lo & ~1;
-                    gx = std::max(gx, strip_wgs(nf - anchor, tr.col_hi - anchor));
-                }
-                if (kmax > 0 && kmax <= std::min(c->opt.strip_kmax, STRIP_KMAX)) {
-                    const dim3 grid(gx, 1, n);
-#define STRIP_LAUNCH(G_, KQ_, D_) hipLaunchKernelGGL((k_schur_strip<G_, KQ_, D_>), grid, dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask)
-#define STRIP_DEPTHS(G_, KQ_) do { if (c->opt.strip_depth <= 1) STRIP_LAUNCH(G_, KQ_, 1); else STRIP_LAUNCH(G_, KQ_, 2); } while (0)
-                    if (gather) { if (kmax <= 64) STRIP_DEPTHS(true, 16); else if (kmax <= 112) STRIP_DEPTHS(true, 28); else if (kmax <= 128) STRIP_DEPTHS(true, 32); else STRIP_DEPTHS(true, 40); }
-                    else        { if (kmax <= 64) STRIP_DEPTHS(false, 16); else if (kmax <= 128) STRIP_DEPTHS(false, 32); else STRIP_DEPTHS(false, 40); }
-#undef STRIP_DEPTHS
-#undef STRIP_LAUNCH
-                    return;
-                }
-            }
-            const int ntb = (ntr + 1) / 2;
-            const long long big_wgs = (long long)ntb * (ntb + 1) / 2 * n;
-            if (c->opt.big_tiles && big_wgs >= c->opt.big_min_wg) {
-                const size_t shm = 4 * sizeof(double) * 16 * LSTRB;
-                if (gather) hipLaunchKernelGGL(k_trailing_big<true>, dim3(ntb * (ntb + 1) / 2, 1, n), dim3(256), shm, st, fd, lev, off, C0_, mode, K0_, KW_, mask);
-                else hipLaunchKernelGGL(k_trailing_big<false>, dim3(ntb * (ntb + 1) / 2, 1, n), dim3(256), shm, st, fd, lev, off, C0_, mode, K0_, KW_, mask);
-            } else {
-                // levels of few large fronts: 4 x 4 super-tiles per XCD (k_trailing_mfma, tile_map 1); the grid covers whole rounds of
-                // eight super-tiles, the tiles beyond the front leave at once
-                const bool sup = c->opt.super_tiles && n < 256 && ntr >= c->opt.super_tiles_min;
-                const int nst = (ntr + 3) / 4, nsup = nst * (nst + 1) / 2;
-                const int gx = sup ? (nsup + 7) / 8 * 128 : ntr * (ntr + 1) / 2;
-                if (gather) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
-                else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
-            }
+            // levels of few large fronts: 4 x 4 super-tiles per XCD (k_trailing_mfma, tile_map 1); the grid covers whole rounds of
+            // eight super-tiles, the tiles beyond the front leave at once
+            const bool sup = c->opt.super_tiles && n < 256 && ntr >= c->opt.super_tiles_min;
+            const int nst = (ntr + 3) / 4, nsup = nst * (nst + 1) / 2;
+            const int gx = sup ? (nsup + 7) / 8 * 128 : ntr * (ntr + 1) / 2;
+            if (gather) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
+            else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
         };
         // narrow (schur 0) updates of few workgroups: their K range is cut into slices that run side by side and add their
         // products with atomics (options "narrow_split": most slices, "narrow_split_wg": most tiles of a launch that is cut)
@@ -1212,18 +1155,7 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
                       // 261 / 242 / 178 us with the new kernel throughout against 517 / 164 / 192 / 156).  Option "diag_v1": 1 forces
                       // the old kernel everywhere, 2 the new one.
                       const bool v1 = fuse_rows || c->opt.diag_v1 == 1 || (c->opt.diag_v1 == 0 && cnt >= c->opt.diag_v1_cnt) || (c->opt.diag_v1 == 3 && cnt >= 512 && nblk < NBO / NB);
-                      if (v1 && c->opt.diag_t && nblk < NBO / NB) {
-                          // classes of at most 1 / 2 / 3 sub-blocks: the compile-time-bounded kernel (3-4 workgroups per CU, LDL elimination)
-#define DIAG_T(NBLK_, REP_) do { if (c->opt.diag_t == 2) hipLaunchKernelGGL((k_diag_block_t<NBLK_, REP_, false>), dim3(end - start), dim3(256), diag_block_lds_blocks(NBLK_) * sizeof(blk32), st, \
-                                               fd, lev, start, C0, sw, fr.info, fuse_rows ? 1 : 0); \
-                            else hipLaunchKernelGGL((k_diag_block_t<NBLK_, REP_, true>), dim3(end - start), dim3(256), diag_block_lds_blocks(NBLK_) * sizeof(blk32), st, \
-                                               fd, lev, start, C0, sw, fr.info, fuse_rows ? 1 : 0); } while (0)
-                          const bool rep = c->opt.allow_pivot_repair != 0;
-                          if (nblk == 1) { if (rep) DIAG_T(1, true); else DIAG_T(1, false); }
-                          else if (nblk == 2) { if (rep) DIAG_T(2, true); else DIAG_T(2, false); }
-                          else { if (rep) DIAG_T(3, true); else DIAG_T(3, false); }
-#undef DIAG_T
-                      } else if (v1)
+                      if (v1)
                           hipLaunchKernelGGL(k_diag_block, dim3(end - start), dim3(256), diag_block_lds_blocks(nblk) * sizeof(blk32), st,
                                              fd, lev, start, nblk, C0, sw, fr.info, fuse_rows ? 1 : 0);
                       else if (c->opt.allow_pivot_repair)
@@ -1460,24 +1392,6 @@ static int frontal_fwd(femo_ctx* c, double* v, int l0, int l1, std::vector<Event
         const int* lev = fr.level_nodes + b;
         const int maxnp = fr.h_level_maxnp[L], maxnb = fr.h_level_maxnb[L];
         if (maxnp == 0) continue;
-        if (fr.h_level_wide[L] && c->opt.sweep_fuse && !fr.w_mode) {
-            // the run of consecutive wide levels from here: one launch, tiles ordered by per-front counters
-            if (join_xinv(c)) return 1;
-            int Le = L;
-            while (Le < l1 && fr.h_level_wide[Le]) ++Le;
-            const long long t0 = fr.h_ft_off[L], t1 = fr.h_ft_off[Le];
-            const int s0 = fr.h_level_off[L], s1 = fr.h_level_off[Le];
-            if (t1 > t0) {
-                HIPCHK(c, hipMemsetAsync(fr.sweep_cnt + 2 * (size_t)s0, 0, (size_t)(s1 - s0) * 2 * sizeof(int), c->stream));
-#define FWD_LAUNCH(RM_) hipLaunchKernelGGL(k_sweep_wide_fwd<RM_>, dim3((unsigned)(t1 - t0)), dim3(256), 0, c->stream, fd, (const int*)fr.level_nodes, \
-                                   (const SweepTask*)(fr.ftasks + t0), s0, (const int*)fr.slot_of, fr.sweep_cnt, v, y)
-                if (c->opt.sweep_read_mode == 0) FWD_LAUNCH(0); else if (c->opt.sweep_read_mode == 1) FWD_LAUNCH(1); else FWD_LAUNCH(2);
-#undef FWD_LAUNCH
-            }
-            for (int k = L; k < Le; ++k) { mark(); mark(); }        // the profile books the whole run under its first level
-            L = Le - 1;
-            continue;
-        }
         if (fr.h_level_wide[L]) {
             if (join_xinv(c)) return 1;
             const int nct = (maxnp + 127) / 128, nrt = (maxnb + 127) / 128;
@@ -1520,25 +1434,6 @@ static int frontal_bwd(femo_ctx* c, double* v, int l0, int l1, std::vector<Event
         const int* lev = fr.level_nodes + b;
         const int maxnp = fr.h_level_maxnp[L], maxnb = fr.h_level_maxnb[L];
         if (maxnp == 0) continue;
-        if (fr.h_level_wide[L] && c->opt.sweep_fuse && !fr.w_mode) {
-            if (join_xinv(c)) return 1;
-            int Lb = L;                                            // the run of consecutive wide levels from L down to Lb
-            while (Lb > l0 && fr.h_level_wide[Lb - 1]) --Lb;
-            const long long t0 = fr.h_bt_begin[L], t1 = fr.h_bt_end[Lb];
-            const int s0 = fr.h_level_off[Lb], s1 = fr.h_level_off[L + 1];
-            if (t1 > t0) {
-                int mxnb = 128;
-                for (int k = Lb; k <= L; ++k) mxnb = std::max(mxnb, fr.h_level_maxnb[k]);
-                HIPCHK(c, hipMemsetAsync(fr.sweep_cnt + 2 * (size_t)s0, 0, (size_t)(s1 - s0) * 2 * sizeof(int), c->stream));
-#define BWD_LAUNCH(RM_) hipLaunchKernelGGL(k_sweep_wide_bwd<RM_>, dim3((unsigned)(t1 - t0)), dim3(256), (size_t)mxnb * sizeof(double), c->stream, fd, \
-                                   (const int*)fr.level_nodes, (const SweepTask*)(fr.btasks + t0), s1, (const int*)fr.slot_of, fr.sweep_cnt, y, v)
-                if (c->opt.sweep_read_mode == 0) BWD_LAUNCH(0); else if (c->opt.sweep_read_mode == 1) BWD_LAUNCH(1); else BWD_LAUNCH(2);
-#undef BWD_LAUNCH
-            }
-            for (int k = Lb; k <= L; ++k) { mark(); mark(); }
-            L = Lb;
-            continue;
-        }
         if (fr.h_level_wide[L]) {
             if (join_xinv(c)) return 1;
             const int nct = (maxnp + 127) / 128, nrt = (maxnb + 127) / 128;
@@ -1844,7 +1739,7 @@ static int pcg_frontal(femo_ctx* c, double* b, double* x, bool zero_guess, int32
         // option "sweep_ahead": a cold solve from a zero guess applies the factor to z = b first, and b is known now -- hand it to the
         // factorisation, which starts its forward sweep through the lower levels beside the chain of the top ones
         const bool ahead = zero_guess && c->opt.sweep_ahead > 0 && c->fr.nlevels > c->opt.sweep_ahead + 1 && !c->opt.equilibrate &&
-                           c->opt.sweep_w == 0 && !c->opt.sweep_fuse;
+                           c->opt.sweep_w == 0;
         c->fr.ahead_levels = 0;
         if (ahead) {
             if (mask) hipLaunchKernelGGL(k_mask_zero, dim3(vg), dim3(256), 0, c->stream, b, mask, n);
@@ -3048,20 +2943,13 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "allow_pivot_repair") o.allow_pivot_repair = v != 0;
     else if (k == "stress_regularization") { if (value < 0) return fail(c, "stress_regularization: a coefficient >= 0 (the reference's is 0.5e3)"); c->stress_reg = value; }
     else if (k == "profile_verbose") o.profile_verbose = v != 0;
-    else if (k == "big_tiles") o.big_tiles = v != 0;
-    else if (k == "big_min_wg") o.big_min_wg = v;
-    else if (k == "strip_cnt") o.strip_cnt = v;
-    else if (k == "strip_kmax") o.strip_kmax = v;
-    else if (k == "strip_depth") { if (v < 1 || v > 2) return fail(c, "strip_depth: 1..2 blocks of look-ahead"); o.strip_depth = v; }
     else if (k == "diag_v1") { if (v < 0 || v > 3) return fail(c, "diag_v1: 0 auto, 1 round-2 kernel, 2 overlapped kernel, 3 the rule before the LDS diet"); o.diag_v1 = v; }
     else if (k == "profile") c->fr.profile = v != 0;      // event pair around every factorisation launch until switched off (femo_factorize_profile_get)
     else if (k == "bnd_tiled_nb") o.bnd_tiled_nb = v;
     else if (k == "sweep_butterfly") o.sweep_butterfly = v;
-    else if (k == "sweep_fuse") o.sweep_fuse = v != 0;
     else if (k == "assemble_fc") { if (v < 0 || v > 2) return fail(c, "assemble_fc: 0 never, 1 where it pays, 2 always"); o.assemble_fc = v; }
     else if (k == "sweep_w") { if ((v != 0) != (o.sweep_w != 0)) { o.sweep_w = v != 0; operator_changed(c); } }
     else if (k == "multi_rhs") { o.multi_rhs = v != 0; }
-    else if (k == "diag_t") { o.diag_t = v; }
     else if (k == "apply_lanes") { if (v != 0 && v != 4 && v != 5) return fail(c, "apply_lanes: 0 or 4 (a quad of lanes per element), or 5"); o.apply_lanes = v; }
     else if (k == "sweep_ahead") { if (v < 0) return fail(c, "sweep_ahead: number of top levels left to the solve (0: off)"); o.sweep_ahead = v; }
     else if (k == "stale_rel") { if (!(value >= 0)) return fail(c, "stale_rel: a relative change >= 0"); o.stale_rel = value; }
@@ -3069,7 +2957,6 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "stress_history_chunk") { if (v < 0) return fail(c, "stress_history_chunk: >= 0 levels (0: automatic)"); o.sh_chunk = v; }
     else if (k == "disp_history_chunk") { if (v < 0) return fail(c, "disp_history_chunk: >= 0 levels (0: automatic)"); o.dh_chunk = v; }
     else if (k == "stale_factor") { if (v < 0) return fail(c, "stale_factor: PCG iterations a kept factor is given before the factorisation is refreshed (0: never keep)"); o.stale_factor = v; }
-    else if (k == "sweep_read_mode") { if (v < 0 || v > 2) return fail(c, "sweep_read_mode: 0 returning atomic, 1 agent-scope load, 2 plain load (experiment)"); o.sweep_read_mode = v; }
     else if (k == "swork_slots") { if (c->fr.ready || v < 1) return fail(c, "swork_slots >= 1, before femo_set_frontal_plan"); o.swork_slots = v; }
     else if (k == "xinv_small_cnt") o.xinv_small_cnt = v;
     else return fail(c, "unknown option '" + k + "'");
@@ -4173,41 +4060,9 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
         UPI(fr.cinv0, inv0.data(), ndofs_total); UPI(fr.cinv1, inv1.data(), ndofs_total);
     }
     {
-        // task tables of the fused wide sweeps (k_sweep_wide_fwd / _bwd): per wide level the first-phase tiles of its fronts (in level
-        // order), then the second-phase tiles; forward table by ascending level, backward table by descending level
-        std::vector<int> slot_of(ntree, 0);
+        // front-centric assembly: the elements of every level-0 front, by position in the level
+        std::vector<int> slot_of(ntree, 0);            // position of every front in level_nodes
         for (int i = 0; i < ntree; ++i) slot_of[level_nodes[i]] = i;
-        std::vector<SweepTask> ft, bt;
-        fr.h_ft_off.assign(nlevels + 1, 0); fr.h_bt_begin.assign(nlevels, 0); fr.h_bt_end.assign(nlevels, 0);
-        for (int L = 0; L < nlevels; ++L) {
-            fr.h_ft_off[L] = (long long)ft.size();
-            // (first-phase tiles of ALL fronts of the level, then the second-phase tiles: with a front's two phases next to each other
-            //  the workgroups in flight are the waiting second-phase tiles of a few fronts while the other fronts' first phase queues)
-            if (fr.h_level_wide[L]) {
-                for (int i = level_off[L]; i < level_off[L + 1]; ++i)
-                    for (int k = 0; k < sweep_xtiles(npiv[level_nodes[i]]); ++k) ft.push_back({i, k});
-                for (int i = level_off[L]; i < level_off[L + 1]; ++i) {
-                    const int t = level_nodes[i];
-                    for (int k = 0; k < sweep_ltiles(npiv[t], nf[t] - npiv[t]); ++k) ft.push_back({i, (1 << 24) | k});
-                }
-            }
-        }
-        fr.h_ft_off[nlevels] = (long long)ft.size();
-        for (int L = nlevels - 1; L >= 0; --L) {
-            fr.h_bt_begin[L] = (long long)bt.size();
-            if (fr.h_level_wide[L]) {
-                for (int i = level_off[L]; i < level_off[L + 1]; ++i) {
-                    const int t = level_nodes[i];
-                    for (int k = 0; k < sweep_bblocks(npiv[t], nf[t] - npiv[t]); ++k) bt.push_back({i, k});
-                }
-                for (int i = level_off[L]; i < level_off[L + 1]; ++i)
-                    for (int k = 0; k < sweep_xtiles(npiv[level_nodes[i]]); ++k) bt.push_back({i, (1 << 24) | k});
-            }
-            fr.h_bt_end[L] = (long long)bt.size();
-        }
-        if (sweep_xtiles(fr.max_nf) >= (1 << 24)) return fail(c, "front too large for the fused sweep task table");
-        UPI(fr.slot_of, slot_of.data(), ntree);
-        // front-centric assembly: the elements of every level-0 front
         const int cnt0 = level_off[1] - level_off[0];
         std::vector<int> fel_off(cnt0 + 1, 0), fel((size_t)std::max<long long>(c->nel, 1));
         fr.fc_ok = true;
@@ -4221,8 +4076,6 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
             for (long long e = 0; e < c->nel; ++e) fel[fill[slot_of[elem_front[e]] - level_off[0]]++] = (int)e;
             UPI(fr.fel_off, fel_off.data(), cnt0 + 1); UPI(fr.fel, fel.data(), c->nel);
         }
-        UPI(fr.ftasks, ft.data(), ft.size()); UPI(fr.btasks, bt.data(), bt.size());
-        HIPCHK(c, fr.sweep_cnt.alloc((size_t)std::max(ntree, 1) * 2));
     }
     HIPCHK(c, fr.P.alloc((size_t)std::max<long long>(fr.p_doubles, 1)));
     HIPCHK(c, hipMemset(fr.P, 0, (size_t)std::max<long long>(fr.p_doubles, 1) * sizeof(double)));   // once: the upper triangles of L11 are never written
@@ -4245,9 +4098,6 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
         HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_bnd_cols<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_bwd_w<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_bwd_w<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_wide_bwd<0>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_wide_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_sweep_wide_bwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     }
     // ... and of their NR-vector forms (sweeps_multi.h), NR times as much on the levels that are not wide: the grouped applications
     // take as many interleaved vectors as fit (frontal_apply_group splits a group into pairs or single vectors beyond that)
@@ -4271,8 +4121,6 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block,hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block_lds_blocks(NBO / NB) * sizeof(blk32))));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_panel_rows_preload, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_ROWS_PRELOAD_LDS));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_trailing_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * sizeof(double) * 16 * LSTRB)));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_trailing_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * sizeof(double) * 16 * LSTRB)));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block2<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block2_lds_blocks(NBO / NB) * sizeof(blk32))));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block2<true>, hipFuncAttributeMaxDynamicSharedMemorySize,

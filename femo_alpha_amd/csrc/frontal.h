@@ -935,198 +935,6 @@ k_diag_block(FrontDev fd, const int* __restrict__ level_nodes, int first, int nb
     }
 }
 
-// k_diag_block for the classes of at most NBLK = 1, 2 or 3 sub-blocks (round 6): the same phases with every loop bounded at compile
-// time, so that a front of 72 pivots does not carry the registers of a 128-column block (188 VGPRs: two workgroups per CU whatever
-// the LDS footprint) -- 168 registers, three workgroups per CU for one or two sub-blocks (capped at 128 the elimination spills
-// 370 bytes) -- and with the LDL^T elimination of k_diag_block2 on
-// wave 0.  The levels of many small fronts are bound by workgroups per CU times the latency of one (8192 leaf fronts / (256 CUs x 2)
-// rounds of ~45 us), not by bytes or flops.
-template <int NBLK, bool REPAIR, bool LDL>
-__global__ void __launch_bounds__(256, NBLK <= 2 ? 3 : 2)
-k_diag_block_t(FrontDev fd, const int* __restrict__ level_nodes, int first, int C0, double* __restrict__ Swork,
-               int* __restrict__ info, int fuse_rows) {
-    constexpr int nblk = NBLK, ND = NBLK * (NBLK + 1) / 2;
-    STAMP(31);
-    const int slot = first + blockIdx.x;                       // position of the front in its level
-    const int t = level_nodes[slot];
-    const int np = fd.npiv[t];
-    if (C0 >= np) return;
-    const int kw = min(NBO, np - C0);
-    const int nkb = (kw + NB - 1) / NB;
-    const int ldp = ldp_of(fd.nf[t]);
-    double* F = fd.P + fd.poff[t];                             // pivot columns only
-    // the inverse of this diagonal block: scratch (levels solved with the one-workgroup-per-front kernels) or the diagonal
-    // block of the front's X (wide levels)
-    const int lds_ = Swork ? SPD : ldx_of(np);
-    double* Sout = Swork ? Swork + (size_t)slot * SPD * SPD : fd.X + fd.xoff[t] + C0 + (size_t)lds_ * C0;
-    extern __shared__ double lds_raw[];
-    blk32* D = reinterpret_cast<blk32*>(lds_raw);              // sub-block (i, j), i >= j, at i (i + 1) / 2 + j
-    constexpr int nD = ND;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int si = wv & 1, sj = wv >> 1, l15 = lane & 15, l4 = lane >> 4;
-    // load (identity padding beyond kw; only the lower triangle of the front is maintained): all 40 loads of a thread
-    // are issued before the first one is consumed -- a loop over the sub-blocks would pay the memory latency ten times
-    {
-        double v[ND][4];
-#pragma unroll
-        for (int b = 0; b < ND; ++b) {
-            const int bi = b < 1 ? 0 : b < 3 ? 1 : b < 6 ? 2 : 3;
-            const int bj = b - bi * (bi + 1) / 2;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = tid + 256 * q;
-                const int r = idx % NB, c = idx / NB;
-                const int gr = NB * bi + r, gc = NB * bj + c;
-                v[b][q] = (gr == gc) ? 1.0 : 0.0;
-                if (b < nD && bi < nkb && gr < kw && gc < kw && gc <= gr) v[b][q] = F[(C0 + gr) + (size_t)ldp * (C0 + gc)];
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < ND; ++b)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = tid + 256 * q;
-                if (b < nD) D[b][idx % NB][idx / NB] = v[b][q];
-            }
-    }
-    // (no zero fill of S: every sub-block on or below the block diagonal is written in full below, and nothing above it
-    //  or beyond the kw columns is ever read)
-    STAMP(0);
-    __syncthreads();
-    STAMP(1);
-    for (int j = 0; j < nkb; ++j) {
-        blk32& Djj = D[j * (j + 1) / 2 + j];
-        const int wb = min(NB, kw - NB * j);
-        STAMP(2 + 4 * j);
-        if (wv == 0) {
-            double a[NB];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) a[c] = (lane < NB) ? Djj[lane][c] : (c == lane - NB ? 1.0 : 0.0);
-            // LDL^T elimination: no square root on the pivot chain (4.9 against ~6.5 us per block, scripts/micro/lat_micro.hip); the rows of
-            // the inverse take 1 / sqrt(d_row) afterwards (the broadcast reads lanes < 32 and stays outside the divergent store)
-            int bad;
-            if (LDL) {
-                double rs;
-                bad = ldl32_inverse<REPAIR>(a, wb, lane, &rs);
-#pragma unroll
-                for (int r = 0; r < NB; ++r) a[r] *= rl(rs, r);
-            } else {
-                bad = chol32_inverse(a, wb, lane);
-            }
-            if (lane >= NB) {
-                const int cl = lane - NB;               // this lane holds column cl of the inverse
-                double* Li = fd.Linv + fd.linvoff[t] + (size_t)(C0 / NB + j) * NB * NB;
-#pragma unroll
-                for (int r = 0; r < NB; ++r) {
-                    const double v = (cl < wb && r < wb && cl <= r) ? a[r] : 0.0;
-                    Djj[r][cl] = v;                     // the diagonal sub-block now holds Linv_j
-                    Li[r + NB * cl] = v;
-                }
-                if (cl == 0 && bad) atomicAdd(info, bad);
-            }
-        }
-        __syncthreads();
-        STAMP(3 + 4 * j);
-        if (j + 1 < nkb) {
-            // L_ij = D_ij Linv_j^T for the sub-blocks below
-            mfma_d4 acc[NBLK > 1 ? NBLK - 1 : 1];
-#pragma unroll
-            for (int i = 1; i < NBLK; ++i) {
-                acc[i - 1] = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-                if (j + i < nkb) mfma_blk<false, true>(acc[i - 1], D[(j + i) * (j + i + 1) / 2 + j], Djj, si, sj, l15, l4);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 1; i < NBLK; ++i) {
-                if (j + i >= nkb) continue;
-                blk32& Dij = D[(j + i) * (j + i + 1) / 2 + j];
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int r = 16 * si + l4 + 4 * reg, c = 16 * sj + l15;
-                    Dij[r][c] = acc[i - 1][reg];
-                    const int gr = NB * (j + i) + r, gc = NB * j + c;
-                    if (gr < kw && gc < kw) F[(C0 + gr) + (size_t)ldp * (C0 + gc)] = acc[i - 1][reg];
-                }
-            }
-            __syncthreads();
-            STAMP(4 + 4 * j);
-            // D_ik -= L_ij L_kj^T, i >= k > j (each wave updates its own sub-block of every D_ik)
-            for (int i = j + 1; i < nkb; ++i)
-                for (int k = j + 1; k <= i; ++k) {
-                    mfma_d4 u = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-                    mfma_blk<false, true>(u, D[i * (i + 1) / 2 + j], D[k * (k + 1) / 2 + j], si, sj, l15, l4);
-                    blk32& Dik = D[i * (i + 1) / 2 + k];
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) Dik[16 * si + l4 + 4 * reg][16 * sj + l15] -= u[reg];
-                }
-            __syncthreads();
-        }
-    }
-    // inverse of the kw x kw factor, block column by block column
-    STAMP(20);
-    for (int j = 0; j < nkb; ++j) {
-        const blk32& Sjj = D[j * (j + 1) / 2 + j];
-        if (!fuse_rows)
-        for (int idx = tid; idx < NB * NB; idx += 256) {
-            const int r = idx % NB, c = idx / NB;
-            Sout[(NB * j + r) + (size_t)lds_ * (NB * j + c)] = Sjj[r][c];
-        }
-        for (int i = j + 1; i < nkb; ++i) {
-            // W = sum_{k=j}^{i-1} L_ik S_kj: S_kj (j < k < i) already sits where L_kj was; L_ij is read here for the last time
-            blk32& Dij = D[i * (i + 1) / 2 + j];
-            mfma_d4 w = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-            for (int k = j; k < i; ++k)
-                mfma_blk<false, false>(w, D[i * (i + 1) / 2 + k], D[k * (k + 1) / 2 + j], si, sj, l15, l4);
-            __syncthreads();                                   // every wave has read L_ij: its sub-block takes W
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) Dij[16 * si + l4 + 4 * reg][16 * sj + l15] = w[reg];
-            __syncthreads();
-            // S_ij = -Linv_i W
-            mfma_d4 x = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-            mfma_blk<false, false>(x, D[i * (i + 1) / 2 + i], Dij, si, sj, l15, l4);
-            __syncthreads();                                   // every wave has read W: the sub-block takes S_ij
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int r = 16 * si + l4 + 4 * reg, c = 16 * sj + l15;
-                Dij[r][c] = -x[reg];
-                if (!fuse_rows) Sout[(NB * i + r) + (size_t)lds_ * (NB * j + c)] = -x[reg];
-            }
-            __syncthreads();
-        }
-    }
-    STAMP(21);
-    if (fuse_rows) {
-        // L[r][C0 + c] = sum_{k <= c} A[r][C0 + k] S[c][k] for the rows below the block (k_panel_rows' product): a wave takes 16 rows
-        // at a time, their kw entries in registers as the MFMA B operand, S[c][k] from the sub-blocks in LDS as the A operand
-        __syncthreads();
-        const int nf = fd.nf[t];
-        for (int row0 = C0 + kw + 16 * wv; row0 < nf; row0 += 64) {
-            const int row = row0 + l15;
-            const bool rok = row < nf;
-            double a[NBLK * 8];
-#pragma unroll
-            for (int kk = 0; kk < NBLK * 8; ++kk) {
-                const int k = 4 * kk + l4;
-                a[kk] = (rok && k < kw) ? F[row + (size_t)ldp * (C0 + k)] : 0.0;
-            }
-#pragma unroll
-            for (int cb = 0; cb < NBLK * 2; ++cb) {
-                if (16 * cb >= kw) break;
-                const int bi = cb >> 1;
-                mfma_d4 acc = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int kk = 0; kk < 4 * cb + 4; ++kk)
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(D[bi * (bi + 1) / 2 + (kk >> 3)][16 * (cb & 1) + l15][4 * (kk & 7) + l4], a[kk], acc, 0, 0, 0);
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int c = 16 * cb + l4 + 4 * reg;
-                    if (rok && c < kw) F[row + (size_t)ldp * (C0 + c)] = acc[reg];
-                }
-            }
-        }
-    }
-}
-
 
 // ---- k_diag_block2: the same block, the same outputs, scheduled for latency.
 // k_diag_block runs its phases one after the other on ONE workgroup: four register factorisations on wave 0 (three waves
@@ -1981,418 +1789,6 @@ k_trailing_fine(FrontDev fd, const int* __restrict__ level_nodes, int first, int
         if (cok[reg]) *cp[reg] = cv[reg] - acc[reg];
 }
 
-// ---- the rank-k update of the levels of many small fronts (K <= 160: the leaves and the four or five levels above them), where
-// the update moves its compulsory bytes only and is bound by HBM, not by the matrix cores.  k_trailing_mfma runs those levels at
-// 0.31 of the HBM peak: a 64 x 64 tile there is a chain of dependent round trips -- front metadata, two to nine staged K steps with
-// one step of look-ahead, the index maps of the gather, the children's entries, the store -- about 13 us with three workgroups
-// per CU, and every tile reads its own 2 x 64 rows of the K panel and its own maps.  Here a workgroup takes a 64-ROW STRIP of a
-// front's update (all updated columns up to the diagonal, in chunks of at most STRIP_CH blocks of 16 columns):
-//   * front metadata, the row maps of the gather (one register per child and lane) and the strip's own 64 rows of the K panel
-//     (the MFMA B operand: 16 rows x K per wave, in registers, k_panel_rows' layout) are loaded ONCE per strip;
-//   * the column maps of the chunk go to LDS once (2 x 256 entries);
-//   * per block of 16 columns the other operand (16 rows of the panel x K: 16 KB at K = 128) is staged through LDS, double
-//     buffered, and while the matrix cores work on block n the panel rows AND the children's entries of block n + 1 are already in
-//     flight: a stage is one barrier, K / 4 MFMAs per wave and one epilogue of four entries per lane whose loads were issued a stage
-//     earlier -- no dependent round trip inside the loop.
-// The product is formed as in k_panel_rows (D[i = column][j = row]: a lane stores along the rows of the column-major front).
-// K range, column range and the gather are those of k_trailing_mfma (trail_range); KQ = K steps of 4 the B operand has room for.
-constexpr int STRIP_CH = 16;           // blocks of 16 columns per workgroup at most
-constexpr int STRIP_KMAX = 160;        // the widest K range the kernel is instantiated for
-
-// workgroups the update of one front needs: rows and updated columns counted from the even column anchor
-__device__ __host__ inline int strip_wgs(int nrows, int ncols) {
-    const int nstrips = (nrows + 63) / 64, ncb = (ncols + 15) / 16;
-    int n = 0;
-    for (int s = 0; s < nstrips; ++s) {
-        const int nbk = 4 * (s + 1) < ncb ? 4 * (s + 1) : ncb;
-        n += (nbk + STRIP_CH - 1) / STRIP_CH;
-    }
-    return n;
-}
-
-template <bool GATHER, int KQ, int DEPTH>
-__global__ void __launch_bounds__(256, KQ > 32 ? 2 : 3)
-k_schur_strip(FrontDev fd, const int* __restrict__ level_nodes, int first, int C0, int schur, int K0, int KW,
-              const unsigned char* __restrict__ mask) {
-    // whole fronts per XCD on levels of many fronts (the strips of a front read the same panel rows): k_trailing_mfma's map
-    int bxv = blockIdx.x, zv = blockIdx.z;
-    {
-        const int G = gridDim.x, n = gridDim.z;
-        if (n >= 256 && (n & 7) == 0) {
-            const int flat = bxv + G * zv, x = flat & 7, q = flat >> 3;
-            zv = (q / G) * 8 + x; bxv = q % G;
-        }
-    }
-    const int t = level_nodes[first + zv];
-    const int np = fd.npiv[t], nf = fd.nf[t];
-    const TrailRange tr = trail_range(schur, C0, K0, KW, np, nf);
-    const int kc0 = tr.kc0, kw = tr.kw, col_lo = tr.col_lo, col_hi = tr.col_hi;
-    if (kw <= 0 || col_lo >= col_hi) return;
-    const int anchor = col_lo & ~1;
-    const int nstrips = (nf - anchor + 63) / 64, ncb = (col_hi - anchor + 15) / 16;
-    // strip s (rows anchor + 64 s ..) and chunk of its column blocks; the longest strips come first in launch order
-    int s = nstrips - 1, chunk = -1;
-    for (int lin = bxv; s >= 0; --s) {
-        const int nbk = min(4 * (s + 1), ncb), n = (nbk + STRIP_CH - 1) / STRIP_CH;
-        if (lin < n) { chunk = lin; break; }
-        lin -= n;
-    }
-    if (chunk < 0) return;
-    const int cb_lo = STRIP_CH * chunk, cb_hi = min(min(4 * (s + 1), ncb), cb_lo + STRIP_CH);
-    __shared__ __attribute__((aligned(16))) double sA[2][4 * KQ][16];      // sA[.][k][c] = L[anchor + 16 cb + c][kc0 + k]
-    __shared__ int cmap[2][16 * STRIP_CH];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
-    const FrontView fv = front_view(fd, t);
-    const int ldp = ldp_of(nf);
-    const int rw = anchor + 64 * s + 16 * wv;                  // this wave's 16 rows
-    const int r = rw + l15;
-    const bool rok = r < nf;
-    const double* Lk = fv.P + (size_t)ldp * kc0;               // the K panel: always pivot columns
-    // B operand: the wave's rows, every k, in registers.  Addresses are clamped and NOTHING is masked: rows past the front give
-    // products that are never stored, and the K range is cut off by the other operand (zero beyond kw).  (A select on the loaded
-    // value makes the compiler sink every load into a branch of its own with a full wait behind it: 32 dependent round trips.)
-    double b[KQ];
-    {
-        const double* rowp = Lk + min(r, nf - 1);
-#pragma unroll
-        for (int kk = 0; kk < KQ; ++kk) b[kk] = rowp[(size_t)ldp * min(4 * kk + l4, kw - 1)];
-    }
-    // staging of the other operand: thread (row pair cp, k slot kq) loads rows 2 cp, 2 cp + 1 of the block at k = kq + 32 q
-    const int cp = tid & 7, kq = tid >> 3;
-    constexpr int NQ = (4 * KQ + 31) / 32;
-    constexpr int NSET = DEPTH + 1;
-    // A wave's vector-memory operations retire in ISSUE order: waiting for the panel rows of the next block waits for every load
-    // issued before them.  So the panel rows (L2 hits) are requested one block FURTHER ahead than the children's entries (HBM) and
-    // always before them -- DEPTH + 1 register sets -- or the entries would have one stage to arrive whatever their look-ahead.
-    d2 pa[NSET][NQ];
-    auto fetchA = [&](int cb, d2 (&dst)[NQ]) {
-        const double* p = Lk + min(anchor + 16 * cb + 2 * cp, ldp - 2);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int k = kq + 32 * q;
-            const d2 v = *reinterpret_cast<const d2*>(p + (size_t)ldp * min(k, kw - 1));
-            const d2 z = {0.0, 0.0};
-            dst[q] = k < kw ? v : z;
-        }
-    };
-    auto stashA = [&](int buf, const d2 (&src)[NQ]) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int k = kq + 32 * q;
-            if (k < 4 * KQ) *reinterpret_cast<d2*>(&sA[buf][k][2 * cp]) = src[q];
-        }
-    };
-    // the gather: rows of the children's fronts that land on this lane's row (registers) and on the chunk's columns (LDS)
-    const long long dp = fd.doff[t];
-    int xrow[2] = {-1, -1}, npc[2] = {0, 0}, nbc[2] = {0, 0};
-    const double* Sc[2] = {fd.S, fd.S};
-    if (GATHER) {
-        int chd[2];
-#pragma unroll
-        for (int sd = 0; sd < 2; ++sd) {
-            const int ch = fd.child[sd][t];
-            const int chs = ch >= 0 ? ch : t;
-            chd[sd] = ch;
-            npc[sd] = fd.npiv[chs]; nbc[sd] = fd.nf[chs] - npc[sd];
-            Sc[sd] = fd.S + fd.soff[chs];
-            const int x = fd.cinv[sd][dp + min(r, nf - 1)];
-            xrow[sd] = (ch >= 0 && rok) ? x : -1;
-        }
-        for (int i = tid; i < 2 * 16 * STRIP_CH; i += 256) {
-            const int sd = i / (16 * STRIP_CH), j = i % (16 * STRIP_CH);
-            const int cc = anchor + 16 * cb_lo + j;
-            const int y = fd.cinv[sd][dp + min(cc, nf - 1)];
-            cmap[sd][j] = (chd[sd] >= 0 && cc >= col_lo && cc < col_hi) ? y : -1;
-        }
-    }
-    fetchA(cb_lo, pa[0]);
-    stashA(0, pa[0]);
-    __syncthreads();
-    // entries of C this lane's epilogue needs for block cb: the children's (GATHER) or the front's own -- requested a stage ahead;
-    // `okm` keeps which of them exist (the select waits for the data, so it is left to the epilogue)
-    constexpr int NG = GATHER ? 8 : 4;
-    auto request = [&](int cb, double (&g)[NG], unsigned& okm) {
-        okm = 0;
-        const int j0 = 16 * (cb - cb_lo);
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int cc = anchor + 16 * cb + l4 + 4 * reg;
-            const bool tri = rok && r >= cc && cc >= col_lo && cc < col_hi;
-            if (GATHER) {
-#pragma unroll
-                for (int sd = 0; sd < 2; ++sd) {
-                    const int x = xrow[sd], y = cmap[sd][j0 + l4 + 4 * reg];
-                    const bool ok = tri && x >= 0 && y >= 0;
-                    const int lo = min(x, y) - npc[sd], hi = max(x, y) - npc[sd];
-                    g[2 * reg + sd] = Sc[sd][ok ? hi + (size_t)nbc[sd] * lo : 0];
-                    okm |= (ok ? 1u : 0u) << (2 * reg + sd);
-                }
-            } else {
-                const double* src = tri ? fv.col(cc) + r : fv.P;      // (one load from a selected address, not a load in a branch)
-                g[reg] = *src;
-                okm |= (tri ? 1u : 0u) << reg;
-            }
-        }
-    };
-    const int* gd = fd.dofs + dp;
-    // one stage: block cb with the entries `g` requested DEPTH stages earlier; the next block's panel rows and the entries of block
-    // cb + DEPTH go on their way first
-    auto stage = [&](int cb, const double (&g)[NG], unsigned okm, double (&gnext)[NG], unsigned& oknext, d2 (&anew)[NQ], const d2 (&anext)[NQ]) {
-        const int buf = (cb - cb_lo) & 1;
-        if (cb + DEPTH + 1 < cb_hi) fetchA(cb + DEPTH + 1, anew);
-        if (cb + DEPTH < cb_hi) request(cb + DEPTH, gnext, oknext);
-        const int cj = anchor + 16 * cb;
-        // the wave has entries in this block if its last row reaches the block's first column (lower triangle)
-        if (rw < nf && rw + 15 >= cj) {
-            mfma_d4 acc = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < KQ; ++kk)
-                if (4 * kk < kw) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sA[buf][4 * kk + l4][l15], b[kk], acc, 0, 0, 0);   // D[i = column][j = row]
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int cc = cj + l4 + 4 * reg;
-                const bool tri = rok && r >= cc && cc >= col_lo && cc < col_hi;
-                double cv;
-                if (GATHER) {
-                    cv = (((okm >> (2 * reg)) & 1u) ? g[2 * reg] : 0.0) + (((okm >> (2 * reg + 1)) & 1u) ? g[2 * reg + 1] : 0.0);
-                    if (mask && tri && r == cc && cc < np && mask[gd[r]]) cv = 1.0;      // strong-BC pivots: unit diagonal, as in the extend-add
-                } else {
-                    cv = g[reg];
-                }
-                if (tri) fv.col(cc)[r] = cv - acc[reg];
-            }
-        }
-        if (cb + 1 < cb_hi) stashA(buf ^ 1, anext);
-        __syncthreads();
-    };
-    // DEPTH + 1 register sets each for the requested entries and for the panel rows, rotated by unrolling (a copy would wait for the
-    // loads just issued): at stage n the panel rows of block n + DEPTH + 1 are requested, then the entries of block n + DEPTH.
-    // A stage lasts K / 4 MFMAs (0.35-0.9 us), a load of the children's entries from HBM 2-3 us under load.
-    double g[NSET][NG];
-    unsigned okm[NSET];
-#pragma unroll
-    for (int d = 1; d <= DEPTH; ++d)
-        if (cb_lo + d < cb_hi) fetchA(cb_lo + d, pa[d % NSET]);
-#pragma unroll
-    for (int d = 0; d < DEPTH; ++d) {
-        okm[d] = 0;
-        if (cb_lo + d < cb_hi) request(cb_lo + d, g[d], okm[d]);
-    }
-    for (int cb = cb_lo; cb < cb_hi; cb += NSET) {
-#pragma unroll
-        for (int u = 0; u < NSET; ++u)
-            if (cb + u < cb_hi) stage(cb + u, g[u], okm[u], g[(u + DEPTH) % NSET], okm[(u + DEPTH) % NSET], pa[u], pa[(u + 1) % NSET]);
-    }
-}
-
-// ---- the same rank-k update on 128 x 128 tiles (schur 1, 2, 5: the updates of whole Schur complements / trailing matrices).
-// The per-level counter table (profiles/r3_pmc_trailing_levels.md) shows where the 64 x 64 kernel loses: on the MFMA-bound
-// levels (6 and up) it moves 2.2-3 x its compulsory bytes at ~4 TB/s -- every tile re-reads 2 x 64 rows of the K panel, and
-// the tiles of a front are spread over eight L2s -- and it issues one LDS read per MFMA.  A workgroup of the same four waves on a
-// 128 x 128 tile (a wave: 64 x 64 = 4 x 4 MFMA blocks, 128 accumulator registers) reads half the panel bytes per updated entry and
-// one LDS operand per TWO MFMAs.  Used where the fronts are large enough to fill the chip with such tiles (host: option "big_nb").
-constexpr int TSB = 128;
-constexpr int LSTRB = TSB + 16;
-
-template <bool GATHER>
-__global__ void __launch_bounds__(256, 2)
-k_trailing_big(FrontDev fd, const int* __restrict__ level_nodes, int first, int C0, int schur, int K0, int KW,
-               const unsigned char* __restrict__ mask) {
-    const int t = level_nodes[first + blockIdx.z];
-    const int np = fd.npiv[t];
-    const int nf = fd.nf[t];
-    const TrailRange tr = trail_range(schur, C0, K0, KW, np, nf);
-    const int kc0 = tr.kc0, kw = tr.kw, col_lo = tr.col_lo, col_hi = tr.col_hi;
-    if (kw <= 0) return;
-    const int lin = blockIdx.x;
-    int ti = (int)((sqrt(8.0 * lin + 1.0) - 1.0) * 0.5);
-    while ((ti + 1) * (ti + 2) / 2 <= lin) ++ti;
-    while (ti * (ti + 1) / 2 > lin) --ti;
-    const int by = lin - ti * (ti + 1) / 2, bx = ti - by;          // column tile by, row tile by + bx
-    const int cj = (col_lo & ~1) + by * TSB;
-    if (cj >= col_hi) return;
-    const int ri = cj + bx * TSB;
-    if (ri >= nf) return;
-    const FrontView fv = front_view(fd, t);
-    constexpr int KC = 16;
-    extern __shared__ __attribute__((aligned(16))) double lds_big[];
-    typedef double stage_t[KC][LSTRB];
-    stage_t* si = reinterpret_cast<stage_t*>(lds_big);             // si[buf][k][r] = L[ri + r][kc0 + k0 + k]
-    stage_t* sj = si + 2;                                          // sj[buf][k][c] = L[cj + c][kc0 + k0 + k]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int wr = (wv & 1) * 64, wc = (wv >> 1) * 64;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    // staging: thread (row pair rp of 64, group cg of 4) loads factor columns cg, cg + 4, cg + 8, cg + 12 of both operand blocks
-    const int rp = tid & 63, cg = tid >> 6;
-    const int ldp = ldp_of(nf);
-    const int rowi = min(ri + 2 * rp, ldp - 2), rowj = min(cj + 2 * rp, ldp - 2);
-    const char* base = reinterpret_cast<const char*>(fv.P + (size_t)ldp * kc0);
-    const size_t stage_bytes = (size_t)ldp * KC * 8;
-    unsigned obi[4], obj[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        obi[q] = 8u * (unsigned)(rowi + ldp * (cg + 4 * q));
-        obj[q] = 8u * (unsigned)(rowj + ldp * (cg + 4 * q));
-    }
-    d2 pi[4], pj[4];
-    auto fetch = [&](const char* b) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            pi[q] = *reinterpret_cast<const d2*>(b + obi[q]);
-            pj[q] = *reinterpret_cast<const d2*>(b + obj[q]);
-        }
-    };
-    auto fetch_tail = [&](const char* b, int left) {
-        const d2 z = {0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const unsigned a = 8u * (unsigned)(ldp * min(cg + 4 * q, left - 1));
-            const d2 vi = *reinterpret_cast<const d2*>(b + 8u * (unsigned)rowi + a), vj = *reinterpret_cast<const d2*>(b + 8u * (unsigned)rowj + a);
-            pi[q] = cg + 4 * q < left ? vi : z;
-            pj[q] = cg + 4 * q < left ? vj : z;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            *reinterpret_cast<d2*>(&si[buf][cg + 4 * q][2 * rp]) = pi[q];
-            *reinterpret_cast<d2*>(&sj[buf][cg + 4 * q][2 * rp]) = pj[q];
-        }
-    };
-    if (kw >= KC) fetch(base); else fetch_tail(base, kw);
-    base += stage_bytes;
-    mfma_d4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (mfma_d4){0.0, 0.0, 0.0, 0.0};
-    stash(0);
-    __syncthreads();
-    int cur = 0;
-    for (int k0 = 0; k0 < kw; k0 += KC) {
-        const int left = kw - k0 - KC;
-        if (left > 0) {
-            if (left >= KC) fetch(base); else fetch_tail(base, left);
-            base += stage_bytes;
-        }
-#pragma unroll
-        for (int kk = 0; kk < KC; kk += 4) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) av[a] = sj[cur][kk + l4][wc + 16 * a + l15];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bv[b] = si[cur][kk + l4][wr + 16 * b + l15];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        if (left > 0) stash(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    // epilogue, one 16-column block of the wave's quarter at a time (a): C -= D, or C = (children's entries) - D
-    const long long dp = fd.doff[t];
-    int rr[2][4];
-    const double* Sc[2] = {nullptr, nullptr};
-    int npc[2] = {0, 0}, nbc[2] = {0, 0}, chv[2] = {-1, -1};
-    if (GATHER) {
-#pragma unroll
-        for (int sd = 0; sd < 2; ++sd) {
-            const int ch = fd.child[sd][t];
-            const int chs = ch >= 0 ? ch : t;
-            chv[sd] = ch;
-            npc[sd] = fd.npiv[chs]; nbc[sd] = fd.nf[chs] - npc[sd];
-            Sc[sd] = fd.S + fd.soff[chs];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int r = ri + wr + 16 * b + l15;
-                rr[sd][b] = fd.cinv[sd][dp + min(r, nf - 1)];
-                if (ch < 0 || r >= nf) rr[sd][b] = -1;
-            }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        bool cok[4];
-        double* cp[4];
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-            cok[reg] = cc >= col_lo && cc < col_hi;
-            cp[reg] = cok[reg] ? fv.col(cc) : fv.P - (nf - 1);
-        }
-        double cv[4][4];
-        if (!GATHER) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                    const int r = ri + wr + 16 * b + l15;
-                    const bool ok = cok[reg] && r < nf && r >= cc;
-                    cv[b][reg] = cp[reg][ok ? r : nf - 1];
-                }
-        } else {
-            int cr[2][4];
-#pragma unroll
-            for (int sd = 0; sd < 2; ++sd)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                    cr[sd][reg] = fd.cinv[sd][dp + min(cc, nf - 1)];
-                    if (chv[sd] < 0 || !cok[reg]) cr[sd][reg] = -1;
-                }
-            double g0[4][4], g1[4][4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                    const int r = ri + wr + 16 * b + l15;
-                    const bool tri = r >= cc;
-                    {
-                        const int x = rr[0][b], y = cr[0][reg];
-                        const bool ok = tri && x >= 0 && y >= 0;
-                        const int lo = min(x, y) - npc[0], hi = max(x, y) - npc[0];
-                        g0[b][reg] = Sc[0][ok ? hi + (size_t)nbc[0] * lo : 0];
-                        if (!ok) g0[b][reg] = 0.0;
-                    }
-                    {
-                        const int x = rr[1][b], y = cr[1][reg];
-                        const bool ok = tri && x >= 0 && y >= 0;
-                        const int lo = min(x, y) - npc[1], hi = max(x, y) - npc[1];
-                        g1[b][reg] = Sc[1][ok ? hi + (size_t)nbc[1] * lo : 0];
-                        if (!ok) g1[b][reg] = 0.0;
-                    }
-                }
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) cv[b][reg] = g0[b][reg] + g1[b][reg];
-            if (mask && bx == 0) {
-                const int* gd = fd.dofs + dp;
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                        const int r = ri + wr + 16 * b + l15;
-                        if (r == cc && cok[reg] && cc < np && mask[gd[r]]) cv[b][reg] = 1.0;
-                    }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                const int r = ri + wr + 16 * b + l15;
-                if (cok[reg] && r < nf && r >= cc) cp[reg][r] = cv[b][reg] - acc[a][b][reg];
-            }
-    }
-}
-
 // ------------------------------------------------------------------------------------------ solves
 // M^-1 = L^-T L^-1 applied level by level.  Each sweep is split per level into a sequential part on
 // the triangular pivot block L11 (one workgroup per front, panels chained through the stored diagonal
@@ -2814,252 +2210,6 @@ k_sweep_bwd_w(FrontDev fd, const int* __restrict__ level_nodes, int first, int n
     const int t = level_nodes[first + blockIdx.y];
     if ((int)blockIdx.x < nx) gemv_t_tile<true>(fd, t, (int)blockIdx.x, y, x);
     else bnd_cols_block<BFLY, true>(fd, t, (int)blockIdx.x - nx, x, x, xs_bnd);     // reads the boundary entries of x, adds to the pivot entries
-}
-
-// ---- the wide levels as ONE launch per sweep direction: tiles as tasks with per-front dependencies.
-// Level by level, a sweep pays two dependent launches per wide level, and the first of the two (the product with X) lasts ~10 us
-// whatever it moves: at 1 M DOF twenty launches per sweep, 0.2 ms of an application of 1.5 ms, with the chip mostly idle.  Here every
-// 128 x 128 tile of X and of L21 (every block of 16 columns in the backward sweep) of ALL consecutive wide levels is one workgroup of
-// one grid, listed in the order the level-wise schedule would run them, and what a launch boundary used to enforce is a counter:
-//   forward    X tiles of front t wait until both children are complete; the L21 tiles of t wait until all X tiles of t have added
-//              their part of y_p -- with their own first 32 loads per thread already in flight;
-//   backward   the column blocks of L21^T x_B of front t wait until the parent is complete, the X^T tiles of t until all column
-//              blocks of t have subtracted their part.
-// Workgroups are dispatched in grid order and every dependency points to an EARLIER workgroup, so a waiting workgroup never
-// waits for one that cannot start.  Memory model (MI355X_MICROARCH.md, inter-workgroup visibility: the per-XCD L2s are not
-// coherent, a CU's L1 is never refreshed): every value that crosses workgroups inside the launch is WRITTEN by an agent-scope
-// atomic add and READ by a returning agent-scope atomic (add of zero) -- both execute at the memory side, never in a cache;
-// a workgroup signals (one lane, agent-scope atomic add on the front's counter) only after every one of its waves has waited
-// for its own atomics (s_waitcnt vmcnt(0)) and a workgroup barrier; the consumer polls the counter with agent-scope loads.
-struct SweepTask { int slot, kt; };                       // position of the front in level_nodes; kind << 24 | tile
-__device__ __host__ inline int sweep_nct(int np) { return (np + 127) / 128; }
-__device__ __host__ inline int sweep_xtiles(int np) { const int n = sweep_nct(np); return n * (n + 1) / 2; }
-__device__ __host__ inline int sweep_ltiles(int np, int nb) { return ((nb + 127) / 128) * sweep_nct(np); }
-constexpr int BB_COLS_F = 16;                             // columns per workgroup of the fused L21^T x_B (== BB_COLS)
-__device__ __host__ inline int sweep_bblocks(int np, int nb) { return nb > 0 ? (np + BB_COLS_F - 1) / BB_COLS_F : 0; }
-
-// Every wait has an exit: after ~4 million polls (seconds; a dependency is microseconds away) the workgroup gives up, poisons what it
-// was about to compute with a NaN -- the Krylov loop then stops with "NaN residual" -- and signals as if it had finished, so that the
-// grid drains whatever went wrong (a workgroup order this code did not expect) instead of hanging the device.
-__device__ __forceinline__ bool sweep_wait(const int* cnt, int want) {
-    for (int it = 0; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want; ++it) {
-        if (it > (1 << 22)) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return true;
-}
-// RM 0: a returning atomic (add of zero): the value as the memory side holds it; RM 1: an agent-scope load (global_load sc1: past
-// this CU's L1); RM 2: a plain load (an experiment: NOT safe across workgroups)
-template <int RM>
-__device__ __forceinline__ double sweep_read(double* p) {
-    if (RM == 0) return __hip_atomic_fetch_add(p, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (RM == 1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-__device__ __forceinline__ void sweep_add(double* p, double v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// every wave's atomics have been acknowledged, then one lane counts the workgroup in
-__device__ __forceinline__ void sweep_signal(int* c0, int* c1) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (c0) __hip_atomic_fetch_add(c0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (c1) __hip_atomic_fetch_add(c1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// forward: y_p = X b_p (kind 0), v_B -= L21 y_p (kind 1).  cnt[2 slot]: X tiles of the front done; cnt[2 slot + 1]: all tiles done.
-template <int RM>
-__global__ void __launch_bounds__(256)
-k_sweep_wide_fwd(FrontDev fd, const int* __restrict__ level_nodes, const SweepTask* __restrict__ tasks, int slot_lo,
-                 const int* __restrict__ slot_of, int* __restrict__ cnt, double* __restrict__ v, double* __restrict__ y) {
-    const SweepTask tk = tasks[blockIdx.x];
-    const int slot = tk.slot, kind = tk.kt >> 24, tile = tk.kt & 0xffffff;
-    const int t = level_nodes[slot];
-    const int np = fd.npiv[t], nf = fd.nf[t];
-    const int nct = sweep_nct(np);
-    const int* gd = fd.dofs + fd.doff[t];
-    int* xdone = cnt + 2 * slot;
-    int* fin = xdone + 1;
-    __shared__ double xs[128];
-    __shared__ double part[128];
-    const int tid = threadIdx.x, lr = tid & 127, ch = tid >> 7;
-    if (kind == 0) {
-        int ti = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
-        while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-        while (ti * (ti + 1) / 2 > tile) --ti;
-        const int tj = tile - ti * (ti + 1) / 2;
-        const int ld = ldx_of(np);
-        const double* M = fd.X + fd.xoff[t];
-        const int r0 = 128 * ti, c0 = 128 * tj, r = r0 + lr;
-        const double* row = M + r;                                 // (r < ld: inside X whatever np is)
-        const int cb0 = c0 + 64 * ch;                              // first column of this thread's half
-        const int cmax = min(np - cb0, 64);
-        const int clim = ti == tj ? min(cmax, lr - 64 * ch + 1) : cmax;
-        // the tile's own entries first (they depend on nothing), then the wait for the children; addresses are clamped into the
-        // front's columns and the values masked where they are used (no load sits in a branch)
-        double a[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) a[k] = row[(size_t)ld * min(cb0 + k, np - 1)];
-        if (tid == 0) {
-            bool ok = true;
-#pragma unroll
-            for (int sd = 0; sd < 2; ++sd) {
-                const int c = fd.child[sd][t];
-                if (c < 0) continue;
-                const int cs = slot_of[c];
-                if (cs < slot_lo) continue;                    // finished by an earlier launch
-                const int cnp = fd.npiv[c];
-                ok = sweep_wait(cnt + 2 * cs + 1, sweep_xtiles(cnp) + sweep_ltiles(cnp, fd.nf[c] - cnp)) && ok;
-            }
-            part[0] = ok ? 0.0 : __builtin_nan("");
-        }
-        __syncthreads();
-        const double poison = part[0];                          // 0, or NaN after a wait that gave up
-        __syncthreads();
-        if (tid < 128) xs[tid] = (c0 + tid < np ? sweep_read<RM>(&v[gd[c0 + tid]]) : 0.0) + poison;
-        __syncthreads();
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s += (r < np && k < clim ? a[k] : 0.0) * xs[64 * ch + k];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) a[k] = row[(size_t)ld * min(cb0 + 32 + k, np - 1)];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s += (r < np && 32 + k < clim ? a[k] : 0.0) * xs[64 * ch + 32 + k];
-        if (ch) part[lr] = s;
-        __syncthreads();
-        if (!ch && r < np) sweep_add(&y[gd[r]], s + part[lr]);
-        sweep_signal(xdone, fin);
-    } else {
-        const int nb = nf - np;
-        const int ti = tile / nct, tj = tile % nct;
-        const int ld = ldp_of(nf);
-        const double* M = fd.P + fd.poff[t] + np;                  // L21 starts at row np of the pivot columns
-        const int cw = ((np + nct - 1) / nct + 1) & ~1, hw = cw / 2;
-        const int r0 = 128 * ti, c0 = cw * tj, r = r0 + lr;
-        const double* row = M + min(r, nb - 1);
-        const int cb0 = c0 + hw * ch;
-        const int clim = min(np - cb0, hw);
-        double a[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) a[k] = row[(size_t)ld * min(cb0 + k, np - 1)];
-        if (tid == 0) part[0] = sweep_wait(xdone, sweep_xtiles(np)) ? 0.0 : __builtin_nan("");
-        __syncthreads();
-        const double poison = part[0];
-        __syncthreads();
-        if (tid < 128) xs[tid] = ((tid < cw && c0 + tid < np) ? sweep_read<RM>(&y[gd[c0 + tid]]) : 0.0) + poison;
-        __syncthreads();
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s += (k < clim ? a[k] : 0.0) * xs[hw * ch + k];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) a[k] = row[(size_t)ld * min(cb0 + 32 + k, np - 1)];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s += (32 + k < clim ? a[k] : 0.0) * xs[hw * ch + 32 + k];
-        if (ch) part[lr] = s;
-        __syncthreads();
-        if (!ch && r < nb) sweep_add(&v[gd[np + r]], -(s + part[lr]));
-        sweep_signal(nullptr, fin);
-    }
-}
-
-// backward: s_p = y_p - L21^T x_B (kind 0, one workgroup per 16 pivot columns), x_p = X^T s_p (kind 1).
-// cnt[2 slot]: column blocks of the front done; cnt[2 slot + 1]: X^T tiles done (the front is complete when all are).
-template <int RM>
-__global__ void __launch_bounds__(256)
-k_sweep_wide_bwd(FrontDev fd, const int* __restrict__ level_nodes, const SweepTask* __restrict__ tasks, int slot_hi,
-                 const int* __restrict__ slot_of, int* __restrict__ cnt, double* __restrict__ sv, double* __restrict__ xv) {
-    const SweepTask tk = tasks[blockIdx.x];
-    const int slot = tk.slot, kind = tk.kt >> 24, tile = tk.kt & 0xffffff;
-    const int t = level_nodes[slot];
-    const int np = fd.npiv[t], nf = fd.nf[t];
-    const int nb = nf - np;
-    const int* gd = fd.dofs + fd.doff[t];
-    int* bdone = cnt + 2 * slot;
-    int* xfin = bdone + 1;
-    extern __shared__ double xsd[];                       // kind 0: nb doubles (x_B); kind 1: 128
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (kind == 0) {
-        const int c0 = tile * BB_COLS_F;
-        const int ldp = ldp_of(nf);
-        const double* L21 = fd.P + fd.poff[t] + np;
-        const int cb = c0 + 4 * wv;
-        const double* col[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) col[k] = L21 + (size_t)ldp * min(cb + k, np - 1);
-        // the first 512 rows of the wave's four columns are requested before the wait
-        double a[4][8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a[k][u] = col[k][min(lane + 64 * u, nb - 1)];
-        __shared__ double poison_s;
-        if (tid == 0) {
-            const int p = fd.parent[t];
-            bool ok = true;
-            if (p >= 0 && slot_of[p] < slot_hi) ok = sweep_wait(cnt + 2 * slot_of[p] + 1, sweep_xtiles(fd.npiv[p]));
-            poison_s = ok ? 0.0 : __builtin_nan("");
-        }
-        __syncthreads();
-        for (int r = tid; r < nb; r += 256) xsd[r] = sweep_read<RM>(&xv[gd[np + r]]) + poison_s;
-        __syncthreads();
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int rb = 0; rb < nb; rb += 512) {
-            if (rb > 0) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) a[k][u] = col[k][min(rb + lane + 64 * u, nb - 1)];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int r = rb + lane + 64 * u;
-                const double xr = r < nb ? xsd[r] : 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s[k] += a[k][u] * xr;
-            }
-        }
-        int k;
-        const double tot = wave_sum_cols<4>(s, lane, k);
-        if (!(lane & 15) && cb + k < np) sweep_add(&sv[gd[cb + k]], -tot);
-        sweep_signal(bdone, nullptr);
-    } else {
-        int ti = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
-        while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-        while (ti * (ti + 1) / 2 > tile) --ti;
-        const int tj = tile - ti * (ti + 1) / 2;
-        const int ld = ldx_of(np);
-        const double* M = fd.X + fd.xoff[t];
-        const int r0 = 128 * ti, c0 = 128 * tj;
-        const int ra = r0 + lane, rb = r0 + lane + 64;
-        double a0[32], a1[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-            const int c = c0 + 32 * wv + k;
-            const double* colp = M + (size_t)ld * min(c, np - 1);
-            a0[k] = colp[min(ra, np - 1)];
-            a1[k] = colp[min(rb, np - 1)];
-        }
-        __shared__ double poison_x;
-        if (tid == 0) poison_x = sweep_wait(bdone, sweep_bblocks(np, nb)) ? 0.0 : __builtin_nan("");
-        __syncthreads();
-        if (tid < 128) xsd[tid] = (r0 + tid < np ? sweep_read<RM>(&sv[gd[r0 + tid]]) : 0.0) + poison_x;
-        __syncthreads();
-        const double x0 = xsd[lane], x1 = xsd[lane + 64];
-        double p[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-            const int c = c0 + 32 * wv + k;
-            const bool ca = c < np && ra < np && ra >= c, cbb = c < np && rb < np && rb >= c;     // triangular: rows >= column
-            p[k] = (ca ? a0[k] : 0.0) * x0 + (cbb ? a1[k] : 0.0) * x1;
-        }
-        int colw;
-        const double sum = wave_sum_cols<32>(p, lane, colw);
-        const int c = c0 + 32 * wv + colw;
-        if (!(lane & 1) && c < np) sweep_add(&xv[gd[c]], sum);
-        sweep_signal(nullptr, xfin);
-    }
 }
 
 // X = L11^-1 beyond its 128 x 128 diagonal blocks (which k_diag_block leaves in place), by recursive doubling: at block

@@ -191,12 +191,11 @@ SCHEDULES = [
     ("super_panel 256 ahead", dict(SP, super_panel=256, super_panel_ahead=1)),
     ("super_panel 512 ahead", dict(SP, super_panel=512, super_panel_ahead=1)),
     ("super_panel 384 diag_ahead", dict(SP, super_panel=384, diag_ahead=1, rows_preload_wg=100000, narrow_split=4, narrow_split_wg=100000)),
-    ("diag_t 1", dict(diag_t=1)), ("diag_t 2", dict(diag_t=2)),
     ("diag_v1 1", dict(diag_v1=1, diag_v1_cnt=1)), ("diag_v1 2", dict(diag_v1=2, diag_v1_cnt=1)),
-    ("big_tiles", dict(big_tiles=1, big_min_wg=1)), ("super_tiles", dict(super_tiles=1, super_tiles_min=1)),
+    ("super_tiles", dict(super_tiles=1, super_tiles_min=1)),
     ("fuse_rows 0", dict(fuse_rows=0)), ("fuse_rows everywhere", dict(fuse_rows=1, fuse_rows_cnt=1, fuse_rows_np=256)),
     ("split 3 groups", dict(split_cnt=100000, split_groups=3)), ("narrow_split 4", dict(narrow_split=4, narrow_split_wg=100000)),
-    ("strip", dict(strip_cnt=1)), ("rows fine / preload", dict(rows_fine_wg=100000, rows_preload_wg=100000, narrow_fine_wg=100000)),
+    ("rows fine / preload", dict(rows_fine_wg=100000, rows_preload_wg=100000, narrow_fine_wg=100000)),
     ("lookahead 0", dict(trailing=2, lookahead=0, super_panel=0)), ("lookahead 1", dict(trailing=2, lookahead=1, lookahead_cnt=1000, super_panel=0)),
     ("fused_schur 0", dict(fused_schur=0)),
     ("grid_chunk 3", dict(grid_chunk=3)), ("xinv_small_cnt 0", dict(xinv_small_cnt=0)), ("xinv_small_cnt all", dict(xinv_small_cnt=100000)),
@@ -238,7 +237,7 @@ def test_factorisation_schedules(name):
 # ------------------------------------------------------------------ sweeps
 SWEEPS_PRE = [("wide_cnt 0", dict(wide_cnt=0)), ("wide_cnt 100000", dict(wide_cnt=100000)), ("wide_np 64", dict(wide_np=64)),
               ("wide_np 100000", dict(wide_np=100000)), ("no wide level", dict(wide_np=100000, wide_cnt=0))]
-SWEEPS_POST = [("bnd_tiled_nb 0", dict(bnd_tiled_nb=0)), ("sweep_fuse", dict(sweep_fuse=1)), ("sweep_w", dict(sweep_w=1))] + \
+SWEEPS_POST = [("bnd_tiled_nb 0", dict(bnd_tiled_nb=0)), ("sweep_w", dict(sweep_w=1))] + \
               [(f"sweep_butterfly {b}", dict(sweep_butterfly=b)) for b in range(4)] + \
               [("sweep_graph 0", dict(sweep_graph=0)), ("sweep_graph 1", dict(sweep_graph=1))]
 
@@ -366,7 +365,7 @@ def test_nan_right_hand_side_is_an_error(nrhs):
 
 # ------------------------------------------------------------------ per-front Schur blocks, level by level
 @pytest.mark.parametrize("name", ["plate_small", "wing_small"])
-@pytest.mark.parametrize("sched", ["default", "trailing 2 super_panel 256", "diag_t 1"])
+@pytest.mark.parametrize("sched", ["default", "trailing 2 super_panel 256"])
 def test_schur_blocks_level_by_level(name, sched):
     """After femo_factorize_range(l, l + 1) the Schur block of every front of level l is D - B A^-1 B^T of its subtree's own matrix
     (the element matrices of the subtree's cells; strong-BC rows and columns emptied, a unit diagonal where a constrained DOF is
@@ -380,7 +379,7 @@ def _schur_blocks_level_by_level(name, sched, leaf=8):
     import scipy.sparse.linalg as spla
     import torch
     from oracle.rm_shell_oracle import ShellOracle
-    post = {"default": {}, "trailing 2 super_panel 256": dict(trailing=2, super_panel=256, super_panel_cnt=100000), "diag_t 1": dict(diag_t=1)}[sched]
+    post = {"default": {}, "trailing 2 super_panel 256": dict(trailing=2, super_panel=256, super_panel_cnt=100000)}[sched]
     m, K, c = _context(name, leaf, post=post)
     pivot_free = 0
     try:
