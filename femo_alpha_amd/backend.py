@@ -64,6 +64,7 @@ class ShellContext:
         # schedule experiments without touching the caller: FEMO_OPTIONS="sweep_graph=1,super_tiles=1" sets those options on every context
         import os
         self.env_options = {}
+        self.tail_max = None              # plan option "tail_max": None = the package's default (solver.symbolic.TAIL_MAX)
         for kv in filter(None, (t.strip() for t in os.environ.get("FEMO_OPTIONS", "").split(","))):
             k, sep, v = kv.partition("=")
             try:
@@ -95,8 +96,15 @@ class ShellContext:
         'split_cnt', 'split_groups', 'super_tiles', 'super_tiles_min', 'diag_v1', 'diag_v1_cnt', 'xinv_small_cnt', 'grid_chunk',
         'assemble_fc', 'precond_nquad', 'equilibrate'.  Sweeps and solves: 'sweep_graph', 'sweep_ahead', 'sweep_w', 'sweep_butterfly',
         'bnd_tiled_nb', 'multi_rhs', 'apply_lanes', 'stale_factor', 'stale_rel'.  Before the frontal plan is set: 'wide_np', 'wide_cnt',
-        'swork_slots'.  Outputs and profiling: 'stress_regularization', 'stress_history_levels_per_thread', 'stress_history_chunk',
+        'swork_slots', 'tail_max' (the tail-delay pass of the symbolic analysis, solver.symbolic.build_plan: the longest last outer
+        panel, in pivot DOFs, that a tree level hands to its parents; 0 = off, default 32; kept on the Python side, where the plan is
+        built).  Outputs and profiling: 'stress_regularization', 'stress_history_levels_per_thread', 'stress_history_chunk',
         'disp_history_chunk', 'profile', 'profile_verbose'.  An unknown name raises FemoHipError."""
+        if key == "tail_max":
+            if float(value) < 0 or float(value) != int(value):
+                raise FemoHipError("option 'tail_max' takes a non-negative whole number of DOFs (0 = off)")
+            self.tail_max = int(value)
+            return
         self._chk(self.lib.femo_set_option(self._h, key.encode(), float(value)))
 
     def close(self):
@@ -335,14 +343,16 @@ class ShellContext:
         """Run the symbolic analysis on the host (mesh only) and upload it; afterwards
         ``set_solver(preconditioner=2)`` selects the multifrontal Cholesky preconditioner.
         ``plan`` may carry a ready-made plan (the multi-GPU driver passes rank-local plans);
-        ``options`` are plan-shaping switches set before the upload (``wide_np``, ``wide_cnt``)."""
+        ``options`` are plan-shaping switches set before the upload (``wide_np``, ``wide_cnt``, ``tail_max``).  The plan is built
+        with the tail-delay pass on (``tail_max`` 32 unless the option says otherwise); ``self.plan`` is the plan in use."""
         import time
-        from .solver.symbolic import build_plan
+        from .solver.symbolic import TAIL_MAX, build_plan
         leaf_size = self.mesh.recommended_leaf_size() if leaf_size is None else int(leaf_size)
         for k, v in options.items():
             self.set_option(k, v)
         t0 = time.perf_counter()
-        plan = self.plan = build_plan(self.mesh, leaf_size) if plan is None else plan
+        tail_max = TAIL_MAX if self.tail_max is None else self.tail_max
+        plan = self.plan = build_plan(self.mesh, leaf_size, tail_max=tail_max) if plan is None else plan
         self.symbolic_s = time.perf_counter() - t0
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)

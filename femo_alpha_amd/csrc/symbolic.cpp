@@ -58,7 +58,13 @@ int femo_plan_build_ex(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, in
 int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, int32_t npc, int32_t ndpc, const int32_t* cell_p2,
                         const double* cent, const double* cext, const int32_t* cell_dofs, int32_t leaf_size, int32_t min_depth,
                         int32_t axis_rule, double gap_coeff, int32_t node_order) {
-    if (!out || node_order < 0 || node_order > 1 || nel < 1 || nP2 < 1 || nV < 1 || npc < 1 || ndpc < 1 || !cell_p2 || !cent || !cell_dofs || leaf_size < 1 || min_depth < 0 ||
+    return femo_tail_delay_plan_build(out, nel, nP2, nV, npc, ndpc, cell_p2, cent, cext, cell_dofs, leaf_size, min_depth, axis_rule, gap_coeff, node_order, 0);
+}
+
+int femo_tail_delay_plan_build(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, int32_t npc, int32_t ndpc, const int32_t* cell_p2,
+                               const double* cent, const double* cext, const int32_t* cell_dofs, int32_t leaf_size, int32_t min_depth,
+                               int32_t axis_rule, double gap_coeff, int32_t node_order, int32_t tail_max) {
+    if (!out || tail_max < 0 || node_order < 0 || node_order > 1 || nel < 1 || nP2 < 1 || nV < 1 || npc < 1 || ndpc < 1 || !cell_p2 || !cent || !cell_dofs || leaf_size < 1 || min_depth < 0 ||
         axis_rule < 0 || axis_rule > 2 || (axis_rule >= 1 && !cext) || !(gap_coeff >= 0.0)) {
         g_error = "femo_plan_build: bad arguments";
         return 1;
@@ -317,6 +323,109 @@ int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, i
             }
         }
     }
+    // ---- 3b. tail delay (tail_max > 0): whole levels hand the pivots of a short last outer panel to their parents.
+    //   The numeric phase factorises a level in lock-step, one chain step (diagonal block, rows below, update) per outer panel of
+    //   NBO = 128 columns, ceil(max npiv / 128) steps however few columns the last one holds.  A pivot may always be eliminated later,
+    //   at the parent: it is fully assembled in the child, stays there as a boundary row and becomes a pivot of the parent.  So, bottom-up
+    //   and level by level: with P = ceil(max npiv / 128) >= 2 and tail_t = max(0, npiv_t - 128 (P - 1)), EVERY front of the level with a
+    //   tail delays its last pivot nodes (whole nodes: the fewest that hold at least tail_t DOFs) -- if
+    //     * no tail is longer than tail_max DOFs,
+    //     * every such front may delay (it lies below min_depth: the partition boundary of the multi-GPU driver; the root never does),
+    //     * no level that receives pivots gets a further panel (the saved step would be paid back there; a level that already received
+    //       pivots is measured as it stands now, so no level ever has more panels than without the pass), and
+    //     * the factorisation's flop count stays within 1 % of the plan's without the pass (3 x flops in integers: exact, and the same
+    //       decision in the numpy twin).
+    //   The delayed nodes go IN FRONT of the parent's own pivots (left child's, then right child's, each in the child's order): the
+    //   parent's own tail stays its own separator end, and a child's rows of the parent's group are one more run, not a split of one.
+    //   Owners and ranks are updated, so the owner-grouped boundary order below holds for every descendant as it stands.
+    auto ndofs_of = [&](int32_t n) { return n < nV ? 6 : 3; };
+    int32_t nlevels = 0;
+    for (int32_t t = 0; t < ntree; ++t) nlevels = std::max(nlevels, height[t] + 1);
+    std::vector<int64_t> td_dofs(nlevels, 0), td_flops3(2, 0);
+    std::vector<int32_t> td_saved(nlevels, 0);
+    if (tail_max > 0) {
+        constexpr int64_t NBO = 128;
+        std::vector<int64_t> np(ntree, 0), nfv(ntree, 0);
+        std::vector<std::vector<int32_t>> piv(ntree), by_height(nlevels);
+        auto flops3 = [](int64_t a, int64_t f) { return 3 * a * f * f - 3 * a * a * f + a * a * a; };
+        int64_t F0 = 0;
+        std::vector<int64_t> lev_max(nlevels, 0);
+        for (int32_t t = 0; t < ntree; ++t) {
+            piv[t].assign(piv_nodes.begin() + piv_off[t], piv_nodes.begin() + piv_off[t + 1]);
+            for (int32_t n : piv[t]) np[t] += ndofs_of(n);
+            nfv[t] = np[t];
+            for (int32_t n : bnd[t]) nfv[t] += ndofs_of(n);
+            F0 += flops3(np[t], nfv[t]);
+            by_height[height[t]].push_back(t);
+            lev_max[height[t]] = std::max(lev_max[height[t]], np[t]);
+        }
+        int64_t F = F0;
+        auto panels = [&](int64_t m) { return (m + NBO - 1) / NBO; };
+        struct Move { int32_t t; int32_t nnodes; int64_t dofs; };
+        std::vector<int64_t> add(ntree, 0);
+        std::vector<std::vector<int32_t>> recv(ntree);
+        for (int32_t h = 0; h + 1 < nlevels; ++h) {
+            const int64_t P = panels(lev_max[h]);
+            if (P < 2) continue;
+            const int64_t keep = NBO * (P - 1);
+            std::vector<Move> mv;
+            std::vector<int32_t> par;              // the receiving parents, ascending (children of one parent are neighbours in id)
+            bool ok = true;
+            for (int32_t t : by_height[h]) {
+                const int64_t tail = np[t] - keep;
+                if (tail <= 0) continue;
+                if (tail > tail_max || parent[t] < 0 || depth[t] <= min_depth) { ok = false; break; }
+                int64_t got = 0;
+                int32_t cnt = 0;
+                for (int64_t i = (int64_t)piv[t].size() - 1; got < tail; --i) { got += ndofs_of(piv[t][i]); ++cnt; }
+                mv.push_back({t, cnt, got});
+                if (add[parent[t]] == 0) par.push_back(parent[t]);
+                add[parent[t]] += got;
+            }
+            int64_t Fn = F;
+            if (ok) {
+                std::vector<int64_t> grown(lev_max);
+                for (int32_t p : par) grown[height[p]] = std::max(grown[height[p]], np[p] + add[p]);
+                for (int32_t p : par)
+                    if (panels(grown[height[p]]) > panels(lev_max[height[p]])) ok = false;
+                for (const Move& m : mv) Fn += flops3(np[m.t] - m.dofs, nfv[m.t]) - flops3(np[m.t], nfv[m.t]);
+                for (int32_t p : par) Fn += flops3(np[p] + add[p], nfv[p] + add[p]) - flops3(np[p], nfv[p]);
+                if (100 * Fn > 101 * F0) ok = false;
+            }
+            if (ok) {
+                for (const Move& m : mv) {
+                    const int32_t t = m.t, p = parent[t];
+                    for (size_t i = piv[t].size() - m.nnodes; i < piv[t].size(); ++i) {
+                        const int32_t n = piv[t][i];
+                        owner[n] = p; recv[p].push_back(n); bnd[t].push_back(n);
+                    }
+                    piv[t].resize(piv[t].size() - m.nnodes);
+                    std::sort(bnd[t].begin(), bnd[t].end());
+                    np[t] -= m.dofs;
+                    td_dofs[h] += m.dofs;
+                }
+                for (int32_t p : par) {
+                    recv[p].insert(recv[p].end(), piv[p].begin(), piv[p].end());
+                    piv[p].swap(recv[p]);
+                    recv[p].clear();
+                    np[p] += add[p]; nfv[p] += add[p];
+                    lev_max[height[p]] = std::max(lev_max[height[p]], np[p]);
+                }
+                lev_max[h] = 0;
+                for (int32_t t : by_height[h]) lev_max[h] = std::max(lev_max[h], np[t]);
+                td_saved[h] = (int32_t)(P - panels(lev_max[h]));
+                F = Fn;
+            }
+            for (int32_t p : par) add[p] = 0;
+        }
+        td_flops3[0] = F0; td_flops3[1] = F;
+        for (int32_t t = 0; t < ntree; ++t) {
+            piv_off[t + 1] = piv_off[t] + (int64_t)piv[t].size();
+            std::copy(piv[t].begin(), piv[t].end(), piv_nodes.begin() + piv_off[t]);
+            if (node_order == 1)
+                for (size_t i = 0; i < piv[t].size(); ++i) rank[piv[t][i]] = (int32_t)i;
+        }
+    }
     if (node_order == 1) {
         // (the unions above need the lists in ascending id; the order of the rows is settled here, once every list is complete)
 #pragma omp parallel for num_threads(nthreads) schedule(dynamic, 64)
@@ -331,7 +440,6 @@ int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, i
     std::vector<int32_t> bnd_nodes(bnd_off[ntree]);
     for (int32_t t = 0; t < ntree; ++t) std::copy(bnd[t].begin(), bnd[t].end(), bnd_nodes.begin() + bnd_off[t]);
     // ---- front DOF lists: pivots first, then the boundary; a vertex node carries u and theta (6 DOFs), the others u (3)
-    auto ndofs_of = [&](int32_t n) { return n < nV ? 6 : 3; };
     std::vector<int32_t> npiv(ntree), nf(ntree);
     std::vector<int64_t> dof_off(ntree + 1, 0);
     for (int32_t t = 0; t < ntree; ++t) {
@@ -390,8 +498,6 @@ int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, i
     }
     if (bad) { g_error = "a boundary or element DOF is missing from the front that should hold it"; return 5; }
     // levels by height; inside a level the largest fronts first (stable)
-    int32_t nlevels = 0;
-    for (int32_t t = 0; t < ntree; ++t) nlevels = std::max(nlevels, height[t] + 1);
     std::vector<int64_t> level_off(nlevels + 1, 0);
     for (int32_t t = 0; t < ntree; ++t) ++level_off[height[t] + 1];
     for (int32_t h = 0; h < nlevels; ++h) level_off[h + 1] += level_off[h];
@@ -413,6 +519,8 @@ int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, i
     p->i32["front_dofs"] = std::move(front_dofs); p->i32["up_map"] = std::move(up_map);
     p->i32["elem_front"] = std::move(elem_front); p->i32["elem_map"] = std::move(elem_map);
     p->i32["level_nodes"] = std::move(level_nodes); p->i64["level_off"] = std::move(level_off);
+    p->i64["tail_delay_dofs"] = std::move(td_dofs); p->i32["tail_delay_saved"] = std::move(td_saved);
+    p->i64["tail_delay_flops3"] = std::move(td_flops3);
     *out = p;
     return 0;
 }

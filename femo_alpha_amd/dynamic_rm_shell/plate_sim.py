@@ -31,7 +31,7 @@ from ..backend import ShellContext
 
 class PlateSim:
     def __init__(self, mesh, E, nu, rho, dt, Nsteps, element_wise_thickness=False, custom_bc_func=None,
-                 add_self_weight=False, g_factor=None, quad_deg=3, comm=None, device=0, leaf_size=None, rtol=1e-8):
+                 add_self_weight=False, g_factor=None, quad_deg=3, comm=None, device=0, leaf_size=None, rtol=1e-8, tail_max=None):
         import torch
         self.torch = torch
         self.mesh, self.E, self.nu, self.rho, self.dt = mesh, E, nu, rho, dt
@@ -50,7 +50,8 @@ class PlateSim:
         npts = (quad_deg + 2) // 2                                       # Gauss points per direction for that degree
         if mesh.is_quad and npts < 4:
             ctx.set_strain_quadrature(npts)
-        ctx.enable_frontal(leaf_size)
+        # tail_max: the tail-delay pass of the symbolic analysis (None: the context's default, on; 0: off)
+        ctx.enable_frontal(leaf_size, **({} if tail_max is None else dict(tail_max=tail_max)))
         # The reference solves every step with ONE sparse LU solve (solveNonlinear_mod: a single Newton iteration,
         # nonlinear_utils.py:220-229).  Here the preconditioner is the exact Cholesky factor of the step operator: its first
         # application is that direct solve (relative residual 6e-9 at 508 k DOF, the history within 7e-10 of the fully converged

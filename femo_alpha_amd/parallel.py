@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .solver.symbolic import analyse, rank_plan
+from .solver.symbolic import TAIL_MAX, analyse, rank_plan
 
 __all__ = ["Comm", "HipEngine", "DistributedShell"]
 
@@ -170,7 +170,7 @@ class DistributedShell:
     """Forward solve, scalar outputs and the adjoint gradient on an element partition."""
 
     def __init__(self, mesh, comm: Comm, bc_marker=None, beta=1.0e15, leaf_size=None, engine_factory=None,
-                 element_wise_material=False, device=0, tree=None, nquad=None, strict=True):
+                 element_wise_material=False, device=0, tree=None, nquad=None, strict=True, tail_max=None):
         import torch
         self.torch = torch
         self.strict = bool(strict)       # a PCG that stops at maxit short of rtol raises (option "strict" of the single-GPU path)
@@ -178,7 +178,13 @@ class DistributedShell:
         self.ewm = bool(element_wise_material)
         d = int(np.log2(comm.size))
         leaf_size = mesh.recommended_leaf_size() if leaf_size is None else int(leaf_size)
-        self.tree = analyse(mesh, leaf_size, min_depth=d) if tree is None else tree
+        # the tail-delay pass of the analysis (on by default, FEMO_OPTIONS "tail_max" as on a single context) works below the partition
+        # depth only: the subtree roots, their Schur blocks and the replicated top are what they are without it
+        if tail_max is None:
+            import os
+            env = dict(kv.split("=", 1) for kv in os.environ.get("FEMO_OPTIONS", "").replace(" ", "").split(",") if "=" in kv)
+            tail_max = int(float(env["tail_max"])) if "tail_max" in env else TAIL_MAX
+        self.tree = analyse(mesh, leaf_size, min_depth=d, tail_max=tail_max) if tree is None else tree
         self.sub, self.plan, self.info = rank_plan(mesh, self.tree, comm.rank, comm.size)
         self._rule_auto = nquad is None
         self.nquad = mesh.recommended_nquad() if nquad is None else int(nquad)

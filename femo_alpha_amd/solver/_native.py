@@ -24,9 +24,15 @@ SIGNATURES = {
     "femo_plan_last_error": (C.c_char_p, []),
 }
 
+# the entry point with the tail-delay pass: the plan builders' arguments and tail_max.  Its own table: SIGNATURES is the femo_plan_*
+# family, whose members tests/test_cabi.py counts
+TAIL_DELAY_SIGNATURES = {
+    "femo_tail_delay_plan_build": (C.c_int, SIGNATURES["femo_plan_build_ex2"][1] + [C.c_int32]),
+}
+
 ARRAYS = ("lo", "hi", "left", "right", "parent", "depth", "height", "eorder", "epos", "owner", "piv_nodes", "piv_off",
           "bnd_nodes", "bnd_off", "npiv", "nf", "dof_off", "front_dofs", "up_map", "elem_front", "elem_map", "level_nodes",
-          "level_off")
+          "level_off", "tail_delay_dofs", "tail_delay_saved", "tail_delay_flops3")
 
 
 def load():
@@ -34,19 +40,20 @@ def load():
     if _lib is None:
         path = _build.build_symbolic() if _build.symbolic_needs_build() else _build.SYM_LIB
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **TAIL_DELAY_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
 
 
-def plan_arrays(mesh, leaf_size, min_depth=0, axis_rule=0, gap=0.0, node_order=0):
+def plan_arrays(mesh, leaf_size, min_depth=0, axis_rule=0, gap=0.0, node_order=0, tail_max=0):
     """All arrays of include/femo_symbolic.h for ``mesh`` as a dict of numpy arrays.
 
     The library assumes that the P2 nodes below ``nV`` carry six DOFs (u and theta) and the others three.  For CG2CR1 the rotation
     lives on the EDGE nodes, so the mesh is handed over with its P2 nodes relabelled -- edge midpoints first (they are the "vertices"
-    of that layout), vertices behind them -- and the node and DOF numbers of the result are mapped back."""
+    of that layout), vertices behind them -- and the node and DOF numbers of the result are mapped back.  ``tail_max``: the
+    tail-delay pass of femo_tail_delay_plan_build (0 = off)."""
     lib = load()
     cr = getattr(mesh, "element", "") == "CG2CR1"
     nV_lib = mesh.nE if cr else mesh.nV
@@ -66,9 +73,11 @@ def plan_arrays(mesh, leaf_size, min_depth=0, axis_rule=0, gap=0.0, node_order=0
     cext = np.ascontiguousarray(xc.max(axis=1) - xc.min(axis=1), dtype=np.float64)
     h = C.c_void_p()
     dp = C.POINTER(C.c_double)
-    rc = lib.femo_plan_build_ex2(C.byref(h), mesh.nel, mesh.nP2, nV_lib, cell_p2.shape[1], cell_dofs.shape[1],
-                                 cell_p2.ctypes.data_as(_i32p), cent.ctypes.data_as(dp), cext.ctypes.data_as(dp),
-                                 cell_dofs.ctypes.data_as(_i32p), int(leaf_size), int(min_depth), int(axis_rule), float(gap), int(node_order))
+    args = (C.byref(h), mesh.nel, mesh.nP2, nV_lib, cell_p2.shape[1], cell_dofs.shape[1],
+            cell_p2.ctypes.data_as(_i32p), cent.ctypes.data_as(dp), cext.ctypes.data_as(dp),
+            cell_dofs.ctypes.data_as(_i32p), int(leaf_size), int(min_depth), int(axis_rule), float(gap), int(node_order))
+    # tail_max None: the entry point without the tail-delay pass (the tests compare it with tail_max 0 of the newer one)
+    rc = lib.femo_plan_build_ex2(*args) if tail_max is None else lib.femo_tail_delay_plan_build(*args, int(tail_max))
     if rc:
         msg = lib.femo_plan_last_error().decode()
         raise ValueError(msg) if rc == 2 else RuntimeError(msg)

@@ -35,10 +35,17 @@ class FrontalPlan:
         nf, npv = self.nf, self.npiv
         flops = float(np.sum(npv.astype(np.float64) * nf.astype(np.float64) ** 2
                              - npv.astype(np.float64) ** 2 * nf + npv.astype(np.float64) ** 3 / 3.0))
-        return dict(fronts=int(self.ntree), levels=int(self.nlevels), leaves=int(self.nleaves),
-                    max_front=int(nf.max()), max_pivots=int(npv.max()),
-                    front_doubles=int(self.front_off[-1]), front_GB=float(self.front_off[-1] * 8 / 1e9),
-                    factor_doubles=int(np.sum(nf.astype(np.int64) * npv)), factor_gflop=flops / 1e9)
+        out = dict(fronts=int(self.ntree), levels=int(self.nlevels), leaves=int(self.nleaves),
+                   max_front=int(nf.max()), max_pivots=int(npv.max()),
+                   front_doubles=int(self.front_off[-1]), front_GB=float(self.front_off[-1] * 8 / 1e9),
+                   factor_doubles=int(np.sum(nf.astype(np.int64) * npv)), factor_gflop=flops / 1e9)
+        td = getattr(self, "tail_delay", None)
+        if td is not None and int(np.sum(td["saved"])):
+            # the tail-delay pass: DOFs handed to the parents, chain steps saved per level, flops against the plan without the pass
+            f0, f1 = td["flops3"]
+            out.update(delayed_dofs=int(np.sum(td["dofs"])), panels_saved={int(h): int(s) for h, s in enumerate(td["saved"]) if s},
+                       delay_flop_change=float(f1 - f0) / float(f0))
+        return out
 
 
 class Tree:
@@ -87,7 +94,12 @@ def _tree_from_native(A) -> Tree:
     pn, bn = A["piv_nodes"].astype(np.int64), A["bnd_nodes"].astype(np.int64)
     T.piv_nodes = [pn[po[t]:po[t + 1]] for t in range(T.ntree)]
     T.bnd_nodes = [bn[bo[t]:bo[t + 1]] for t in range(T.ntree)]
+    T.tail_delay = _tail_delay_native(A)
     return T
+
+
+def _tail_delay_native(A):
+    return dict(dofs=A["tail_delay_dofs"], saved=A["tail_delay_saved"], flops3=tuple(int(v) for v in A["tail_delay_flops3"]))
 
 
 # Rules of the bisection (csrc/symbolic.cpp, femo_plan_build_ex).  AXIS_RULE 1: cut across the axis along which a piece is longest in
@@ -105,15 +117,16 @@ GAP_NMIN = 128
 AXIS_NMIN = 16         # rule 2 measures the separators of pieces of at least this many cells
 
 
-def analyse(mesh, leaf_size=12, min_depth=0, impl="native", axis_rule=None, gap=None, node_order=None) -> Tree:
+def analyse(mesh, leaf_size=12, min_depth=0, impl="native", axis_rule=None, gap=None, node_order=None, tail_max=0) -> Tree:
     """Bisection tree, node ownership and boundary lists.  ``min_depth`` forces every branch to be
-    split at least that deep (the multi-GPU driver needs 2^d subtrees)."""
+    split at least that deep (the multi-GPU driver needs 2^d subtrees).  ``tail_max`` > 0 runs the tail-delay pass
+    (``_tail_delay``) on the fronts below ``min_depth``: the subtree roots of a partition and the replicated top stay as they are."""
     axis_rule = AXIS_RULE if axis_rule is None else int(axis_rule)
     gap = GAP if gap is None else float(gap)
     node_order = NODE_ORDER if node_order is None else int(node_order)
     if impl == "native":
         from . import _native
-        return _tree_from_native(_native.plan_arrays(mesh, leaf_size, min_depth, axis_rule, gap, node_order))
+        return _tree_from_native(_native.plan_arrays(mesh, leaf_size, min_depth, axis_rule, gap, node_order, tail_max))
     if getattr(mesh, "element", "") == "CG2CR1":
         raise NotImplementedError("the numpy twin of the analysis knows the vertex-rotation layouts only; CG2CR1 goes through the native library")
     nel, nP2 = mesh.nel, mesh.nP2
@@ -254,19 +267,89 @@ def analyse(mesh, leaf_size=12, min_depth=0, impl="native", axis_rule=None, gap=
         nc = np.zeros((nP2, 3))
         np.add.at(nc, mesh.cell_p2.ravel(), np.repeat(cent, mesh.cell_p2.shape[1], axis=0))      # sequential, (cell, local node) order
         nc /= np.maximum(np.bincount(mesh.cell_p2.ravel(), minlength=nP2), 1)[:, None]
-        rank = np.zeros(nP2, dtype=np.int64)
         for t in range(T.ntree):
             p = T.piv_nodes[t]
             if p.size > 1:
                 ax = int(np.argmax(nc[p].max(axis=0) - nc[p].min(axis=0)))
-                p = p[np.argsort(nc[p, ax], kind="stable")]
-                T.piv_nodes[t] = p
-            rank[p] = np.arange(p.size)
+                T.piv_nodes[t] = p[np.argsort(nc[p, ax], kind="stable")]
+    T.tail_delay = _tail_delay(T, bnd, mesh.nV, int(min_depth), int(tail_max))
+    if node_order == 1:
+        rank = np.zeros(nP2, dtype=np.int64)
+        for t in range(T.ntree):
+            rank[T.piv_nodes[t]] = np.arange(T.piv_nodes[t].size)
         for t in range(T.ntree):
             b = bnd[t]
             bnd[t] = b[np.lexsort((rank[b], -T.depth[owner[b]]))]
     T.bnd_nodes = bnd
     return T
+
+
+NBO = 128        # columns of an outer panel of the numeric phase (csrc/frontal.h): a level takes ceil(max npiv / NBO) chain steps
+TAIL_MAX = 32    # tail-delay pass: the longest last panel (DOFs) a level hands to its parents; what the solver contexts switch on
+
+
+def _tail_delay(T, bnd, nV, min_depth, tail_max):
+    """The tail-delay pass of csrc/symbolic.cpp (section 3b there states the rule), on the lists of ``T`` and ``bnd`` (ascending ids,
+    before the rows are ordered), in place.  Returns per level the DOFs handed up and the chain steps saved, and three times the
+    factorisation's flops without and with the pass (integers)."""
+    nlev = int(T.height.max()) + 1
+    dofs, saved = np.zeros(nlev, dtype=np.int64), np.zeros(nlev, dtype=np.int32)
+    if tail_max <= 0:
+        return dict(dofs=dofs, saved=saved, flops3=(0, 0))
+    nd = lambda a: int(np.where(np.asarray(a) < nV, 6, 3).sum())
+    flops3 = lambda a, f: 3 * a * f * f - 3 * a * a * f + a * a * a
+    panels = lambda m: (m + NBO - 1) // NBO
+    npv = [nd(T.piv_nodes[t]) for t in range(T.ntree)]
+    nfv = [npv[t] + nd(bnd[t]) for t in range(T.ntree)]
+    F0 = F = sum(flops3(a, f) for a, f in zip(npv, nfv))
+    by_height = [np.nonzero(T.height == h)[0] for h in range(nlev)]
+    lev_max = [max(npv[t] for t in by_height[h]) for h in range(nlev)]
+    for h in range(nlev - 1):
+        P = panels(lev_max[h])
+        if P < 2:
+            continue
+        keep = NBO * (P - 1)
+        mv, add, ok = [], {}, True
+        for t in by_height[h]:
+            tail = npv[t] - keep
+            if tail <= 0:
+                continue
+            if tail > tail_max or T.parent[t] < 0 or T.depth[t] <= min_depth:
+                ok = False
+                break
+            w = np.where(T.piv_nodes[t] < nV, 6, 3)[::-1].cumsum()
+            cnt = int(np.searchsorted(w, tail)) + 1              # the fewest trailing nodes that hold at least ``tail`` DOFs
+            mv.append((int(t), cnt, int(w[cnt - 1])))
+            add[int(T.parent[t])] = add.get(int(T.parent[t]), 0) + int(w[cnt - 1])
+        if not ok:
+            continue
+        grown = list(lev_max)
+        for p, a in add.items():
+            grown[T.height[p]] = max(grown[T.height[p]], npv[p] + a)
+        if any(panels(grown[T.height[p]]) > panels(lev_max[T.height[p]]) for p in add):
+            continue
+        Fn = F + sum(flops3(npv[t] - d, nfv[t]) - flops3(npv[t], nfv[t]) for t, _, d in mv) \
+               + sum(flops3(npv[p] + a, nfv[p] + a) - flops3(npv[p], nfv[p]) for p, a in add.items())
+        if 100 * Fn > 101 * F0:
+            continue
+        recv = {p: [] for p in add}
+        for t, cnt, d in mv:
+            p = int(T.parent[t])
+            D = T.piv_nodes[t][-cnt:]
+            T.owner[D] = p
+            recv[p].append(D)
+            bnd[t] = np.sort(np.concatenate([bnd[t], D]))
+            T.piv_nodes[t] = T.piv_nodes[t][:-cnt]
+            npv[t] -= d
+            dofs[h] += d
+        for p, a in add.items():                                 # (children in ascending id: the left one's nodes first)
+            T.piv_nodes[p] = np.concatenate(recv[p] + [T.piv_nodes[p]])
+            npv[p] += a; nfv[p] += a
+            lev_max[T.height[p]] = max(lev_max[T.height[p]], npv[p])
+        lev_max[h] = max(npv[t] for t in by_height[h])
+        saved[h] = P - panels(lev_max[h])
+        F = Fn
+    return dict(dofs=dofs, saved=saved, flops3=(int(F0), int(F)))
 
 
 def _assemble_plan(dof_lists, npiv, parent, left, right, level_of, elem_front, elem_dofs):
@@ -329,18 +412,21 @@ def _plan_from_native(A) -> FrontalPlan:
     lo = A["level_off"]
     plan.nlevels = int(lo.size - 1)
     plan.level_nodes = [A["level_nodes"][lo[h]:lo[h + 1]] for h in range(plan.nlevels)]
+    plan.tail_delay = _tail_delay_native(A)
     return plan
 
 
-def build_plan(mesh, leaf_size=12, impl="native", axis_rule=None, gap=None, node_order=None) -> FrontalPlan:
-    """Single-GPU plan: every tree node is a front, levels by height."""
+def build_plan(mesh, leaf_size=12, impl="native", axis_rule=None, gap=None, node_order=None, tail_max=0) -> FrontalPlan:
+    """Single-GPU plan: every tree node is a front, levels by height.  ``tail_max`` > 0: levels whose last outer panel holds at most
+    that many pivot DOFs hand it to their parents (the tail-delay pass, csrc/symbolic.cpp section 3b); 0 (the default) is the plain
+    plan -- the solver contexts ask for ``TAIL_MAX``."""
     axis_rule = AXIS_RULE if axis_rule is None else int(axis_rule)
     gap = GAP if gap is None else float(gap)
     node_order = NODE_ORDER if node_order is None else int(node_order)
     if impl == "native":
         from . import _native
-        return _plan_from_native(_native.plan_arrays(mesh, leaf_size, 0, axis_rule, gap, node_order))
-    T = analyse(mesh, leaf_size, impl="python", axis_rule=axis_rule, gap=gap, node_order=node_order)
+        return _plan_from_native(_native.plan_arrays(mesh, leaf_size, 0, axis_rule, gap, node_order, tail_max))
+    T = analyse(mesh, leaf_size, impl="python", axis_rule=axis_rule, gap=gap, node_order=node_order, tail_max=tail_max)
     nV, ndof_u = mesh.nV, mesh.ndof_u
     # DOF lists of all fronts from ONE expansion of the concatenated node lists (pivots first, then the boundary)
     seq = [a for t in range(T.ntree) for a in (T.piv_nodes[t], T.bnd_nodes[t])]
@@ -358,6 +444,7 @@ def build_plan(mesh, leaf_size=12, impl="native", axis_rule=None, gap=None, node
         leaf_of_pos[T.lo[t]:T.hi[t]] = t
     plan = _assemble_plan(dof_lists, npiv, T.parent, T.left, T.right, T.height, leaf_of_pos[T.epos], mesh.cell_dofs())
     plan.eorder = T.eorder.astype(np.int32)
+    plan.tail_delay = T.tail_delay
     return plan
 
 

@@ -17,6 +17,7 @@
  *   fronts:    "npiv", "nf" (pivot DOFs, all DOFs), "dof_off" (int64), "front_dofs" (pivots first),
  *              "up_map" (row of every boundary DOF in the parent front, -1 on pivots)
  *   schedule:  "level_nodes" / "level_off": fronts by height, largest first inside a level
+ *   tail delay (femo_tail_delay_plan_build): "tail_delay_dofs", "tail_delay_saved" (per level), "tail_delay_flops3"
  */
 #ifndef FEMO_SYMBOLIC_H
 #define FEMO_SYMBOLIC_H
@@ -61,6 +62,19 @@ int femo_plan_build_ex(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, in
 int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, int32_t npc, int32_t ndpc, const int32_t* cell_p2,
                         const double* cent, const double* cext, const int32_t* cell_dofs, int32_t leaf_size, int32_t min_depth,
                         int32_t axis_rule, double gap_coeff, int32_t node_order);
+/* The same with the tail-delay pass (femo_plan_build_ex2 = tail_max 0: off).  The numeric phase factorises a level in lock-step, one
+ * chain step per outer panel of 128 pivot columns: ceil(max npiv / 128) steps, however few columns the last one holds.  A pivot may
+ * always be eliminated at the parent instead (it stays in the child as a boundary row), so, bottom-up and one whole level at a time:
+ * with P = ceil(max npiv / 128) >= 2 and tail_t = max(0, npiv_t - 128 (P - 1)), every front of the level with a tail hands its last
+ * pivot nodes (whole nodes, the fewest that hold tail_t DOFs) to its parent, and the level has P - 1 steps -- provided that no tail is
+ * longer than tail_max DOFs, that no receiving level gets a further panel, that no front at depth <= min_depth would have to delay
+ * (the partition boundary; the root never delays) and that the factorisation's flops stay within 1 % of the plan's without the pass.
+ * At the child: npiv shrinks, nf stays; at the parent: npiv and nf grow, the delayed nodes first among its pivots.  "owner" names the
+ * front that eliminates a node after the pass.  Per level: "tail_delay_dofs" (int64, DOFs handed up), "tail_delay_saved" (int32,
+ * chain steps saved); "tail_delay_flops3" (int64 x 2): three times the factorisation flops without and with the pass. */
+int femo_tail_delay_plan_build(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, int32_t npc, int32_t ndpc, const int32_t* cell_p2,
+                               const double* cent, const double* cext, const int32_t* cell_dofs, int32_t leaf_size, int32_t min_depth,
+                               int32_t axis_rule, double gap_coeff, int32_t node_order, int32_t tail_max);
 /* number of entries of a named array (-1: no such array); 4 or 8 bytes per entry (0: no such array) */
 int64_t femo_plan_size(const femo_plan* p, const char* name);
 int femo_plan_itemsize(const femo_plan* p, const char* name);

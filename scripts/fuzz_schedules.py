@@ -40,7 +40,7 @@ def solve(m, marker, strong, leaf, pre, post):
 
 bad = 0
 for name, m, marker, strong in cases:
-    it0, w0, g0 = solve(m, marker, strong, 8, {}, dict(super_panel=0, fused_schur=0, lookahead=0))
+    it0, w0, g0 = solve(m, marker, strong, 8, dict(tail_max=0), dict(super_panel=0, fused_schur=0, lookahead=0))
     print(f"{name}: {m.ndof} DOF, reference {it0} iterations", flush=True)
     for k in range(ncomb):
         post = dict(trailing=int(rng.integers(0, 3)), left_min=int(rng.choice([1, 8, 64, 4096])), left_max=int(rng.choice([16, 2048, 100000])),
@@ -48,7 +48,8 @@ for name, m, marker, strong in cases:
                     super_panel_ahead=int(rng.integers(0, 2)), diag_ahead=int(rng.integers(0, 2)), rows_preload_wg=int(rng.choice([0, 64, 100000])), rows_fine_wg=int(rng.choice([0, 64, 96, 100000])), narrow_fine_wg=int(rng.choice([0, 16, 128, 100000])), narrow_split=int(rng.choice([1, 3, 4, 8])), narrow_split_wg=int(rng.choice([8, 1024, 100000])), super_tiles=int(rng.integers(0, 2)), super_tiles_min=int(rng.choice([1, 3, 8])), split_cnt=int(rng.choice([0, 16, 100000])), split_groups=int(rng.choice([2, 3, 4, 8])), fuse_rows=int(rng.integers(0, 2)), sweep_ahead=int(rng.integers(0, 4)), sweep_graph=int(rng.integers(0, 2)), fuse_rows_cnt=int(rng.choice([1, 512])), fuse_rows_np=int(rng.choice([128, 256, 100000])), diag_v1_cnt=int(rng.choice([1, 512])), lookahead=int(rng.integers(0, 2)), lookahead_cnt=int(rng.choice([4, 16, 1000])),
                     fused_schur=int(rng.integers(0, 2)), diag_v1=int(rng.integers(0, 3)), grid_chunk=int(rng.choice([3, 17, 65535])), xinv_small_cnt=int(rng.choice([0, 32, 100000])),
                     sweep_w=int(rng.integers(0, 2)), assemble_fc=int(rng.choice([0, 1, 2])))
-        pre = dict(wide_cnt=int(rng.choice([0, 8, 512, 100000])), wide_np=int(rng.choice([64, 512])), swork_slots=int(rng.choice([2, 100, 8192])))
+        pre = dict(wide_cnt=int(rng.choice([0, 8, 512, 100000])), wide_np=int(rng.choice([64, 512])), swork_slots=int(rng.choice([2, 100, 8192])),
+                   tail_max=int(rng.choice([0, 16, 32])))          # the tail-delay pass of the symbolic plan: off, and two lengths
         leaf = int(rng.choice([4, 8, 12, 20]))
         try:
             it, w, g = solve(m, marker, strong, leaf, pre, post)

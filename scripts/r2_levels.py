@@ -18,7 +18,7 @@ c = ShellContext(m)
 for k, v in fields.items():
     c.set_field(k, v)
 c.set_penalty_facets(m.penalty_facets(marker))
-pre = {k: v for k, v in opts.items() if k in ("wide_np", "wide_cnt", "swork_slots")}
+pre = {k: v for k, v in opts.items() if k in ("wide_np", "wide_cnt", "swork_slots", "tail_max")}     # tail_max=0: the plan without the tail-delay pass
 plan = c.enable_frontal(int(opts.pop("leaf", 12)), **pre)
 for k, v in opts.items():
     if k not in pre:
