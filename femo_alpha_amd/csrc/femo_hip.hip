@@ -1316,7 +1316,10 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             std::swap(c->stream, c->stream_a); fr.x_inflight = false;  // (the sweep's own join has nothing to wait for: done above)
             const int rc_a = frontal_fwd(c, fr.ahead_vec, 0, L + 1, nullptr);
             std::swap(c->stream, c->stream_a); fr.x_inflight = keep_inflight;
-            if (rc_a) return rc_a;
+            if (rc_a) {                             // whatever part of the sweep was launched ends before the main stream goes on
+                if (hipEventRecord(c->ev_a[2], c->stream_a) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ev_a[2], 0);
+                return rc_a;
+            }
             HIPCHK(c, hipEventRecord(c->ev_a[2], c->stream_a));
             fr.ahead_levels = L + 1;
         }
@@ -1748,7 +1751,14 @@ static int pcg_frontal(femo_ctx* c, double* b, double* x, bool zero_guess, int32
         }
         const int rc = frontal_factorize(c);
         c->fr.ahead_vec = nullptr;
-        if (rc) { c->fr.ahead_levels = 0; return rc; }
+        if (rc) {
+            // a factorisation that fails (a non-positive pivot is only known at its end) has the ahead sweep in flight on stream_a, reading
+            // the panel store and writing c->z and c->tmp: the main stream waits for it, so that what the caller does next -- new fields,
+            // a new factorisation into the same store -- is ordered behind it
+            if (c->fr.ahead_levels > 0) (void)hipStreamWaitEvent(c->stream, c->ev_a[2], 0);
+            c->fr.ahead_levels = 0;
+            return rc;
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     auto dot = [&](const double* a, const double* bb, double* out) -> int {
@@ -1761,7 +1771,10 @@ static int pcg_frontal(femo_ctx* c, double* b, double* x, bool zero_guess, int32
     };
     if (mask) hipLaunchKernelGGL(k_mask_zero, dim3(vg), dim3(256), 0, c->stream, b, mask, n);
     double bb = 0, rr = 0, pAp = 0;
-    if (dot(b, b, &bb)) return 1;
+    if (dot(b, b, &bb)) {
+        if (c->fr.ahead_levels > 0) { (void)hipStreamWaitEvent(c->stream, c->ev_a[2], 0); c->fr.ahead_levels = 0; }
+        return 1;
+    }
     if (!std::isfinite(bb)) {
         if (c->fr.ahead_levels > 0) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_a[2], 0)); c->fr.ahead_levels = 0; }   // the started sweep ends first
         return fail(c, "PCG: the right-hand side is not finite (NaN or infinite b.b)");
