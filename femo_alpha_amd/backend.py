@@ -61,7 +61,7 @@ class ShellContext:
         self.nghost = int(nghost)
         self.ndof = int(self.lib.femo_ndof(h))            # vector length: mesh DOFs + ghost entries
         assert self.ndof == mesh.ndof + self.nghost
-        # schedule experiments without touching the caller: FEMO_OPTIONS="sweep_graph=1,super_tiles=1" sets those options on every context
+        # schedule experiments without touching the caller: FEMO_OPTIONS="sweep_graph=1,sweep_w=1" sets those options on every context
         import os
         self.env_options = {}
         self.tail_max = None              # plan option "tail_max": None = the package's default (solver.symbolic.TAIL_MAX)
@@ -72,7 +72,7 @@ class ShellContext:
                     raise ValueError
                 self.env_options[k.strip()] = float(v)
             except ValueError:
-                raise FemoHipError(f"FEMO_OPTIONS: '{kv}' is not of the form option=number (e.g. FEMO_OPTIONS=\"sweep_graph=1,super_tiles=1\")") from None
+                raise FemoHipError(f"FEMO_OPTIONS: '{kv}' is not of the form option=number (e.g. FEMO_OPTIONS=\"sweep_graph=1,sweep_w=1\")") from None
             self.set_option(k.strip(), self.env_options[k.strip()])
         if self.env_options:
             import sys
@@ -91,9 +91,8 @@ class ShellContext:
     def set_option(self, key, value):
         """Schedule switches and failure policy of this context (femo_set_option; include/femo_hip.h documents every name and its
         default).  Failure policy: 'strict', 'allow_pivot_repair'.  Factorisation schedule: 'trailing', 'left_min', 'left_max',
-        'super_panel', 'super_panel_cnt', 'super_panel_ahead', 'lookahead', 'lookahead_cnt', 'diag_ahead', 'fused_schur', 'fuse_rows',
-        'fuse_rows_cnt', 'fuse_rows_np', 'rows_fine_wg', 'rows_preload_wg', 'narrow_fine_wg', 'narrow_split', 'narrow_split_wg',
-        'split_cnt', 'split_groups', 'super_tiles', 'super_tiles_min', 'diag_v1', 'diag_v1_cnt', 'xinv_small_cnt', 'grid_chunk',
+        'super_panel', 'super_panel_cnt', 'lookahead', 'lookahead_cnt', 'fused_schur', 'fuse_rows', 'fuse_rows_cnt', 'fuse_rows_np',
+        'rows_fine_wg', 'narrow_fine_wg', 'diag_v1', 'diag_v1_cnt', 'xinv_small_cnt', 'grid_chunk',
         'assemble_fc', 'precond_nquad', 'equilibrate'.  Sweeps and solves: 'sweep_graph', 'sweep_ahead', 'sweep_w', 'sweep_butterfly',
         'bnd_tiled_nb', 'multi_rhs', 'apply_lanes', 'stale_factor', 'stale_rel'.  Before the frontal plan is set: 'wide_np', 'wide_cnt',
         'swork_slots', 'tail_max' (the tail-delay pass of the symbolic analysis, solver.symbolic.build_plan: the longest last outer

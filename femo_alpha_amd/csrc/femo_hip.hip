@@ -56,12 +56,7 @@ struct femo_ctx {
     long long opt_version = 0;               // bumped by every femo_set_option
     Stream stream2;                          // look-ahead: the bulk of a trailing update runs beside the next panel
     Event ev_la[2];
-    Event ev_sp[2];
-    Stream stream_g;                         // second stream of the levels whose fronts are dealt to two streams (option "split_cnt")
-    Event ev_g[2];
-    Stream stream_m;                         // diagonal look-ahead: a stream that may not use the CUs reserved for the diagonal blocks
-    Event ev_da[2];
-    Stream stream3;                          // L11^-1 of a finished level is formed beside the factorisation of the next ones
+    Stream stream3;                         // L11^-1 of a finished level is formed beside the factorisation of the next ones
     Stream stream_a;                         // option "sweep_ahead": the forward sweep of the lower levels beside the factorisation of the top
     Event ev_a[3];
     Event ev_x[2];
@@ -199,13 +194,11 @@ struct femo_ctx {
         int trailing = 0;             // rank-k update schedule: 0 auto, 1 left-looking, 2 right-looking
         int left_min = 64, left_max = 2048;   // auto: levels with this many fronts are left-looking
         int lookahead = 1, lookahead_cnt = 16;
-        int super_panel = 512, super_panel_cnt = 64, super_panel_ahead = 0;
-        int rows_preload_wg = 0;              // k_panel_rows launches of at most this many workgroups preload S into LDS
+        int super_panel = 512, super_panel_cnt = 64;
         // k_panel_rows launches of at most this many (64-row) workgroups run k_panel_rows_fine (16 rows per workgroup).  Measured at 1 M DOF
         // (scripts/r4_ab.py, one process, interleaved): rows per panel of the two top levels 16 -> 10 us; factorisation 12.73 ms without the
         // fine kernels, 12.61 with this one at 96 or 256, 12.72 at 768 (levels of 8-32 fronts lose), 12.52 with both at (96, 128)
         int rows_fine_wg = 96;
-        int narrow_split = 1, narrow_split_wg = 1024;
         int narrow_fine_wg = 128;             // narrow updates of at most this many 64 x 64 tiles run k_trailing_fine (32 x 32 tiles, a 16 x 16 block per wave): the
                                               // root's updates 24 -> 18 us each; levels of four fronts and more lose (512: +5 % on level 11)
         // fronts of non-wide levels with at least fuse_rows_cnt fronts whose widest front has at most fuse_rows_np pivots: the rows under a
@@ -217,9 +210,6 @@ struct femo_ctx {
         int fuse_rows_np = 2 * NBO;
         int sweep_graph = 0;                        // the preconditioner application of the PCG loop replayed as a HIP graph
         int diag_v1_cnt = 512;                      // levels of at least this many fronts: k_diag_block (80 KB of LDS, two workgroups per CU)
-        int split_cnt = 0, split_groups = 2;        // levels of 2..split_cnt fronts: dealt to two streams in split_groups groups (off: no gain measured)
-        int super_tiles = 0, super_tiles_min = 8;   // rank-k updates of few large fronts: 4 x 4 super-tiles per XCD from this many 64-row tiles
-        int diag_ahead = 0;                   // super-panel levels: the next diagonal block runs beside the rest of this panel's rows and updates
         int fused_schur = 1;          // left-looking levels: the Schur update gathers its block from the children
         // Experiment: factorise D K D with D = diag(K)^-1/2 (1) or its nearest powers of two (2) and apply
         // D (L L^T)^-1 D.  Measured: no change in what one application of the factor leaves -- every operation of
@@ -943,19 +933,29 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
         const int* lev = fr.level_nodes + b;
         int max_np = 0;
         for (int i = b; i < e; ++i) max_np = std::max(max_np, fr.h_npiv[fr.h_level_nodes[i]]);
+        const int cnt_level = cnt, max_np_level = max_np;          // (the chunks of the level below have their own cnt and max_np)
+        const int* lev_level = lev;
+        // The schedule of the level, decided once.
+        // Rank-k updates, two schedules (option "trailing": 0 auto, 1 left, 2 right):
+        //   right-looking -- after every outer panel, everything behind it is updated with that panel's 128 columns;
+        //   left-looking  -- a panel's columns receive all earlier columns' updates just before they are factorised and
+        //                    the Schur complement is updated once with K = npiv (each entry read and written once).
+        // Left-looking wins where a level has enough fronts to fill the chip with the narrow panel updates (measured at
+        // 1M DOF: levels of 16..2048 fronts), right-looking at the top of the tree and on the single-panel leaves.
+        const bool right_looking = c->opt.trailing == 2 ? true : c->opt.trailing == 1 ? false : (cnt_level < c->opt.left_min || cnt_level > c->opt.left_max);
+        // the super-panel width the schedule really uses (whole outer panels): every decision below tests THIS value, so an
+        // option between two multiples of 128 cannot switch the gathering update on while the super-panel branch stays off
+        const int SP_opt = c->opt.super_panel / NBO * NBO;
+        const bool use_sp = right_looking && SP_opt > NBO && cnt_level <= c->opt.super_panel_cnt && max_np_level > NBO;
+        const bool lookahead = right_looking && !use_sp && cnt_level < c->opt.lookahead_cnt && c->opt.lookahead != 0;
         // Levels above the leaves whose Schur complements receive exactly ONE rank-k update (left-looking levels; right-looking
         // levels of single-panel fronts without look-ahead): that update gathers the block from the children itself, and
         // the extend-add fills the pivot columns only (option "fused_schur").  Measured at 1M DOF: extend-add 3.3 -> 2.3 ms,
         // rank-k updates 8.4 -> 8.7 ms.
-        const bool left_level = !(c->opt.trailing == 2 ? true : c->opt.trailing == 1 ? false : (cnt < c->opt.left_min || cnt > c->opt.left_max));
-        // the super-panel width the schedule really uses (whole outer panels): every decision below tests THIS value, so an
-        // option between two multiples of 128 cannot switch the gathering update on while the super-panel branch stays off
-        const int SP_opt = c->opt.super_panel / NBO * NBO;
-        const bool sp_level = !left_level && SP_opt > NBO && cnt <= c->opt.super_panel_cnt && max_np > NBO && !c->opt.super_panel_ahead;
-        const bool single_update = left_level || (max_np <= NBO && !(cnt < c->opt.lookahead_cnt && c->opt.lookahead != 0));
+        const bool single_update = !right_looking || (max_np_level <= NBO && !lookahead);
         // super-panel levels: the FIRST update behind a super-panel reaches every Schur complement of the level: it gathers,
         // the later ones read and write what it stored
-        const bool fused_schur = L > 0 && (single_update || sp_level) && c->opt.fused_schur != 0;
+        const bool fused_schur = L > 0 && (single_update || use_sp) && c->opt.fused_schur != 0;
         if (L > 0) {
             // children Schur complements into the parents of this level
             int max_nb = 0;
@@ -972,28 +972,10 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
                   hipLaunchKernelGGL(k_extend_gather, dim3(grid.x, n), dim3(256), 0, c->stream, fd, lev, off, mask, fused_schur ? 1 : 0); }
         }
         const bool wide = fr.h_level_wide[L];                      // these levels keep S (inside X) for the triangular solves
-        const int cnt_level = cnt, max_np_level = max_np;
-        const int* lev_level = lev;
         // the other levels park the inverse of a diagonal block in Swork between k_diag_block and k_panel_rows, one 128 x 128
         // slot per front: levels with more fronts than Swork has slots are factorised in chunks of that many fronts
-        // Levels of a handful of large fronts (option "split_cnt": at most that many, at least two): the fronts are dealt to TWO streams in
-        // "split_groups" contiguous groups (fronts are sorted by size: groups alternate between the streams).  Each stream runs the whole
-        // chain of its groups -- while one is inside a diagonal block (one workgroup per front: the chip is empty), the other's rows
-        // and rank-k updates fill it.  Only wide levels (their diagonal-block inverses go to X, not to the shared Swork slots), and
-        // not with the schedules that use the second stream themselves.
-        const bool level_right = c->opt.trailing == 2 ? true : c->opt.trailing == 1 ? false : (cnt_level < c->opt.left_min || cnt_level > c->opt.left_max);
-        const bool level_sp = level_right && SP_opt > NBO && cnt_level <= c->opt.super_panel_cnt && max_np_level > NBO;
-        const bool level_la = level_right && !level_sp && cnt_level < c->opt.lookahead_cnt && c->opt.lookahead != 0;
-        const bool split = wide && c->stream_g && cnt_level >= 2 && cnt_level <= c->opt.split_cnt && !level_la &&
-                           !(level_sp && (c->opt.super_panel_ahead || c->opt.diag_ahead));
-        const int ngroups = split ? std::max(2, std::min(cnt_level, c->opt.split_groups)) : 1;
-        const int chunk_cap = split ? (cnt_level + ngroups - 1) / ngroups : wide ? cnt_level : std::min(cnt_level, fr.swork_slots);
-        if (split) {
-            HIPCHK(c, hipEventRecord(c->ev_g[0], c->stream));                  // the extend-add of the level
-            HIPCHK(c, hipStreamWaitEvent(c->stream_g, c->ev_g[0], 0));
-        }
+        const int chunk_cap = wide ? cnt_level : std::min(cnt_level, fr.swork_slots);
         for (int chunk_b = b; chunk_b < fr.h_level_off[L + 1]; chunk_b += chunk_cap) {
-        hipStream_t st = (split && ((chunk_b - fr.h_level_off[L]) / chunk_cap) % 2 == 1) ? c->stream_g : c->stream;
         const int b = chunk_b, e = std::min(chunk_b + chunk_cap, fr.h_level_off[L + 1]);
         const int cnt = e - b;
         const int* lev = fr.level_nodes + b;
@@ -1005,15 +987,6 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
         // front), the rows below it (one GEMM against the inverse), the trailing update
         int max_nb = 0;
         for (int i = b; i < e; ++i) max_nb = std::max(max_nb, fr.h_nf[fr.h_level_nodes[i]] - fr.h_npiv[fr.h_level_nodes[i]]);
-        // Rank-k updates, two schedules (option "trailing": 0 auto, 1 left, 2 right):
-        //   right-looking -- after every outer panel, everything behind it is updated with that panel's 128 columns;
-        //   left-looking  -- a panel's columns receive all earlier columns' updates just before they are factorised and
-        //                    the Schur complement is updated once with K = npiv (each entry read and written once).
-        // Left-looking wins where a level has enough fronts to fill the chip with the narrow panel updates (measured at
-        // 1M DOF: levels of 16..2048 fronts), right-looking at the top of the tree and on the single-panel leaves.
-        const bool right_looking = c->opt.trailing == 2 ? true : c->opt.trailing == 1 ? false : (cnt_level < c->opt.left_min || cnt_level > c->opt.left_max);
-        const bool use_sp = right_looking && SP_opt > NBO && cnt_level <= c->opt.super_panel_cnt && max_np_level > NBO;
-        const bool lookahead = right_looking && !use_sp && cnt_level < c->opt.lookahead_cnt && c->opt.lookahead != 0;
         bool bulk_pending = false;
         // flops of one k_trailing_mfma launch over this level, with the kernel's own column / K ranges (profiling only)
         auto count_trailing = [&](int C0, int schur, int K0 = 0, int KW = NBO) {
@@ -1043,31 +1016,19 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
             }
             return (need + TS - 1) / TS;
         };
-        // Triangular-grid updates (schur 1, 2, 5) on 64 x 64 tiles.  `ntr`: 64-row tiles the launch needs (trail_tiles).
-        auto launch_tri = [&](bool gather, int ntr, int off, int n, int C0_, int mode, int K0_, int KW_, hipStream_t st) {
-            // levels of few large fronts: 4 x 4 super-tiles per XCD (k_trailing_mfma, tile_map 1); the grid covers whole rounds of
-            // eight super-tiles, the tiles beyond the front leave at once
-            const bool sup = c->opt.super_tiles && n < 256 && ntr >= c->opt.super_tiles_min;
-            const int nst = (ntr + 3) / 4, nsup = nst * (nst + 1) / 2;
-            const int gx = sup ? (nsup + 7) / 8 * 128 : ntr * (ntr + 1) / 2;
-            if (gather) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
-            else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0_, mode, K0_, KW_, mask, 0, sup ? 1 : 0);
-        };
-        // narrow (schur 0) updates of few workgroups: their K range is cut into slices that run side by side and add their
-        // products with atomics (options "narrow_split": most slices, "narrow_split_wg": most tiles of a launch that is cut)
-        auto narrow_slices = [&](int gx, int n, int K) {
-            if (c->opt.narrow_split <= 1 || (long long)gx * n > c->opt.narrow_split_wg) return 1;
-            return std::max(1, std::min(c->opt.narrow_split, K / 32));
+        // Triangular-grid updates (schur 1, 2) on 64 x 64 tiles.  `ntr`: 64-row tiles the launch needs (trail_tiles).
+        auto launch_tri = [&](bool gather, int ntr, int off, int n, int C0_, int mode, int K0_, int KW_) {
+            const int gx = ntr * (ntr + 1) / 2;
+            if (gather) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0_, mode, K0_, KW_, mask);
+            else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0_, mode, K0_, KW_, mask);
         };
         // rows below a diagonal block: launches of few workgroups (what one workgroup takes is what the launch takes) use the
-        // kernel that brings all of S into LDS at once (option "rows_preload_wg": up to that many workgroups per launch)
-        auto launch_rows = [&](int ntiles, int off, int n, int C0_, const double* sw_, int tile_first, hipStream_t st) {
+        // kernel that gives a workgroup 16 rows (option "rows_fine_wg": up to that many 64-row workgroups per launch)
+        auto launch_rows = [&](int ntiles, int off, int n, int C0_, const double* sw_) {
             if ((long long)ntiles * n <= c->opt.rows_fine_wg)
-                hipLaunchKernelGGL(k_panel_rows_fine, dim3(4 * ntiles, n), dim3(256), 0, st, fd, lev, off, C0_, sw_, tile_first);
-            else if ((long long)ntiles * n <= c->opt.rows_preload_wg)
-                hipLaunchKernelGGL(k_panel_rows_preload, dim3(ntiles, n), dim3(256), PANEL_ROWS_PRELOAD_LDS, st, fd, lev, off, C0_, sw_, tile_first);
+                hipLaunchKernelGGL(k_panel_rows_fine, dim3(4 * ntiles, n), dim3(256), 0, c->stream, fd, lev, off, C0_, sw_);
             else
-                hipLaunchKernelGGL(k_panel_rows, dim3(ntiles, n), dim3(256), 0, st, fd, lev, off, C0_, sw_, tile_first);
+                hipLaunchKernelGGL(k_panel_rows, dim3(ntiles, n), dim3(256), 0, c->stream, fd, lev, off, C0_, sw_);
         };
         // k_diag_block: factor + inverse of the kw x kw block ~ 2/3 kw^3 + 1/3 kw^3; k_panel_rows: rows x triangular S
         auto count_panel = [&](int C0) {
@@ -1084,58 +1045,37 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
         };
         // right-looking levels with few, large fronts work in super-panels of SP columns: inside one the panels are
         // updated left-looking, and everything behind it is updated once, with K = SP -- the K = 128 update of the whole
-        // trailing matrix is HBM-bound (16 flop per byte moved).  With "super_panel_ahead" that bulk update runs on the second
-        // stream beside the NEXT super-panel's chain (diagonal block -> rows -> narrow update, latency-bound at the top
-        // of the tree): it leaves the next super-panel's pivot columns out (schur 5), and those columns take the factor
-        // columns of both super-panels in their own narrow updates (K0 = start of the previous super-panel).  Measured at
-        // 1M DOF: slower than the plain super-panel schedule (19.0 against 18.4 ms) -- the one-workgroup-per-front
-        // diagonal-block kernels lose more to sharing their CUs with the bulk update than the overlap gains; off by default.
+        // trailing matrix is HBM-bound (16 flop per byte moved).
         const int SP = use_sp ? SP_opt : NBO;
-        const bool sp_ahead = use_sp && c->opt.super_panel_ahead != 0;
-        int sp_bulks = 0;                                // bulk updates of this chunk issued on stream2 so far
-        // Diagonal look-ahead inside a super-panel (option "diag_ahead"): the chain diagonal block -> rows -> narrow update of
-        // the next panel -> next diagonal block is what the top of the tree waits for, but the next diagonal block needs only
-        // the rows of the NEXT panel (two 64-row tiles) and the three tiles of the narrow update that cover it.  Those stay on
-        // the main stream; the other row tiles and the other tiles of the narrow update go to stream_m and run beside the
-        // next diagonal block, whose rows wait for them (ev_da[1]).
-        // (wide levels only: elsewhere the inverse of a diagonal block sits in the front's ONE Swork slot, which the next diagonal block
-        // would overwrite while the rest of this panel's rows still read it)
-        const bool diag_ahead = use_sp && !sp_ahead && c->opt.diag_ahead && c->stream_m && wide;
-        constexpr int DIAG_TILES = 3, NEXT_ROW_TILES = NBO / TS;
-        bool rest_pending = false;
         // single-panel fronts on a level that keeps no S: rows inside the diagonal-block kernel (option "fuse_rows")
         const bool fuse_rows = !wide && max_np_level <= std::max(NBO, c->opt.fuse_rows_np) && c->opt.fuse_rows != 0 && cnt_level >= c->opt.fuse_rows_cnt;
         for (int C0 = 0; C0 < max_np; C0 += NBO) {
             double* sw = wide ? nullptr : fr.Swork;
             const int S0 = C0 / SP * SP;                 // start of this panel's super-panel (== C0 when SP == NBO)
-            const int K0 = !right_looking ? 0 : sp_ahead ? std::max(0, S0 - SP) : S0;
-            if (sp_ahead && C0 == S0 && sp_bulks >= 2)
-                // the bulk update two super-panels back wrote this super-panel's columns
-                HIPCHK(c, hipStreamWaitEvent(st, c->ev_sp[sp_bulks & 1], 0));
+            const int K0 = right_looking ? S0 : 0;
             if (C0 > K0) {
                 // left-looking update of this panel's columns with the factor columns [K0, C0) to their left
-                ProfScope ps(c, 2, st);
+                ProfScope ps(c, 2);
                 count_trailing(C0, 0, K0);
                 const int ntr = trail_tiles(C0, 0, K0);
                 // fused levels: these pivot columns are touched here for the first time (left-looking: every panel behind
                 // the first; super-panel schedule: the panels of the first super-panel) -- gathered from the children
                 const bool gather_panel = fused_schur && K0 == 0;
-                // diagonal look-ahead: only the tiles of the diagonal block here, the others were issued on stream_m behind the previous rows
-                const int gx = diag_ahead ? std::min(DIAG_TILES, ntr * (NBO / TS)) : ntr * (NBO / TS);
+                const int gx = ntr * (NBO / TS);
                 // few tiles (the top of the tree): the fine kernel -- a quarter of the MFMA chain per wave, four times the workgroups
-                const bool fine = !diag_ahead && (C0 - K0) % 64 == 0 && (long long)gx * cnt <= c->opt.narrow_fine_wg;
+                const bool fine = (C0 - K0) % 64 == 0 && (long long)gx * cnt <= c->opt.narrow_fine_wg;
                 if (ntr > 0)
                 FOR_FRONT_CHUNKS(cnt, off, n) {
                     if (fine) {
                         const int gx32 = 2 * ntr * (NBO / 32);           // 32-row tiles from the even column anchor down, four column tiles
-                        if (gather_panel) hipLaunchKernelGGL(k_trailing_fine<true>, dim3(gx32, 1, n), dim3(256), 0, st, fd, lev, off, C0, K0, mask, 0);
-                        else hipLaunchKernelGGL(k_trailing_fine<false>, dim3(gx32, 1, n), dim3(256), 0, st, fd, lev, off, C0, K0, mask, 0);
-                    } else if (gather_panel) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, st, fd, lev, off, C0, 0, K0, NBO, mask, 0, 0);
-                    else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, narrow_slices(gx, n, C0 - K0), n), dim3(256), 0, st, fd, lev, off, C0, 0, K0, NBO, mask, 0, 0);
+                        if (gather_panel) hipLaunchKernelGGL(k_trailing_fine<true>, dim3(gx32, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0, K0, mask);
+                        else hipLaunchKernelGGL(k_trailing_fine<false>, dim3(gx32, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0, K0, mask);
+                    } else if (gather_panel) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0, 0, K0, NBO, mask);
+                    else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, 1, n), dim3(256), 0, c->stream, fd, lev, off, C0, 0, K0, NBO, mask);
                 }
             }
             count_panel(C0);
-            { ProfScope ps(c, 1, st);
+            { ProfScope ps(c, 1);
               // classes of equal sub-block count (fronts are sorted by pivot count); small levels go in one launch
               const int* hn = fr.h_level_nodes.data() + b;
               auto first_above = [&](int thr) {          // first position whose front has more than thr pivots
@@ -1156,13 +1096,13 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
                       // the old kernel everywhere, 2 the new one.
                       const bool v1 = fuse_rows || c->opt.diag_v1 == 1 || (c->opt.diag_v1 == 0 && cnt >= c->opt.diag_v1_cnt) || (c->opt.diag_v1 == 3 && cnt >= 512 && nblk < NBO / NB);
                       if (v1)
-                          hipLaunchKernelGGL(k_diag_block, dim3(end - start), dim3(256), diag_block_lds_blocks(nblk) * sizeof(blk32), st,
+                          hipLaunchKernelGGL(k_diag_block, dim3(end - start), dim3(256), diag_block_lds_blocks(nblk) * sizeof(blk32), c->stream,
                                              fd, lev, start, nblk, C0, sw, fr.info, fuse_rows ? 1 : 0);
                       else if (c->opt.allow_pivot_repair)
-                          hipLaunchKernelGGL(k_diag_block2<true>, dim3(end - start), dim3(256), diag_block2_lds_blocks(nblk) * sizeof(blk32), st,
+                          hipLaunchKernelGGL(k_diag_block2<true>, dim3(end - start), dim3(256), diag_block2_lds_blocks(nblk) * sizeof(blk32), c->stream,
                                              fd, lev, start, nblk, C0, sw, fr.info);
                       else
-                          hipLaunchKernelGGL(k_diag_block2<false>, dim3(end - start), dim3(256), diag_block2_lds_blocks(nblk) * sizeof(blk32), st,
+                          hipLaunchKernelGGL(k_diag_block2<false>, dim3(end - start), dim3(256), diag_block2_lds_blocks(nblk) * sizeof(blk32), c->stream,
                                              fd, lev, start, nblk, C0, sw, fr.info);
                   }
                   start = end;
@@ -1173,102 +1113,60 @@ static int frontal_factorize_range(femo_ctx* c, int l0, int l1, bool assemble) {
                 if (np > C0) rows_below = std::max(rows_below, fr.h_nf[t] - C0 - std::min(NBO, np - C0));
             }
             const int tiles = fuse_rows ? 0 : (rows_below + TS - 1) / TS;        // fused: the diagonal-block kernel did the rows
-            // the rest of this panel's narrow update ran on stream_m: these rows read what it wrote
-            if (rest_pending) { HIPCHK(c, hipStreamWaitEvent(st, c->ev_da[1], 0)); rest_pending = false; }
-            // the next panel of the same super-panel takes a narrow update from this one
-            const bool ahead = diag_ahead && C0 + NBO < S0 + SP && C0 + NBO < max_np;
-            const int tiles_main = ahead ? std::min(tiles, NEXT_ROW_TILES) : tiles;
-            if (tiles_main > 0) {
-                ProfScope ps(c, 0, st);
+            if (tiles > 0) {
+                ProfScope ps(c, 0);
                 FOR_FRONT_CHUNKS(cnt, off, n)
-                    launch_rows(tiles_main, off, n, C0, sw, 0, st);
-            }
-            if (ahead) {
-                HIPCHK(c, hipEventRecord(c->ev_da[0], st));
-                HIPCHK(c, hipStreamWaitEvent(c->stream_m, c->ev_da[0], 0));
-                if (tiles > tiles_main) {
-                    ProfScope ps(c, 0, c->stream_m);
-                    FOR_FRONT_CHUNKS(cnt, off, n)
-                        launch_rows(tiles - tiles_main, off, n, C0, sw, tiles_main, c->stream_m);
-                }
-                const int C1 = C0 + NBO;
-                const int gx = trail_tiles(C1, 0, K0) * (NBO / TS) - DIAG_TILES;
-                if (gx > 0) {
-                    ProfScope ps(c, 2, c->stream_m);
-                    const bool gather_panel = fused_schur && K0 == 0;
-                    FOR_FRONT_CHUNKS(cnt, off, n) {
-                        if (gather_panel) hipLaunchKernelGGL(k_trailing_mfma<true>, dim3(gx, 1, n), dim3(256), 0, c->stream_m, fd, lev, off, C1, 0, K0, NBO, mask, DIAG_TILES, 0);
-                        else hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(gx, narrow_slices(gx, n, C1 - K0), n), dim3(256), 0, c->stream_m, fd, lev, off, C1, 0, K0, NBO, mask, DIAG_TILES, 0);
-                    }
-                }
-                HIPCHK(c, hipEventRecord(c->ev_da[1], c->stream_m));
-                rest_pending = true;
+                    launch_rows(tiles, off, n, C0, sw);
             }
             if (right_looking && SP > NBO) {
                 if (C0 + NBO >= S0 + SP || C0 + NBO >= max_np) {
                     // the super-panel is complete: one update of everything behind it
-                    const int mode = sp_ahead ? 5 : 2;
-                    const int ntr = trail_tiles(S0, mode, 0, SP);
+                    const int ntr = trail_tiles(S0, 2, 0, SP);
                     if (ntr > 0) {
-                        hipStream_t bs = sp_ahead ? c->stream2 : st;
-                        if (sp_ahead) {
-                            HIPCHK(c, hipEventRecord(c->ev_la[0], st));
-                            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_la[0], 0));
-                        }
-                        { ProfScope ps(c, 2, bs);
-                          count_trailing(S0, mode, 0, SP);
-                          FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur && S0 == 0, ntr, off, n, S0, mode, 0, SP, bs); }
-                        if (sp_ahead) {
-                            HIPCHK(c, hipEventRecord(c->ev_sp[sp_bulks & 1], c->stream2));
-                            ++sp_bulks;
-                        }
+                        ProfScope ps(c, 2);
+                        count_trailing(S0, 2, 0, SP);
+                        FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur && S0 == 0, ntr, off, n, S0, 2, 0, SP);
                     }
                 }
             } else if (right_looking && trail_tiles(C0, 2) > 0) {
                 const int ntr = trail_tiles(C0, 2);              // tiles are anchored at an even column, at most one before the first updated one
                 if (!lookahead) {
-                    ProfScope ps(c, 2, st);
+                    ProfScope ps(c, 2);
                     count_trailing(C0, 2);
                     // only the FIRST update behind the pivot columns may gather: a later one would overwrite the earlier panels' updates
-                    FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur && !left_level && C0 == 0, ntr, off, n, C0, 2, 0, NBO, st);
+                    FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur && C0 == 0, ntr, off, n, C0, 2, 0, NBO);
                 } else {
                     // look-ahead: the next panel's 128 columns are updated first, on the main stream; everything behind
                     // them goes to the second stream and runs beside the next diagonal block and its rows, which are a
                     // chain of latency-bound launches at the top of the tree.  The next narrow update touches columns
                     // the bulk update also writes, so it waits for it (ev_la[1]).
-                    if (bulk_pending) { HIPCHK(c, hipStreamWaitEvent(st, c->ev_la[1], 0)); bulk_pending = false; }
-                    { ProfScope ps(c, 2, st);
+                    if (bulk_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_la[1], 0)); bulk_pending = false; }
+                    { ProfScope ps(c, 2);
                       count_trailing(C0, 3);
-                      hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntr * (NBO / TS), 1, cnt), dim3(256), 0, st, fd, lev, 0, C0, 3, 0, NBO, mask, 0, 0); }
+                      hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntr * (NBO / TS), 1, cnt), dim3(256), 0, c->stream, fd, lev, 0, C0, 3, 0, NBO, mask); }
                     const int ntb = trail_tiles(C0, 4);
                     if (ntb > 0) {
-                        HIPCHK(c, hipEventRecord(c->ev_la[0], st));
+                        HIPCHK(c, hipEventRecord(c->ev_la[0], c->stream));
                         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_la[0], 0));
                         { ProfScope ps(c, 2, c->stream2);
                           count_trailing(C0, 4);
-                          hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntb * (ntb + 1) / 2, 1, cnt), dim3(256), 0, c->stream2, fd, lev, 0, C0, 4, 0, NBO, mask, 0, 0); }
+                          hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntb * (ntb + 1) / 2, 1, cnt), dim3(256), 0, c->stream2, fd, lev, 0, C0, 4, 0, NBO, mask); }
                         HIPCHK(c, hipEventRecord(c->ev_la[1], c->stream2));
                         bulk_pending = true;
                     }
                 }
             }
         }
-        if (bulk_pending) { HIPCHK(c, hipStreamWaitEvent(st, c->ev_la[1], 0)); bulk_pending = false; }
-        if (rest_pending) { HIPCHK(c, hipStreamWaitEvent(st, c->ev_da[1], 0)); rest_pending = false; }
-        if (sp_bulks > 0) HIPCHK(c, hipStreamWaitEvent(st, c->ev_sp[(sp_bulks - 1) & 1], 0));     // stream2 runs its launches in order
+        if (bulk_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_la[1], 0)); bulk_pending = false; }
         if (max_nb > 0 && !right_looking) {
             // Schur complement: one update with all npiv factor columns
-            ProfScope ps(c, 2, st);
+            ProfScope ps(c, 2);
             count_trailing(0, 1);
             const int ntr = trail_tiles(0, 1);
             if (ntr > 0)
-            FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur, ntr, off, n, 0, 1, 0, NBO, st);
+            FOR_FRONT_CHUNKS(cnt, off, n) launch_tri(fused_schur, ntr, off, n, 0, 1, 0, NBO);
         }
         }   // chunks of the level
-        if (split) {
-            HIPCHK(c, hipEventRecord(c->ev_g[1], c->stream_g));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_g[1], 0));
-        }
         const bool w_level = wide && fr.w_mode && fr.h_level_maxnb[L] > 0;
         if (wide && (max_np_level > NBO || w_level)) {
             const int max_np = max_np_level, cnt = cnt_level;
@@ -1981,24 +1879,10 @@ static int create_impl(femo_ctx* c, const double* xyz, const int32_t* cells, con
     HIPCHK(c, hipStreamCreate(c->stream.out()));
     HIPCHK(c, hipStreamCreate(c->stream2.out()));
     for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_la[i].out(), hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_sp[i].out(), hipEventDisableTiming));
     HIPCHK(c, hipStreamCreate(c->stream3.out()));
     for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_x[i].out(), hipEventDisableTiming));
-    HIPCHK(c, hipStreamCreate(c->stream_g.out()));
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_g[i].out(), hipEventDisableTiming));
     HIPCHK(c, hipStreamCreate(c->stream_a.out()));   // (a lowest-priority stream here made the factorisation 6 ms SLOWER: 13.4 -> 19.4 ms)
     for (int i = 0; i < 3; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_a[i].out(), hipEventDisableTiming));
-    {
-        // The diagonal look-ahead (factorize_fronts) runs the bulk of a panel's work on stream_m beside the next diagonal
-        // block, whose one workgroup per front needs a whole CU's LDS: stream_m leaves 32 of the 256 CUs alone (bits whose
-        // index / 8 is a multiple of 8 -- four CUs per XCD if the mask interleaves the XCDs, eight in every other XCD if
-        // it runs through them one after the other), so those workgroups start at once.  Without the mask the schedule
-        // is still correct; the option falls back to the plain super-panel order when the stream cannot be made.
-        uint32_t cumask[8];
-        for (int w = 0; w < 8; ++w) cumask[w] = (w & 1) ? 0xffffffffu : 0xffffff00u;
-        if (hipExtStreamCreateWithCUMask(c->stream_m.out(), 8, cumask) != hipSuccess) (void)hipGetLastError();   // stream_m stays null
-        for (int i = 0; i < 2; ++i) HIPCHK(c, hipEventCreateWithFlags(c->ev_da[i].out(), hipEventDisableTiming));
-    }
     for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventCreate(c->ev[i].out()));
     const int nel = c->nel, nvc = c->nvc, npc = c->npc;
     // SoA connectivity
@@ -2927,22 +2811,13 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "lookahead_cnt") o.lookahead_cnt = v;
     else if (k == "super_panel") { if (v < 0) return fail(c, "super_panel: a column count (rounded down to whole 128-column panels; < 256 switches it off)"); o.super_panel = v; }
     else if (k == "super_panel_cnt") o.super_panel_cnt = v;
-    else if (k == "super_panel_ahead") o.super_panel_ahead = v != 0;
-    else if (k == "diag_ahead") o.diag_ahead = v != 0;
     else if (k == "rows_fine_wg") o.rows_fine_wg = v;
     else if (k == "narrow_fine_wg") o.narrow_fine_wg = v;
-    else if (k == "rows_preload_wg") o.rows_preload_wg = v;
-    else if (k == "narrow_split") { if (v < 1 || v > 32) return fail(c, "narrow_split: 1..32 slices of the K range"); o.narrow_split = v; }
-    else if (k == "narrow_split_wg") o.narrow_split_wg = v;
-    else if (k == "split_cnt") o.split_cnt = v;
     else if (k == "diag_v1_cnt") o.diag_v1_cnt = v;
     else if (k == "sweep_graph") o.sweep_graph = v != 0;
     else if (k == "fuse_rows") o.fuse_rows = v != 0;
     else if (k == "fuse_rows_cnt") o.fuse_rows_cnt = v;
     else if (k == "fuse_rows_np") o.fuse_rows_np = v;
-    else if (k == "split_groups") { if (v < 2) return fail(c, "split_groups: at least 2"); o.split_groups = v; }
-    else if (k == "super_tiles") o.super_tiles = v != 0;
-    else if (k == "super_tiles_min") o.super_tiles_min = v;
     else if (k == "fused_schur") o.fused_schur = v != 0;
     else if (k == "precond_nquad") { if (v != 0 && (v < 2 || v > 6)) return fail(c, "precond_nquad: 0 (the operator's rule) or 2..6"); o.precond_nquad = v; operator_changed(c); }
     else if (k == "equilibrate") { if (v < 0 || v > 2) return fail(c, "equilibrate: 0 off, 1 diag^-1/2, 2 nearest powers of two"); o.equilibrate = v; operator_changed(c); }
@@ -4133,7 +4008,6 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
     }
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block,hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block_lds_blocks(NBO / NB) * sizeof(blk32))));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_panel_rows_preload, hipFuncAttributeMaxDynamicSharedMemorySize, PANEL_ROWS_PRELOAD_LDS));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block2<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(diag_block2_lds_blocks(NBO / NB) * sizeof(blk32))));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_diag_block2<true>, hipFuncAttributeMaxDynamicSharedMemorySize,

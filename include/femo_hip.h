@@ -266,8 +266,8 @@ int femo_set_solver(femo_ctx* ctx, int preconditioner, double rtol, int32_t maxi
  *   "trailing" 0 auto | 1 left-looking | 2 right-looking rank-k updates; "left_min", "left_max" (auto: levels with this
  *   many fronts are left-looking; defaults 64, 2048); "super_panel" (default 512; 0 = off), "super_panel_cnt" (default 64):
  *   right-looking levels of at most that many fronts update the trailing matrix once per super-panel of that many factor
- *   columns instead of once per 128; "super_panel_ahead" (default 0): that update on a second stream beside the next
- *   super-panel's panels; "lookahead" 0/1, "lookahead_cnt": the same for the 128-column schedule;
+ *   columns instead of once per 128; "lookahead" 0/1, "lookahead_cnt": levels of fewer fronts than that on the 128-column
+ *   schedule run the bulk of an update on a second stream beside the next panel;
  *   "fused_schur" (default 1): Schur complements are gathered from the children by the rank-k update that touches them
  *   first instead of by the extend-add;
  *   "fuse_rows" (default 1), "fuse_rows_cnt" (2048), "fuse_rows_np" (256): levels of at least that many fronts whose widest front has at most

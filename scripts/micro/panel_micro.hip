@@ -52,14 +52,14 @@ int main(int argc, char** argv) {
             {
                 CK(hipEventRecord(e0));
                 if (variant == 0) hipLaunchKernelGGL(k_diag_block, dim3(nfr), dim3(256), diag_block_lds_blocks(4) * sizeof(blk32), 0, fd, dlev, 0, 4, C0, Sw, info, 0);
-                else hipLaunchKernelGGL(k_diag_block2<false>, dim3(nfr), dim3(256), diag_block2_lds_blocks(4) * sizeof(blk32), 0, fd, dlev, 0, 4, C0, Sw, info, 0);
+                else hipLaunchKernelGGL(k_diag_block2<false>, dim3(nfr), dim3(256), diag_block2_lds_blocks(4) * sizeof(blk32), 0, fd, dlev, 0, 4, C0, Sw, info);
                 CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1)); tp += ms;
                 const int tiles = (nf - C0 - kw + TS - 1) / TS;
                 float ms2 = 0;
                 if (tiles > 0) {
                     CK(hipEventRecord(e0));
-                    hipLaunchKernelGGL(k_panel_rows, dim3(tiles, nfr), dim3(256), 0, 0, fd, dlev, 0, C0, Sw, 0);
+                    hipLaunchKernelGGL(k_panel_rows, dim3(tiles, nfr), dim3(256), 0, 0, fd, dlev, 0, C0, Sw);
                     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
                     CK(hipEventElapsedTime(&ms2, e0, e1)); tp += ms2;
                 }
@@ -79,7 +79,7 @@ int main(int argc, char** argv) {
             const int nt = (nf - C0 - kw + 1 + TS - 1) / TS;
             if (nt > 0) {
                 CK(hipEventRecord(e0));
-                hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(nt * (nt + 1) / 2, 1, nfr), dim3(256), 0, 0, fd, dlev, 0, C0, 2, 0, NBO, (const unsigned char*)nullptr, 0, 0);
+                hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(nt * (nt + 1) / 2, 1, nfr), dim3(256), 0, 0, fd, dlev, 0, C0, 2, 0, NBO, (const unsigned char*)nullptr);
                 CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1)); tt += ms;
                 if (rep == 1) printf("  trailing C0=%4d nt=%3d: %7.1f us\n", C0, nt, ms * 1e3);

@@ -1,6 +1,6 @@
-// micro-benchmark: the rank-k update kernels on in-situ shapes -- nfr fronts of nf rows, one update of everything behind the
-// first KW columns (schur 2), 64 x 64 tiles (k_trailing_mfma) against 128 x 128 tiles (k_trailing_big), with and without the
-// XCD super-tile map.     usage: tile_micro [nfr nf KW reps]
+// micro-benchmark: the rank-k update kernel on in-situ shapes -- nfr fronts of nf rows, one update of everything behind the
+// first KW columns (schur 2) on 64 x 64 tiles (k_trailing_mfma).  The 128 x 128 tiles and the XCD super-tile map it was
+// written to compare against measured slower and left the library (profiles/HISTORY.md).     usage: tile_micro [nfr nf KW reps]
 #include "../../femo_alpha_amd/csrc/frontal.h"
 #include <cstdio>
 #include <cstdlib>
@@ -24,24 +24,17 @@ int main(int argc, char** argv) {
     CK(hipMemset(P, 0, sizeof(double) * poff[nfr])); CK(hipMemset(S, 0, sizeof(double) * (soff[nfr] + 2)));
     fd.P = P; fd.S = S;
     int* dlev = up(lev);
-    const size_t shm = 4 * sizeof(double) * 16 * LSTRB;
-    CK(hipFuncSetAttribute((const void*)k_trailing_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     const double flops = (double)nfr * ((double)nb * (nb + 1) / 2) * 2.0 * KW;
-    const int ntr = (nb + (np & 1) + TS - 1) / TS, ntb = (ntr + 1) / 2;
-    const int nst = (ntr + 3) / 4, nsup = nst * (nst + 1) / 2;
+    const int ntr = (nb + (np & 1) + TS - 1) / TS;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int var = 0; var < 3; ++var) {
-        float best = 1e30f;
-        for (int r = 0; r < reps; ++r) {
-            CK(hipEventRecord(e0));
-            if (var == 0) hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntr * (ntr + 1) / 2, 1, nfr), dim3(256), 0, 0, fd, dlev, 0, 0, 2, 0, KW, (const unsigned char*)nullptr, 0, 0);
-            else if (var == 1) hipLaunchKernelGGL(k_trailing_mfma<false>, dim3((nsup + 7) / 8 * 128, 1, nfr), dim3(256), 0, 0, fd, dlev, 0, 0, 2, 0, KW, (const unsigned char*)nullptr, 0, 1);
-            else hipLaunchKernelGGL(k_trailing_big<false>, dim3(ntb * (ntb + 1) / 2, 1, nfr), dim3(256), shm, 0, fd, dlev, 0, 0, 2, 0, KW, (const unsigned char*)nullptr);
-            CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
-            float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = ms < best ? ms : best;
-        }
-        printf("%d fronts nf %d K %d: %-28s %8.1f us  %6.1f TFLOP/s (%d workgroups)\n", nfr, nf, KW, var == 0 ? "64x64 tiles" : var == 1 ? "64x64, XCD super-tiles" : "128x128 tiles",
-               best * 1e3, flops / (best * 1e-3) / 1e12, var == 2 ? ntb * (ntb + 1) / 2 * nfr : ntr * (ntr + 1) / 2 * nfr);
+    float best = 1e30f;
+    for (int r = 0; r < reps; ++r) {
+        CK(hipEventRecord(e0));
+        hipLaunchKernelGGL(k_trailing_mfma<false>, dim3(ntr * (ntr + 1) / 2, 1, nfr), dim3(256), 0, 0, fd, dlev, 0, 0, 2, 0, KW, (const unsigned char*)nullptr);
+        CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = ms < best ? ms : best;
     }
+    printf("%d fronts nf %d K %d: 64x64 tiles %8.1f us  %6.1f TFLOP/s (%d workgroups)\n", nfr, nf, KW,
+           best * 1e3, flops / (best * 1e-3) / 1e12, ntr * (ntr + 1) / 2 * nfr);
     return 0;
 }

@@ -1,4 +1,4 @@
-"""Target of scripts/r3_timeline.sh: three factorisations of one mesh under the given schedule options.
+"""Target of a `rocprofv3 --kernel-trace` run (scripts/r3_timeline.py reads its CSV): three factorisations of one mesh under the given schedule options.
     python3 scripts/r3_timeline_target.py wing1m [key=value ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

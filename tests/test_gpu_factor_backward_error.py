@@ -188,14 +188,9 @@ SCHEDULES = [
     ("all left-looking", dict(trailing=0, left_min=1, left_max=100000)), ("all right-looking", dict(trailing=0, left_min=100000)),
     ("super_panel 200", dict(SP, super_panel=200)), ("super_panel 256", dict(SP, super_panel=256)),
     ("super_panel 384", dict(SP, super_panel=384)), ("super_panel 512", dict(SP, super_panel=512)),
-    ("super_panel 256 ahead", dict(SP, super_panel=256, super_panel_ahead=1)),
-    ("super_panel 512 ahead", dict(SP, super_panel=512, super_panel_ahead=1)),
-    ("super_panel 384 diag_ahead", dict(SP, super_panel=384, diag_ahead=1, rows_preload_wg=100000, narrow_split=4, narrow_split_wg=100000)),
     ("diag_v1 1", dict(diag_v1=1, diag_v1_cnt=1)), ("diag_v1 2", dict(diag_v1=2, diag_v1_cnt=1)),
-    ("super_tiles", dict(super_tiles=1, super_tiles_min=1)),
     ("fuse_rows 0", dict(fuse_rows=0)), ("fuse_rows everywhere", dict(fuse_rows=1, fuse_rows_cnt=1, fuse_rows_np=256)),
-    ("split 3 groups", dict(split_cnt=100000, split_groups=3)), ("narrow_split 4", dict(narrow_split=4, narrow_split_wg=100000)),
-    ("rows fine / preload", dict(rows_fine_wg=100000, rows_preload_wg=100000, narrow_fine_wg=100000)),
+    ("rows fine", dict(rows_fine_wg=100000, narrow_fine_wg=100000)),
     ("lookahead 0", dict(trailing=2, lookahead=0, super_panel=0)), ("lookahead 1", dict(trailing=2, lookahead=1, lookahead_cnt=1000, super_panel=0)),
     ("fused_schur 0", dict(fused_schur=0)),
     ("grid_chunk 3", dict(grid_chunk=3)), ("xinv_small_cnt 0", dict(xinv_small_cnt=0)), ("xinv_small_cnt all", dict(xinv_small_cnt=100000)),

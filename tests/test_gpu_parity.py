@@ -197,13 +197,12 @@ def test_multifrontal_preconditioner(kind, ewm, bc, uhat, wide_cnt):
     assert rel(c.get_state(), o.solve()) < 1e-8
 
 
-@pytest.mark.parametrize("sp,force_right,ahead", [(256, False, 1), (256, True, 1), (256, True, 0), (512, True, 1)])
-def test_super_panel_schedule_gives_the_same_factor(sp, force_right, ahead):
+@pytest.mark.parametrize("sp,force_right", [(256, False), (256, True), (512, True)])
+def test_super_panel_schedule_gives_the_same_factor(sp, force_right):
     """Right-looking levels may update the trailing matrix once per super-panel of 256 / 512 factor columns instead of
-    once per 128 (option "super_panel"), with the bulk update on a second stream beside the next super-panel's panels
-    (option "super_panel_ahead"): the factor is the same up to rounding, whatever the schedule -- same iteration count, same
-    solution as the panel-by-panel schedule, same parity with the oracle.  The root front has 582 pivots: three
-    super-panels of 256, so the second-stream dependencies (two bulk updates in flight) are exercised."""
+    once per 128 (option "super_panel"): the factor is the same up to rounding, whatever the schedule -- same iteration
+    count, same solution as the panel-by-panel schedule, same parity with the oracle.  The root front has 582 pivots:
+    three super-panels of 256, the last one partial."""
     from femo_alpha_amd.backend import ShellContext
     from oracle.rm_shell_oracle import ShellOracle, degree4_rule
     m = plate_mesh(2.0, 5.0, 64, 64)
@@ -220,7 +219,6 @@ def test_super_panel_schedule_gives_the_same_factor(sp, force_right, ahead):
         c.set_option("super_panel", super_panel)
         c.set_option("fused_schur", 1 if super_panel else 0)      # the reference run also fills the Schur columns in the extend-add
         c.set_option("super_panel_cnt", 64)
-        c.set_option("super_panel_ahead", ahead)
         if force_right:
             c.set_option("trailing", 2)
         plan = c.enable_frontal(leaf_size=8)
@@ -235,7 +233,7 @@ def test_super_panel_schedule_gives_the_same_factor(sp, force_right, ahead):
         c.close()
     assert sols[0][0] == sols[1][0]
     assert rel(sols[1][1], sols[0][1]) < 1e-9
-    if sp == 256 and force_right and ahead:
+    if sp == 256 and force_right:
         o = ShellOracle(m, penalty_facets=pf, beta=1e15)
         o.set_fields(h=fields["thickness"], E=fields["E"], nu=fields["nu"], rho=fields["density"], f=fields["F_solid"])
         assert rel(sols[1][1], o.solve()) < 1e-8
