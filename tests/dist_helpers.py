@@ -333,25 +333,66 @@ class ThreadComm:
         return torch.stack(self._exchange(t.detach().cpu().clone())).to(t.device)
 
 
-def run_threads(world, m, marker, fields, leaf_size=12, rtol=1e-12, device=0):
-    """``world`` drivers with the HIP engine as threads of this process; returns rank 0's results."""
+class PerturbingComm(ThreadComm):
+    """Negative control of the backward-error tests: the all-gather (the driver has one, the exchange of the packed Schur blocks
+    of the subtree roots) hands rank ``receiver`` a copy in which ONE entry of rank ``source``'s block is scaled by
+    ``1 + eps``; every other rank, and every other collective, sees what was sent."""
+
+    def __init__(self, group, rank, receiver, source, entry=0, eps=1e-8):
+        super().__init__(group, rank)
+        self.receiver, self.source, self.entry, self.eps = receiver, source, entry, eps
+        self.hits = 0
+
+    def allgather(self, t):
+        out = super().allgather(t)
+        if self.rank == self.receiver:
+            assert float(out[self.source, self.entry]) != 0.0, "the perturbed entry must not be a zero of the padding"
+            out[self.source, self.entry] *= 1.0 + self.eps
+            self.hits += 1
+        return out
+
+
+def run_ranks(world, mesh, marker, body, *, leaf_size, engine="hip", tail_max=None, comm_factory=None, element_wise_material=False,
+              device=0):
+    """``world`` ranks of the partitioned driver as threads of this process: one ``DistributedShell`` per thread (engine "hip": each
+    with its own context and HIP stream on the one card; "numpy": the stand-in above), ``body(ds, comm)`` on it, the context closed
+    afterwards.  A rank that raises aborts the barrier so that the others do not wait for it, and its exception is raised here.
+    ``comm_factory(group, rank)`` makes a rank's communicator (default ``ThreadComm``); ``tail_max`` None leaves the tail-delay pass
+    to the driver's own default, a number sets it, and the ranks then share one analysis of the mesh.  Returns every rank's result."""
+    import contextlib
     import threading
     from femo_alpha_amd.parallel import DistributedShell
-    from femo_alpha_amd.solver.symbolic import analyse
-    tree = analyse(m, leaf_size, min_depth=int(np.log2(world)))
+    if engine not in ("hip", "numpy"):
+        raise ValueError(engine)
+    tree = None
+    if tail_max is not None:
+        from femo_alpha_amd.solver.symbolic import analyse
+        tree = analyse(mesh, leaf_size, min_depth=int(np.log2(world)), tail_max=int(tail_max))
+    factory = None
+    if engine == "numpy":
+        factory = lambda sub, plan, info: NumpyEngine(sub, plan, info, element_wise_material=element_wise_material,
+                                                      nquad=mesh.recommended_nquad())
+    make_comm = comm_factory or ThreadComm
     group = ThreadGroup(world)
     out, err = [None] * world, [None] * world
+    setup = threading.Lock() if tree is None else contextlib.nullcontext()     # each rank's own analysis: one at a time
 
-    def body(rank):
+    def run(rank):
+        ds = None
         try:
-            ds = DistributedShell(m, ThreadComm(group, rank), bc_marker=marker, leaf_size=leaf_size, device=device, tree=tree)
-            out[rank] = run_driver(ds, fields, rtol)
-            ds.eng.ctx.close()
+            comm = make_comm(group, rank)
+            with setup:
+                ds = DistributedShell(mesh, comm, bc_marker=marker, leaf_size=leaf_size, engine_factory=factory, device=device,
+                                      element_wise_material=element_wise_material, tree=tree, tail_max=tail_max)
+            out[rank] = body(ds, comm)
         except BaseException as e:          # noqa: BLE001 -- a dead rank must not leave the others waiting at the barrier
             err[rank] = e
             group.barrier.abort()
+        finally:
+            if ds is not None and engine == "hip":
+                ds.eng.ctx.close()
 
-    ts = [threading.Thread(target=body, args=(r,)) for r in range(world)]
+    ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
     for t in ts:
         t.start()
     for t in ts:
@@ -362,4 +403,81 @@ def run_threads(world, m, marker, fields, leaf_size=12, rtol=1e-12, device=0):
     for e in err:
         if e is not None:
             raise e
-    return out[0]
+    return out
+
+
+def run_threads(world, m, marker, fields, leaf_size=12, rtol=1e-12, device=0):
+    """``world`` drivers with the HIP engine as threads of this process; returns rank 0's results."""
+    return run_ranks(world, m, marker, lambda ds, comm: run_driver(ds, fields, rtol), leaf_size=leaf_size, tail_max=0, device=device)[0]
+
+
+# ---- one application of the partitioned preconditioner, z = M^-1 v, outside PCG (what the backward-error tests measure)
+def apply_preconditioner(ds, comm, V):
+    """The preconditioner application of the partitioned PCG loop, once per row of ``V`` (global vectors, (k, ndof)), on the factor
+    ``ds`` holds (``ds.factorize()`` first): r = v on the rank's entries -- the replicated ones with their full value on every rank,
+    as b has them after ``_sum_top`` --, ``precond_fwd``, the all-reduce of the replicated entries, ``precond_rest``.  Through the
+    engine's interface only, so the HIP engine and the numpy stand-in take the same steps.  Returns the rank's local z of every
+    probe with what ``global_views`` needs to put the ranks' pieces together."""
+    import torch
+    eng, info = ds.eng, ds.info
+    l2g = np.asarray(info["l2g_dof"])
+    V = np.atleast_2d(np.asarray(V, dtype=np.float64))
+    Z = np.empty((V.shape[0], l2g.size))
+    with eng.on_stream():
+        r, z = eng.vec("r"), eng.vec("z")
+        for j, v in enumerate(V):
+            r.copy_(torch.as_tensor(np.ascontiguousarray(v[l2g])))
+            eng.precond_fwd()
+            if comm.size > 1:
+                comm.allreduce_(eng.topbuf)
+            eng.precond_rest()
+            Z[j] = z.cpu().numpy()
+    return dict(Z=Z, l2g_dof=l2g, top_local=np.asarray(info["top_local"]))
+
+
+def oracle_matrix(m, marker, fields, element_wise_material=False):
+    """(K of the single-domain oracle with penalty facets on ``marker``, boolean mask of the DOFs its penalty facets hold)."""
+    import scipy.sparse as sp
+    from oracle.rm_shell_oracle import ShellOracle
+    o = ShellOracle(m, element_wise_material=element_wise_material, penalty_facets=m.penalty_facets(marker))
+    o.set_fields(h=fields["thickness"], E=fields["E"], nu=fields["nu"], rho=fields["density"], f=fields["F_solid"])
+    pen = np.zeros(m.ndof, bool)
+    for dofs, _ in o._penalty_blocks():
+        pen[np.asarray(dofs)] = True
+    return sp.csr_matrix(o.assemble_K()), pen
+
+
+def preconditioner_views(world, mesh, marker, fields, V, **kw):
+    """Factorise on ``world`` ranks (``run_ranks`` with ``kw``) and apply the preconditioner once to every row of ``V``.  Returns the
+    ``global_views`` and, per rank, the facts the tests assert on so that a case cannot pass empty: replicated entries, ghost
+    entries, pivots the tail-delay pass moved."""
+    def body(ds, comm):
+        ds.set_fields(**fields)
+        ds.factorize()
+        res = apply_preconditioner(ds, comm, V)
+        res.update(ntop=int(ds.ntop), nghost=int(ds.info["nghost"]), saved=int(np.sum(ds.tree.tail_delay["saved"])),
+                   repaired=int(ds.eng.ctx.frontal_info()["pivots_repaired"]) if hasattr(ds.eng, "ctx") else 0)
+        return res
+    results = run_ranks(world, mesh, marker, body, **kw)
+    return global_views(results), [{k: r[k] for k in ("ntop", "nghost", "saved", "repaired")} for r in results]
+
+
+def global_views(results):
+    """From every rank's ``apply_preconditioner`` result, one global array (k, ndof) per rank: view q takes the interior entries from
+    the ranks that own them and the replicated entries from rank q ALONE (an average over the ranks, as ``gather_state`` forms it,
+    would dilute one rank's wrong top by 1 / P).  Every global entry must be covered."""
+    k = results[0]["Z"].shape[0]
+    ndof = 1 + max(int(r["l2g_dof"].max()) for r in results)
+    base = np.full((k, ndof), np.nan)
+    for r in results:
+        inner = np.ones(r["l2g_dof"].size, bool)
+        inner[r["top_local"]] = False
+        assert np.all(np.isnan(base[:, r["l2g_dof"][inner]])), "an interior entry belongs to one rank only"
+        base[:, r["l2g_dof"][inner]] = r["Z"][:, inner]
+    views = []
+    for r in results:
+        g = base.copy()
+        g[:, r["l2g_dof"][r["top_local"]]] = r["Z"][:, r["top_local"]]
+        assert not np.isnan(g).any(), "a global entry that no rank holds"
+        views.append(g)
+    return views

@@ -24,9 +24,10 @@ def _scaled(K):
     return (S @ K @ S).tocsr(), s
 
 
-def omega(K, V, Z):
+def omega(K, V, Z, rows=None):
     """Row-wise scaled backward error of Z as the solution of K Z = V: the largest over the rows and over the columns of V / Z
-    (vectors of K.shape[0] entries, or arrays (n, ncols)).  Returns one float."""
+    (vectors of K.shape[0] entries, or arrays (n, ncols)).  ``rows``: a boolean mask of K.shape[0] entries, the rows the largest is
+    taken over (default: all of them; every row is computed with the whole of Z either way).  Returns one float."""
     Kh, s = _scaled(K)
     Ka = abs(Kh)
     V = np.asarray(V, dtype=np.float64)
@@ -41,6 +42,11 @@ def omega(K, V, Z):
     den = Ka @ np.abs(zh) + np.abs(vh)
     with np.errstate(invalid="ignore", divide="ignore"):
         r = np.where(den > 0, num / np.where(den > 0, den, 1.0), np.where(num > 0, np.inf, 0.0))
+    if rows is not None:
+        rows = np.asarray(rows)
+        if rows.dtype != bool or rows.shape != (Kh.shape[0],) or not rows.any():
+            raise ValueError("omega: rows must be a boolean mask of K.shape[0] entries with at least one row set")
+        r = r[rows]
     return float(r.max())
 
 

@@ -243,18 +243,25 @@ def test_level_ranges_sweeps_and_schur_blocks(assemble_fc):
         with pytest.raises(FemoHipError):
             c.front_block_set(t, torch.zeros(1, dtype=torch.float64, device="cuda"))      # a front with pivots is never overwritten
     c.factorize_range(L - 1, L, False)                   # the root: its block is gathered from the two children
-    # forward sweep over all levels, then backward: M^-1 v; K M^-1 v = v up to the rounding of the factor
+    # forward sweep over all levels, then backward: M^-1 v, held to the scaled backward error of tests/factor_check.py (rel(K x, v) is
+    # dominated by the conditioning of K and blind to a factor that is wrong in its 8th digit)
+    from factor_check import omega
     v = rng.uniform(-1, 1, m.ndof)
     _put(c, "z", v)
     c.frontal_sweep("z", 0, L, False)
     c.frontal_sweep("z", 0, L, True)
     x = _get(c, "z")
-    assert rel(K @ x, v) < 1e-7
+    w_full = omega(K, v, x)
     # ... and in two halves of the tree, as the multi-GPU driver sweeps (local levels, then the replicated top)
     _put(c, "z", v)
     c.frontal_sweep("z", 0, L // 2, False); c.frontal_sweep("z", L // 2, L, False)
     c.frontal_sweep("z", L // 2, L, True); c.frontal_sweep("z", 0, L // 2, True)
-    assert rel(_get(c, "z"), x) < 1e-13
+    x2 = _get(c, "z")
+    w_halves = omega(K, v, x2)
+    print(f"omega level-range sweeps assemble_fc {assemble_fc}: full {w_full:.3e} two halves {w_halves:.3e}")
+    assert w_full <= 1e-12
+    assert w_halves <= 1e-12
+    assert rel(x2, x) < 1e-13
     prof = c.factorize_profile()
     assert prof["trailing"]["launches"] > 0 and prof["trailing_flops"] > 0
     again = c.factorize_profile(run=False)

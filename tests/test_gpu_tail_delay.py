@@ -150,39 +150,16 @@ def test_transient_march():
 def test_two_rank_partition_against_one_rank():
     """Two element partitions on one card with the pass on (it works below the partition depth only) against the one-rank run of the
     same driver: the tolerances of tests/test_gpu_distributed.py (1e-12 on displacement, compliance and gradient; equal PCG counts)."""
-    import threading
     import dist_helpers as H
-    from femo_alpha_amd.parallel import DistributedShell
     m = plate_mesh(2.0, 10.0, 16, 80)
     rng = np.random.default_rng(7)
     fields = dict(thickness=0.02 * (1 + 0.2 * rng.uniform(-1, 1, m.nn)), E=np.array([7e9]), nu=np.array([0.3]),
                   density=np.array([2700.0]), F_solid=rng.uniform(-1, 1, (m.nn, 3)) * 50)
-    res = {}
-    for world in (1, 2):
-        group = H.ThreadGroup(world)
-        out, err = [None] * world, [None] * world
 
-        def body(rank):
-            try:
-                ds = DistributedShell(m, H.ThreadComm(group, rank), bc_marker=CLAMP, leaf_size=24, device=0, tail_max=32)
-                assert int(np.sum(ds.tree.tail_delay["saved"])) > 0
-                out[rank] = H.run_driver(ds, fields)
-                ds.eng.ctx.close()
-            except BaseException as e:          # noqa: BLE001 -- a dead rank must not leave the other waiting at the barrier
-                err[rank] = e
-                group.barrier.abort()
-        ts = [threading.Thread(target=body, args=(r,)) for r in range(world)]
-        for th in ts:
-            th.start()
-        for th in ts:
-            th.join()
-        for e in err:
-            if e is not None and not isinstance(e, threading.BrokenBarrierError):
-                raise e
-        for e in err:
-            if e is not None:
-                raise e
-        res[world] = out[0]
+    def body(ds, comm):
+        assert int(np.sum(ds.tree.tail_delay["saved"])) > 0
+        return H.run_driver(ds, fields)
+    res = {world: H.run_ranks(world, m, CLAMP, body, leaf_size=24, tail_max=32)[0] for world in (1, 2)}
     one, r = res[1], res[2]
     ew, eg = _rel(r["w"], one["w"]), _rel(r["g"], one["g"])
     eJ = abs(float(r["J"]) - float(one["J"])) / abs(float(one["J"]))
