@@ -679,24 +679,28 @@ class ShellContext:
         return out
 
     def field_output_vjp(self, name, wrt, cbar):
-        """(d field / d wrt)^T cbar for the stored state and fields (femo_field_output_vjp); ``cbar``: one cotangent of nvc * nel
-        entries, or several as rows of a 2-D array (the result has the same number of rows).  Points of zero stress contribute
-        zero (a subgradient)."""
+        """(d field / d wrt)^T cbar for the stored state and fields (femo_field_output_vjp); ``cbar``: one cotangent of
+        ``field_size_of(name)`` entries (nvc * nel for the DG1 stress fields; nel * npt, cell-major like
+        ``ply_failure_field().ravel()``, for 'ply_failure_field'), or several as rows of a 2-D array (the result has the same number
+        of rows).  Points of zero stress contribute zero (a subgradient); an entry of the ply failure field is differentiated at
+        its first maximiser, the branch the forward mode takes.  'ply_failure_field' also takes wrt 'ply_table' and, under an
+        active layup, 'ply_thickness' / 'ply_angle'."""
         cb = np.ascontiguousarray(cbar, dtype=np.float64)
         one = cb.ndim == 1
-        cb = cb.reshape(-1, self.mesh.nvc * self.mesh.nel) if cb.size else cb.reshape(0, self.mesh.nvc * self.mesh.nel)
+        cb = self._cotangent_rows(name, cb)
         out = np.empty((cb.shape[0], self.arg_size(wrt)))
         self._chk(self.lib.femo_field_output_vjp(self._h, name.encode(), wrt.encode(), dptr(cb), cb.shape[0], dptr(out),
                                                  out.shape[1]))
         return out[0] if one else out
 
     def field_output_jacobian(self, name, wrt):
-        """The partial Jacobian d field / d wrt as a ``scipy.sparse.csr_matrix`` of shape (nvc * nel, arg_size(wrt)): per cell a
-        dense block, the columns of a row in the cell's local order (femo_field_output_jacobian)."""
+        """The partial Jacobian d field / d wrt as a ``scipy.sparse.csr_matrix`` of shape (field_size_of(name), arg_size(wrt)): per
+        cell a dense block, the columns of a row in the cell's local order (femo_field_output_jacobian).  For 'ply_failure_field'
+        row npt * e + p holds ld entries for 'disp_solid' and the 16 entries of its own recovery point for 'ply_table'."""
         import scipy.sparse as sp
         nnz = C.c_int64()
         self._chk(self.lib.femo_field_output_jacobian_nnz(self._h, name.encode(), wrt.encode(), C.byref(nnz)))
-        nrow = self.mesh.nvc * self.mesh.nel
+        nrow = self.field_size_of(name)
         rowptr = np.empty(nrow + 1, dtype=np.int64)
         colidx = np.empty(nnz.value, dtype=np.int32)
         vals = np.empty(nnz.value)
@@ -706,14 +710,29 @@ class ShellContext:
 
     def field_total_gradients(self, name, cbars, arg):
         """Total derivatives d (cbar_k . field) / d arg through the solved state for the rows cbar_k of ``cbars`` -- one grouped
-        adjoint solve (femo_field_total_gradients).  Returns (gradients (nbar, n), iterations, relative residuals)."""
-        cb = np.ascontiguousarray(np.atleast_2d(np.asarray(cbars, dtype=np.float64)))
+        adjoint solve (femo_field_total_gradients).  Returns (gradients (nbar, n), iterations, relative residuals).  A row has
+        ``field_size_of(name)`` entries.  'ply_failure_field' takes arg 'laminate', 'ply_table', 'F_solid', 'thickness', 'E', 'nu',
+        'density' (no solve runs where the residual does not depend on the argument: iterations 0) and, under an active layup,
+        'ply_thickness' / 'ply_angle', composed on the device: k local failure constraints cost ceil(k / 4) grouped solves."""
+        cb = self._cotangent_rows(name, np.ascontiguousarray(cbars, dtype=np.float64))
         nb = cb.shape[0]
         out = np.empty((nb, self.field_size(arg)))
         it = np.zeros(nb, dtype=np.int32); rr = np.zeros(nb)
         self._chk(self.lib.femo_field_total_gradients(self._h, name.encode(), nb, dptr(cb), arg.encode(), dptr(out), out.shape[1],
                                                       iptr(it), dptr(rr)))
         return out, it, rr
+
+    def _cotangent_rows(self, name, cb):
+        """``cb`` as rows of ``field_size_of(name)`` entries.  Where the size is not known here (an unknown name falls to the DG1
+        size, a ply failure field without a table has none) the library refuses the call with its own message."""
+        nc = self.field_size_of(name)
+        if nc == 0:
+            return cb.reshape(1, -1)
+        if cb.size == 0:
+            return cb.reshape(0, nc)
+        if cb.size % nc:
+            raise ValueError(f"a cotangent of '{name}' has {nc} entries, got {cb.size}: wrong length")
+        return cb.reshape(-1, nc)
 
     def field_size_of(self, name):
         """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field'."""

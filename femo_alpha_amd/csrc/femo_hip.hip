@@ -12,6 +12,7 @@
 #include "disp_history.h"
 #include "ply_failure.h"
 #include "field_jvp.h"
+#include "ply_field_rev.h"
 #include "layup.h"
 #include "layup_mass.h"
 #include "disp_aggregate.h"
@@ -2937,6 +2938,31 @@ static int ply_value_dev(femo_ctx* c, double out4[4]) {
     return 0;
 }
 
+// slot of every cell in ybuf (the inverse of eorder), for the one-thread-per-cell kernels that end in k_gather_sum
+static int ply_eslot(femo_ctx* c) {
+    auto& pl = c->ply;
+    if (pl.eslot) return 0;
+    std::vector<int> eo((size_t)c->nel), inv((size_t)c->nel);
+    HIPCHK(c, hipMemcpy(eo.data(), c->eorder, eo.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int slot = 0; slot < c->nel; ++slot) inv[eo[slot]] = slot;
+    HIPCHK(c, pl.eslot.alloc(inv.size()));
+    HIPCHK(c, hipMemcpy(pl.eslot, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// out (ndof) = the element vectors of ybuf added per node in fixed order
+static int ply_gather_sum(femo_ctx* c, double* out) {
+    const int nthreads = c->nP2 + c->nghost;
+#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
+                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
+    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
+    else if (c->quad) GATHER_SUM(9, 4);
+    else GATHER_SUM(6, 3);
+#undef GATHER_SUM
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 // d K / d w into out (ndof) or d K / d table into out (16 npt nel, cell-major); the shift stays on the device
 static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
     auto& pl = c->ply;
@@ -2948,24 +2974,10 @@ static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
         HIPCHK(c, hipGetLastError());
         return 0;
     }
-    if (!pl.eslot) {
-        std::vector<int> eo((size_t)c->nel), inv((size_t)c->nel);
-        HIPCHK(c, hipMemcpy(eo.data(), c->eorder, eo.size() * sizeof(int), hipMemcpyDeviceToHost));
-        for (int slot = 0; slot < c->nel; ++slot) inv[eo[slot]] = slot;
-        HIPCHK(c, pl.eslot.alloc(inv.size()));
-        HIPCHK(c, hipMemcpy(pl.eslot, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    if (int rc = ply_eslot(c)) return rc;
     ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_DW, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
                 (const double*)c->w, (const double*)pl.res, (const int*)pl.eslot, c->ybuf.get());
-    const int nthreads = c->nP2 + c->nghost;
-#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
-                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
-    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
-    else if (c->quad) GATHER_SUM(9, 4);
-    else GATHER_SUM(6, 3);
-#undef GATHER_SUM
-    HIPCHK(c, hipGetLastError());
-    return 0;
+    return ply_gather_sum(c, out);
 }
 
 // ---- mass and volume from the layup (layup_mass.h): outputs of the layup itself, not of the laminate, and independent of the state
@@ -5262,6 +5274,11 @@ static bool field_zf(const std::string& name, double* zf) {
     return true;
 }
 
+static const char* const FIELD_NAMES_JVP = "stress, stress_mid, stress_bot, ply_failure_field";
+static int field_unknown(femo_ctx* c, const std::string& name) {
+    return fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")");
+}
+
 // entries per row of the partial Jacobian d field / d wrt (0: the field does not depend on wrt); -1: unknown argument
 static int field_jac_width(const femo_ctx* c, const std::string& wrt) {
     if (wrt == "disp_solid") return c->ld;
@@ -5325,11 +5342,174 @@ static int field_vjp_dev(femo_ctx* c, double zf, const std::string& wrt, const d
     return 0;
 }
 
+// ---- reverse mode of the ply failure field (ply_field_rev.h): the same three entry points under the name "ply_failure_field"
+#define COMMA_PFR_STATE , false
+#define COMMA_PFR_TABLE , true
+
+// wrt is an argument the ply failure field is differentiated by in reverse, and n its length (n < 0: not checked).  *lw: layup_wrt's
+// 1 or 2; the products and the totals reach the layup through the table (layup_ok), the sparse Jacobian refuses it as the stress
+// fields do.  The shape derivative is refused like the aggregate's and the forward mode's.
+static int ply_field_rev_arg(femo_ctx* c, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
+    *lw = layup_wrt(c, wrt);
+    if (*lw && !layup_ok) return layup_field_refused(c, wrt);
+    int64_t len;
+    if (wrt == "disp_solid") len = c->ndof;
+    else if (!field_ptr(c, wrt.c_str(), &len) || wrt == "dirichlet") return fail(c, "unknown argument '" + wrt + "'");
+    if (wrt == "uhat") return fail(c, "ply_failure_field: the shape derivative (uhat) of this output is not provided");
+    if (n >= 0 && len != n) return fail(c, "buffer has the wrong length for '" + wrt + "'");
+    return 0;
+}
+
+// entries per row of the partial Jacobian of the ply failure field (0: the field does not depend on wrt)
+static int ply_field_jac_width(const femo_ctx* c, const std::string& wrt) {
+    return wrt == "disp_solid" ? c->ld : wrt == "ply_table" ? PLY_W : 0;
+}
+
+// out (device) = (d field / d w)^T cbar (ndof) or (d field / d table)^T cbar (16 npt nel, cell-major) for one device cotangent of
+// nel npt entries; every entry of out is written
+static int ply_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) {
+    auto& pl = c->ply;
+    const MeshDev m = mesh_dev_all(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+    if (table) {
+        ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_TABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, (const double*)c->w,
+                    cbar, (const int*)nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    if (int rc = ply_eslot(c)) return rc;
+    ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_STATE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, (const double*)c->w, cbar,
+                (const int*)pl.eslot, c->ybuf.get());
+    return ply_gather_sum(c, out);
+}
+
+// out (device, n) = (d field / d wrt)^T cbar for an argument ply_field_rev_arg admitted (lw from there): the kernels for the state
+// and the table, the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
+static int ply_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    if (wrt == "disp_solid" || wrt == "ply_table") return ply_field_vjp_dev(c, wrt == "ply_table", cbar, out);
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    HIPCHK(c, hipGetLastError());
+    if (!lw) return 0;
+    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
+    if (int rc = ply_field_vjp_dev(c, true, cbar, c->lay.tbar)) return rc;
+    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
+}
+
+static int ply_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    if (ply_need_table(c, "ply_failure_field")) return 2;
+    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nel * npt entries");
+    int lw;
+    if (int rc = ply_field_rev_arg(c, a, n, true, &lw)) return rc;
+    const size_t nc = (size_t)c->nel * c->ply.npt;
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)));
+    double* o = d + (size_t)nbar * nc;
+    if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(c, "copy of the cotangents failed");
+    for (int64_t k = 0; k < nbar; ++k)                   // one cotangent at a time: row k is the single call on cbar[k] bit for bit
+        if (int rc = ply_field_arg_vjp_dev(c, a, lw, d + k * nc, o + k * n, n)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int ply_field_jacobian_nnz(femo_ctx* c, const std::string& a, int64_t* nnz) {
+    if (ply_need_table(c, "ply_failure_field")) return 2;
+    int lw;
+    if (int rc = ply_field_rev_arg(c, a, -1, false, &lw)) return rc;
+    if (!nnz) return fail(c, "null nnz");
+    *nnz = (int64_t)ply_field_jac_width(c, a) * c->nel * c->ply.npt;
+    return 0;
+}
+
+static int ply_field_jacobian(femo_ctx* c, const std::string& a, int64_t* rowptr, int32_t* colidx, double* vals, int64_t nnz) {
+    int64_t want;
+    if (int rc = ply_field_jacobian_nnz(c, a, &want)) return rc;
+    if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
+    if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
+    if (nnz > INT32_MAX) return fail(c, "femo_field_output_jacobian: the columns of this Jacobian do not fit 32-bit indices");
+    const int wd = ply_field_jac_width(c, a);
+    const int64_t nrow = (int64_t)c->nel * c->ply.npt;
+    for (int64_t r = 0; r <= nrow; ++r) rowptr[r] = r * wd;
+    if (nnz == 0) return 0;
+    DevBuf<double> dv;
+    DevBuf<int> dc;
+    HIPCHK(c, dv.alloc((size_t)nnz));
+    if (dc.alloc((size_t)nnz) != hipSuccess) return fail(c, "out of device memory");
+    const MeshDev m = mesh_dev_all(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+    if (a == "ply_table")
+        ELEM_LAUNCH(c, k_ply_field_jac, COMMA_PFR_TABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt,
+                    (const double*)c->w, dv.get(), dc.get());
+    else
+        ELEM_LAUNCH(c, k_ply_field_jac, COMMA_PFR_STATE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt,
+                    (const double*)c->w, dv.get(), dc.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(vals, dv, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(colidx, dc, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k for the ply failure field.  R sees the laminate and the load alone in
+// laminate mode: for every other argument no solve runs (iterations 0, residuals 0).  The layup: lbar_k = -(dR / d laminate)^T lambda_k
+// and tbar_k = (d field / d table)^T cbar_k go through ONE pull-back, the composition of dfunctional_dev / dRdarg_T_dev.
+static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
+                                     double* relres) {
+    if (ply_need_table(c, "ply_failure_field")) return 2;
+    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nel * npt entries");
+    if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
+    int lw;
+    if (int rc = ply_field_rev_arg(c, a, n, true, &lw)) return rc;
+    const bool solve = lw || a == "laminate" || a == "F_solid";
+    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * c->ply.npt, ng = (size_t)std::max<int64_t>(n, 1);
+    const int64_t nl = (int64_t)LAM_W * c->nel;
+    HIPCHK(c, c->mr_io.grow((size_t)nbar * (2 * nd + ng + nc)));
+    if (lw) {
+        HIPCHK(c, c->lay.lbar.grow((size_t)nl));
+        HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
+    }
+    double* Bd = c->mr_io;
+    double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * ng;
+    std::vector<double*> B(nbar), X(nbar);
+    for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    int rc = 0;
+    if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
+    if (solve) {
+        for (int k = 0; k < nbar && !rc; ++k) rc = ply_field_vjp_dev(c, false, Cd + k * nc, B[k]);               // (d field / d w)^T cbar_k
+        if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_k
+    } else {
+        for (int k = 0; k < nbar; ++k) {
+            if (iters) iters[k] = 0;
+            if (relres) relres[k] = 0.0;
+        }
+    }
+    for (int k = 0; k < nbar && !rc; ++k) {
+        double* g = Gd + (size_t)k * n;
+        if (lw) {                                         // the stream orders the reuse of lbar and tbar
+            hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 0.0, nl);
+            rc = dRdarg_T_dev(c, "laminate", X[k], -1.0, c->lay.lbar, nl);
+            if (!rc) rc = ply_field_vjp_dev(c, true, Cd + k * nc, c->lay.tbar);
+            if (!rc) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, g, 0.0, n);
+            if (!rc) rc = layup_vjp_dev(c, lw, c->lay.lbar, c->lay.tbar, g);
+        } else {
+            rc = ply_field_arg_vjp_dev(c, a, 0, Cd + k * nc, g, n);                                              // (d field / d arg)^T cbar_k
+            if (!rc && solve) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                         // - (dR/d arg)^T lambda_k
+        }
+    }
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, Gd, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
+    }
+    return rc;
+}
+
 int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const double* cbar, int64_t nbar, double* out, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
-    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (fname == "ply_failure_field") return ply_field_output_vjp(c, a, cbar, nbar, out, n);
+    if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
     if (field_arg_len(c, a, n)) return 1;
     const size_t nc = (size_t)c->nvc * c->nel;
@@ -5347,7 +5527,8 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
 int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wrt, int64_t* nnz) {
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
-    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (fname == "ply_failure_field") return ply_field_jacobian_nnz(c, a, nnz);
+    if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
     if (wd < 0) return fail(c, "unknown argument '" + a + "'");
@@ -5360,6 +5541,7 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     int64_t want;
+    if (fname == "ply_failure_field") return ply_field_jacobian(c, a, rowptr, colidx, vals, nnz);
     if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
@@ -5395,7 +5577,8 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(arg ? arg : "");
     double zf;
-    if (!field_zf(fname, &zf)) return fail(c, "unknown field output '" + fname + "' (stress, stress_mid, stress_bot)");
+    if (fname == "ply_failure_field") return ply_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
+    if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
     if (field_arg_len(c, a, n)) return 1;
@@ -5424,8 +5607,6 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
 #undef FIELD_UHAT_LAUNCH
 
 // ------------------------------------------------------------------------------------------ forward mode of the field outputs (field_jvp.h)
-static const char* const FIELD_NAMES_JVP = "stress, stress_mid, stress_bot, ply_failure_field";
-
 // entries of the field output `name`; -1: unknown name; -2: the ply failure field without a table (the error is set)
 static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
     double zf;
@@ -5580,6 +5761,7 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
     if (refresh_diag(c)) return 1;
     HIPCHK(c, hipMemsetAsync(c->scal, 0, 8 * sizeof(double), c->stream));
     hipLaunchKernelGGL(k_fill, dim3(vg), dim3(256), 0, c->stream, c->scal, 1.0, 8);
+    bool cbar_set = false;
     auto launch = [&]() -> int {
         if (s == "apply") return op_apply(c, c->p, c->Ap, c->scal + 7, nullptr, nullptr, false);
         if (s == "pcg_update") { hipLaunchKernelGGL(k_pcg_update, dim3(vg), dim3(256), 0, c->stream, c->tmp, c->r, c->z, c->p, c->Ap, c->dinv, (const unsigned char*)nullptr, n, c->scal, 0); return 0; }
@@ -5622,6 +5804,20 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             if (nr > c->fr.multi_nr) return fail(c, "the largest front's sweeps do not fit the LDS with this many interleaved vectors");
             hipLaunchKernelGGL(k_fill, dim3(vec_grid(n * nr)), dim3(256), 0, c->stream, c->mr_v, 1.0, n * nr);
             return nr == 2 ? frontal_solve_multi<2>(c, c->mr_v, c->mr_y) : frontal_solve_multi<4>(c, c->mr_v, c->mr_y);
+        }
+        // ply failure: the aggregate's value pass, its whole state gradient on the device (value pass, PF_DW, gather: what
+        // femo_dfunctional enqueues), and the reverse products of the field for a cotangent of ones (state: kernel and gather; table)
+        if (s == "ply_value" || s == "ply_dw" || s == "ply_field_vjp" || s == "ply_field_vjp_table") {
+            if (ply_need_table(c, "femo_bench_kernel")) return 2;
+            if (s == "ply_value") return ply_value_launch(c);
+            if (s == "ply_dw") return ply_grad_dev(c, true, c->tmp);
+            const size_t nc = (size_t)c->nel * c->ply.npt, nt = nc * PLY_W;
+            if (!cbar_set) {                                // once per call: the timed launches are the products alone
+                HIPCHK(c, c->mr_io.grow(nc + nt));
+                hipLaunchKernelGGL(k_fill, dim3(vec_grid((int64_t)nc)), dim3(256), 0, c->stream, c->mr_io.get(), 1.0, (int64_t)nc);
+                cbar_set = true;
+            }
+            return s == "ply_field_vjp" ? ply_field_vjp_dev(c, false, c->mr_io, c->tmp) : ply_field_vjp_dev(c, true, c->mr_io, c->mr_io.get() + nc);
         }
         return fail(c, "unknown kernel '" + s + "'");
     };

@@ -146,8 +146,10 @@ class Form:
 class FieldForm:
     """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1), 'stress_mid', 'stress_bot', and in
     laminate mode with a ply table 'ply_failure_field' ((nel, npt) flattened).  ``assemble(computePartials(field_form, f), dim=2)``
-    is the sparse partial Jacobian of a stress field; ``computeMatVecProductFwd(computePartials(field_form, f), v)`` is the
-    matrix-free tangent of any of them."""
+    is the sparse partial Jacobian of any of them (for the ply failure field with respect to the state and the ply table);
+    ``computeMatVecProductFwd(computePartials(field_form, f), v)`` is the matrix-free tangent and
+    ``computeMatVecProductBwd(computePartials(field_form, f), cbar)`` the matrix-free reverse product.  The totals through the
+    solved state are ``FEA.field_tangents`` and ``FEA.field_gradients``."""
 
     def __init__(self, ctx, name):
         self.ctx, self.name = ctx, name
@@ -254,8 +256,8 @@ def assembleSystem(J, F, bcs=()):
 
 
 def assembleFieldPartial(v: PartialForm):
-    """d field / d argument of a field output as a scipy CSR matrix (nvc * nel rows): the reference's idiom for the partials of
-    an output of dimension 1, ``assemble(computePartials(form, f), dim=2)``."""
+    """d field / d argument of a field output as a scipy CSR matrix (nvc * nel rows, nel * npt for the ply failure field): the
+    reference's idiom for the partials of an output of dimension 1, ``assemble(computePartials(form, f), dim=2)``."""
     wrt = "disp_solid" if v.wrt.role == "state" else v.wrt.role
     return v.form.ctx.field_output_jacobian(v.form.name, wrt)
 
@@ -280,8 +282,14 @@ def computeMatVecProductFwd(A, x):
     return A.mult(x)
 
 
-def computeMatVecProductBwd(A: JacobianOperator, R):
-    return A.multTranspose(R.get() if isinstance(R, Function) else R)
+def computeMatVecProductBwd(A, R):
+    """A^T R for an assembled operator; the partial of a field output (``computePartials(field_form, f)``) is applied matrix-free
+    on the device (femo_field_output_vjp), the counterpart of ``computeMatVecProductFwd``."""
+    R = R.get() if isinstance(R, Function) else R
+    if isinstance(A, PartialForm) and isinstance(A.form, FieldForm):
+        wrt = "disp_solid" if A.wrt.role == "state" else A.wrt.role
+        return A.form.ctx.field_output_vjp(A.form.name, wrt, R)
+    return A.multTranspose(R)
 
 
 def setUpKSP_MUMPS(A: JacobianOperator):
@@ -390,6 +398,34 @@ class FEA:
                 t = t.reshape(t.shape[0], self.nel, -1)[:, new_of_cell].reshape(t.shape[0], -1)     # solver order -> caller order
             out[n] = t[0] if one else t
         return out
+
+    def field_gradients(self, name, cbars, arg_name, state="disp_solid"):
+        """Total gradients of linear functionals of ONE field output with respect to one input, the reverse twin of
+        ``field_tangents``: row k is d (cbars[k] . field) / d arg through the solved state, ceil(k / 4) grouped adjoint solves for k
+        cotangents (femo_field_total_gradients on the context of the state's residual).  Nothing is pushed: the inputs and the state
+        are the ones the context holds.  ``name``: a registered field output or one of the backend's own names ('stress',
+        'stress_mid', 'stress_bot', 'ply_failure_field').  ``cbars`` (one cotangent, or several as rows; cell-major like the field)
+        and the gradients are in caller order when the model was renumbered."""
+        ctx = self.states_dict[state]["residual_form"].ctx
+        fn = self.outputs_field_dict[name]["form"].name if name in self.outputs_field_dict else name
+        cb = np.asarray(cbars, dtype=np.float64)
+        one = cb.ndim == 1
+        cb = cb.reshape(1, -1) if one else cb.reshape(cb.shape[0], -1)
+        if self.cell_of_new is not None:
+            if cb.shape[1] % self.nel:
+                raise ValueError(f"a cotangent of '{name}' has a whole number of entries per cell, got {cb.shape[1]} for {self.nel} cells")
+            cb = cb.reshape(cb.shape[0], self.nel, -1)[:, self.cell_of_new].reshape(cb.shape[0], -1)   # caller order -> solver order
+        space = self.inputs_dict[arg_name]["function_space"]
+        per_cell = space.kind in ("VL", "VP", "VY") or (space.kind == "VT" and ctx.element_wise_material) \
+            or (space.kind == "VF" and ctx.elementwise_pressure)
+        idx = self.cell_of_new if per_cell else self.vertex_of_new
+        g, its, rrs = ctx.field_total_gradients(fn, cb, arg_name)
+        self.last_solve = (int(its.max()), float(rrs.max()))
+        if idx is not None:
+            old = np.empty_like(g).reshape(g.shape[0], len(idx), -1)
+            old[:, idx] = g.reshape(g.shape[0], len(idx), -1)                                    # solver order -> caller order
+            g = old.reshape(g.shape[0], -1)
+        return g[0] if one else g
 
     def add_strong_bc(self, ubc, locate_BC_list, function_space=None):
         for dofs in locate_BC_list:

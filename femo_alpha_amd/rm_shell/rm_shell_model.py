@@ -263,8 +263,8 @@ class RMShellModel:
         if self.layup is not None and shell_pde.ply_npt:
             self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, None)
         if self.ply_failure is not None:
-            # (nel, npt) flattened; a diagnostic with forward-mode tangents only (FEA.field_tangents), so it is not registered as a
-            # field output of the CSDL model, whose operations differentiate in reverse
+            # (nel, npt) flattened, differentiated through FEA.field_tangents (forward) and FEA.field_gradients (reverse: local failure
+            # constraints in groups of four adjoint solves); registering it as a field output of the CSDL model is a separate step
             self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, ply)
         self.fea = fea
 

@@ -173,7 +173,9 @@ class RMShellPDE:
 
     def ply_failure_field(self, w, uhat, ply_table):
         """The (nel, npt) field of the largest ply failure index per cell and recovery point as a field form: its tangents come
-        from ``computeMatVecProductFwd(computePartials(form, f), v)`` and ``FEA.field_tangents`` (forward mode only)."""
+        from ``computeMatVecProductFwd(computePartials(form, f), v)`` and ``FEA.field_tangents``, its reverse products and total
+        gradients from ``computeMatVecProductBwd(computePartials(form, f), cbar)`` and ``FEA.field_gradients``, and
+        ``assemble(computePartials(form, f), dim=2)`` is its sparse partial Jacobian (state and ply table)."""
         return FieldForm(self.ctx, "ply_failure_field")
 
     def pnorm_stress(self, w, uhat, h, E, nu, dx=None, m=1e-6, rho=100, alpha=None, regularization=False):

@@ -135,10 +135,12 @@ int femo_set_laminate(femo_ctx* ctx, const double* clt, int64_t n);
  *     ((dR/d ply_table)^T lambda is zero), "F_solid" as for any functional.  wrt / arg "uhat" is refused: the shape derivative of this
  *     output is not provided.  No float atomics and fixed summation orders: two identical calls return the same bits;
  *   - field femo_ply_failure_field: (nel, npt), entry = max over the cell's quadrature points of FI, every cell whatever the selected
- *     sub-domain (a diagnostic -- which ply, where; differentiated in forward mode only: femo_field_output_jvp and
- *     femo_field_total_jvp, name "ply_failure_field").  The tangent of an entry is the tangent of FI at the quadrature point that
- *     attains the maximum; on ties the first point in quadrature order wins -- the point the value's running maximum keeps, which a
- *     strict > replaces.  It is the one-sided derivative wherever the maximiser is unique.
+ *     sub-domain (which ply, where -- what a local strength constraint is written in).  Differentiated under the name
+ *     "ply_failure_field" in forward mode (femo_field_output_jvp, femo_field_total_jvp) and in reverse (femo_field_output_vjp,
+ *     femo_field_output_jacobian, femo_field_total_gradients).  The derivative of an entry is the derivative of FI at the quadrature
+ *     point that attains the maximum; on ties the first point in quadrature order wins -- the point the value's running maximum
+ *     keeps, which a strict > replaces -- in both modes, which are exact transposes of each other.  It is the one-sided derivative
+ *     wherever the maximiser is unique.
  * femo_set_ply_table is refused with the cell index for non-finite entries, and when not in laminate mode, for npt out of range or a
  * wrong n.  table == NULL with n == 0 removes the table; leaving laminate mode removes it too.  The operator does not see the table:
  * the factor and the Jacobi diagonal are kept.  With a table "ply_table" is an ordinary field (femo_field_size / femo_set_field /
@@ -170,8 +172,10 @@ int femo_ply_failure_field(femo_ctx* ctx, double* out, int64_t n);
  *   - both names are arguments of femo_dfunctional, femo_dRdarg_T, femo_residual_jvp, femo_total_gradient(s) and femo_total_jvp, by
  *     d/dx = (d laminate/dx)^T [d/d laminate] + (d table/dx)^T [d/d ply_table] (or its forward counterpart), composed on the device.
  *     Angle derivatives are per degree;
- *   - not provided: the derivatives of the field outputs with respect to the layup (femo_field_output_vjp / _jvp / _jacobian,
- *     femo_field_total_gradients / _jvp, femo_field_gradient_vec and femo_dist_gradient refuse both names), the regularisation
+ *   - both names are arguments of femo_field_output_vjp and femo_field_total_gradients for the field "ply_failure_field" (below);
+ *   - not provided: every other derivative of the field outputs with respect to the layup (the stress fields in femo_field_output_vjp
+ *     and femo_field_total_gradients, and every field in femo_field_output_jvp, femo_field_output_jacobian, femo_field_total_jvp,
+ *     femo_field_gradient_vec and femo_dist_gradient refuse both names), the regularisation
  *     from the layup (it keeps the "thickness" field, as "mass" and "volume" keep "thickness" and "density"), per-cell ply
  *     materials, the multi-GPU driver and transient laminates.
  * Mass and volume from the layup (femo_alpha_amd/csrc/layup_mass.h) -- new: two functionals of the layup itself, over the selected
@@ -437,7 +441,20 @@ int femo_field_output(femo_ctx* ctx, const char* name, double* out, int64_t n);
  * femo_field_total_gradients: total derivatives of g_k = cbar_k . field through the solved state, for nbar cotangents:
  *   lambda_k = K^-1 (d field / d w)^T cbar_k (one grouped multi-right-hand-side solve, strong-BC rows masked, as in
  *   femo_total_gradients), out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k (nbar x n); iters, relres:
- *   nbar entries or NULL. */
+ *   nbar entries or NULL.
+ * name = "ply_failure_field" (laminate mode with a table; csrc/ply_field_rev.h): a cotangent has nel * npt entries, cell-major like
+ * femo_ply_failure_field; the maximiser convention is stated at femo_set_ply_table above and is the forward mode's.
+ *   femo_field_output_vjp: wrt "disp_solid" and "ply_table" (16 npt nel, cell-major); exact zeros for "laminate", "thickness", "E",
+ *     "nu", "density", "F_solid"; under an active layup "ply_thickness" / "ply_angle", the table cotangent pulled back through the
+ *     layup on the device.  Row k of the result has the bits of the single call on cbar_k.
+ *   femo_field_output_jacobian(_nnz): nel * npt rows (row npt*e + p), ld entries per row for "disp_solid" (columns in the cell's
+ *     local order), 16 for "ply_table" (columns 16 (npt*e + p) + k), 0 for the six arguments above; the layup names are refused.
+ *   femo_field_total_gradients: arg "laminate" and "F_solid" (no explicit partial), "ply_table", "thickness", "E", "nu", "density"
+ *     (R does not depend on them in laminate mode: no solve runs, iters and relres come back 0), and "ply_thickness" / "ply_angle":
+ *     -(dR / d laminate)^T lambda_k and (d field / d table)^T cbar_k through one pull-back of the layup.  k local failure constraints
+ *     cost ceil(k / 4) grouped adjoint solves.
+ *   Refused (nothing is written): "uhat" (the shape derivative of this output is not provided), a missing table (the message names
+ *   femo_set_ply_table), a wrong n.  No float atomics, fixed summation orders: two identical calls return the same bits. */
 int femo_field_output_vjp(femo_ctx* ctx, const char* name, const char* wrt, const double* cbar, int64_t nbar, double* out, int64_t n);
 int femo_field_output_jacobian_nnz(femo_ctx* ctx, const char* name, const char* wrt, int64_t* nnz);
 int femo_field_output_jacobian(femo_ctx* ctx, const char* name, const char* wrt, int64_t* rowptr, int32_t* colidx, double* vals,
@@ -525,7 +542,10 @@ int femo_total_gradients(femo_ctx* ctx, int32_t nfun, const char* const* functio
 int femo_last_timing(const femo_ctx* ctx, double* out5);
 
 /* Average duration (ms) of `reps` back-to-back launches of one kernel, timed with HIP events on
- * the context's stream: "apply" (matrix-free element operator), "pcg_update", "pcg_direction", "diag". */
+ * the context's stream: "apply" (matrix-free element operator), "pcg_update", "pcg_direction", "diag"; with a ply table
+ * "ply_value" (the aggregate's value pass), "ply_dw" (its state gradient as femo_dfunctional enqueues it: value pass, gradient
+ * kernel, gather), "ply_field_vjp" (the field's reverse product with respect to the state: kernel and gather) and
+ * "ply_field_vjp_table" (with respect to the table), the last two for a cotangent of ones. */
 int femo_bench_kernel(femo_ctx* ctx, const char* name, int32_t reps, double* avg_ms);
 
 /* ---- Building blocks of the element-partitioned multi-GPU driver (femo_alpha_amd/parallel.py).  The
