@@ -38,6 +38,10 @@ SIGNATURES = {
     "femo_layup_jvp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _c_double_p, C.c_int64, _c_double_p, _c_double_p]),
     "femo_layup_vjp": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64]),
     "femo_ply_failure_field": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
+    "femo_set_ply_shear_table": (C.c_int, [C.c_void_p, _c_double_p, C.c_int32, C.c_int64]),
+    "femo_set_ply_shear_params": (C.c_int, [C.c_void_p, C.c_double]),
+    "femo_ply_shear_failure_field": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
+    "femo_set_layup_shear_strength": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p]),
     "femo_set_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_get_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_apply_K": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),

@@ -166,7 +166,7 @@ class ShellContext:
 
     LAYUP_SURFACES = {"bot": 1, "mid": 2, "top": 4}
 
-    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None):
+    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None, shear_strength=None):
         """Layup mode (femo_set_layup): the laminate and the ply table are built on the device from ply thicknesses ``t`` and ply
         angles ``theta`` (degrees from E0), both (nel, nply) in solver cell order or (nply,) for the same layup in every cell; plies
         bottom to top.  ``plies``: one dict per ply, or one for all, with E1, E2, G12, nu12, G13, G23 and either the strengths
@@ -176,7 +176,9 @@ class ShellContext:
         once; the mode then holds it constant.  ``plies=None`` leaves the mode and keeps the laminate and the table as ordinary
         values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points.
         ``density``: the (nply,) ply densities of the functional "layup_mass" (``set_layup_density``); None leaves whatever densities
-        the context holds (a layup of another ply count drops them)."""
+        the context holds (a layup of another ply count drops them).  ``shear_strength``: the (nply, 2) or (2,) transverse shear
+        strengths [S13, S23] of the outputs "ply_shear_failure" / "ply_shear_failure_field" (``set_layup_shear_strength``); None
+        likewise leaves what the context holds."""
         if plies is None:
             self._chk(self.lib.femo_set_layup(self._h, 0, None, 0, 0.0, None, None))
             return
@@ -198,6 +200,8 @@ class ShellContext:
         self._chk(self.lib.femo_set_layup(self._h, int(nply), dptr(pc), int(sum(bits)), float(c_drill), dptr(t), dptr(theta)))
         if density is not None:
             self.set_layup_density(density)
+        if shear_strength is not None:
+            self.set_layup_shear_strength(shear_strength)
 
     def set_layup_density(self, rho=None):
         """Ply densities of the functional "layup_mass" (femo_set_layup_density): (nply,) values, finite and >= 0, the same in every
@@ -270,6 +274,47 @@ class ShellContext:
         out = np.empty(max(n, 0) // 16)
         self._chk(self.lib.femo_ply_failure_field(self._h, dptr(out), out.size))
         return out.reshape(self.mesh.nel, -1)
+
+    def set_ply_shear_table(self, table=None, npt=None):
+        """Recovery points of the interlaminar shear outputs (femo_set_ply_shear_table; laminate mode): ``table`` is the
+        (nel, npt, 6) array of ``laminate.ply_shear_table`` in solver cell order (or flat, with ``npt`` given); ``None`` removes it.
+        The factor is kept.  Refused under a layup that carries shear strengths (``set_layup(..., shear_strength=...)``)."""
+        if table is None:
+            self._chk(self.lib.femo_set_ply_shear_table(self._h, None, 0, 0))
+            return
+        a = np.asarray(table, dtype=np.float64)
+        if npt is None:
+            if a.ndim != 3:
+                raise ValueError("set_ply_shear_table: a (nel, npt, 6) array, or npt")
+            npt = a.shape[1]
+        v = self._vec(a)
+        self._chk(self.lib.femo_set_ply_shear_table(self._h, dptr(v), int(npt), v.size))
+
+    def set_ply_shear_params(self, rho=100.0):
+        """Exponent of the "ply_shear_failure" aggregate (femo_set_ply_shear_params)."""
+        self._chk(self.lib.femo_set_ply_shear_params(self._h, float(rho)))
+
+    def ply_shear_failure_field(self):
+        """(nel, npt): the interlaminar shear failure index of the cell-mean transverse shear strain, per recovery point
+        (femo_ply_shear_failure_field)."""
+        n = int(self.lib.femo_field_size(self._h, b"ply_shear_table"))
+        out = np.empty(max(n, 0) // 6)
+        self._chk(self.lib.femo_ply_shear_failure_field(self._h, dptr(out), out.size))
+        return out.reshape(self.mesh.nel, -1)
+
+    def set_layup_shear_strength(self, S=None):
+        """Transverse shear strengths of the plies of the active layup (femo_set_layup_shear_strength): (nply, 2) values [S13, S23],
+        or (2,) for all plies, finite and > 0; ``None`` removes them.  With them the layup builds the shear table (one point per ply)
+        on the device and rebuilds it when "ply_angle" is set; they live with the layup as the densities do.  The factor is kept."""
+        if S is None:
+            self._chk(self.lib.femo_set_layup_shear_strength(self._h, 0, None))
+            return
+        s = np.asarray(S, dtype=np.float64).reshape(-1, 2)
+        n = int(self.lib.femo_field_size(self._h, b"ply_thickness"))       # < 0 outside a layup: the library refuses with its own message
+        if s.shape[0] == 1 and n > 0:
+            s = np.broadcast_to(s, (n // self.mesh.nel, 2))
+        s = np.ascontiguousarray(s)
+        self._chk(self.lib.femo_set_layup_shear_strength(self._h, s.shape[0], dptr(s)))
 
     def set_quadrature(self, nquad):
         """The rule of the static forms (femo_set_quadrature): Gauss points per direction on quadrilaterals, the degree of the symmetric
@@ -735,9 +780,12 @@ class ShellContext:
         return cb.reshape(-1, nc)
 
     def field_size_of(self, name):
-        """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field'."""
+        """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field' and
+        'ply_shear_failure_field' (the recovery points of their own tables)."""
         if name == "ply_failure_field":
             return max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // 16
+        if name == "ply_shear_failure_field":
+            return max(int(self.lib.femo_field_size(self._h, b"ply_shear_table")), 0) // 6
         return self.mesh.nvc * self.mesh.nel
 
     def field_output_jvp(self, name, wrt, V):

@@ -11,6 +11,7 @@
 #include "stress_history.h"
 #include "disp_history.h"
 #include "ply_failure.h"
+#include "ply_shear.h"
 #include "field_jvp.h"
 #include "ply_field_rev.h"
 #include "layup.h"
@@ -38,7 +39,7 @@ constexpr int WIDE_NP_DEFAULT = 512;    // option "wide_np" overrides it for the
 constexpr int WIDE_CNT_DEFAULT = 512;   // option "wide_cnt": levels with at most this many fronts also take the wide (many workgroups per
                                         // front) solve kernels -- one workgroup per front cannot pull a level's factor out of HBM
 
-#define FEMO_VERSION 101
+#define FEMO_VERSION 102
 
 static std::string g_create_error;
 
@@ -132,6 +133,15 @@ struct femo_ctx {
         DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
         DevBuf<int> eslot;          // slot of every cell in ybuf (the inverse of eorder), built at first use
     } ply;
+    // interlaminar shear outputs (femo_set_ply_shear_table; ply_shear.h; laminate mode only): npt recovery points of PSH_W doubles per cell
+    struct PlyShear {
+        int npt = 0;                // 0: no table
+        double rho = 100.0;         // femo_set_ply_shear_params
+        DevBuf<double> tab;         // cell-major (femo_get_field, the layout of d K / d table)
+        DevBuf<double> tabT;        // entry-major [6 p + k][nel]: what the kernels read
+        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
+        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_shear_dtable")
+    } psh;
     // layup mode (femo_set_layup; layup.h): the laminate and the ply table are built on the device from ply thicknesses and angles
     struct Layup {
         bool active = false;
@@ -146,6 +156,11 @@ struct femo_ctx {
         bool has_rho = false;
         DevBuf<double> rho;         // nply values
         DevBuf<double> mpart, mres; // block slots of the value pass; { layup_mass, layup_volume } of k_layup_mass_combine
+        // per-ply shear strengths of "ply_shear_failure" (femo_set_layup_shear_strength): they live and leave with the layup, and
+        // with them the layup owns the shear table (one recovery point per ply)
+        bool has_shear = false;
+        DevBuf<double> sf;          // nply x [F55, F44] = [1 / S13^2, 1 / S23^2]
+        DevBuf<double> sbar;        // shear table cotangent of the chain rule
     } lay;
     // max-displacement aggregates of the static state (femo_set_disp_aggregate; disp_aggregate.h): four parameter slots, and the node
     // mask of every selection that has been asked for, kept until the cell tags change
@@ -628,6 +643,10 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_PF_FIELD , PF_FIELD
 #define COMMA_PF_DW , PF_DW
 #define COMMA_PF_DTABLE , PF_DTABLE
+#define COMMA_PS_VALUE , PS_VALUE
+#define COMMA_PS_FIELD , PS_FIELD
+#define COMMA_PS_DW , PS_DW
+#define COMMA_PS_DTABLE , PS_DTABLE
 
 static const int EB = 128;   // element kernels: threads per block (one element per thread)
 
@@ -2084,6 +2103,7 @@ static double* field_ptr(const femo_ctx* c, const char* name, int64_t* n) {
     if (s == "dirichlet" && c->gdir) { *n = c->ndof; return c->gdir; }
     if (s == "laminate" && c->laminate) { *n = (int64_t)LAM_W * c->nel; return c->clt; }
     if (s == "ply_table" && c->ply.npt > 0) { *n = (int64_t)PLY_W * c->ply.npt * c->nel; return c->ply.tab; }
+    if (s == "ply_shear_table" && c->psh.npt > 0) { *n = (int64_t)PSH_W * c->psh.npt * c->nel; return c->psh.tab; }
     // layup mode: nel x nply values; the device copies are ply-major ([k][nel]), the ABI's vectors cell-major
     if (s == "ply_thickness" && c->lay.active) { *n = (int64_t)c->nel * c->lay.nply; return c->lay.t; }
     if (s == "ply_angle" && c->lay.active) { *n = (int64_t)c->nel * c->lay.nply; return c->lay.th; }
@@ -2169,6 +2189,11 @@ int femo_set_field(femo_ctx* c, const char* name, const double* v, int64_t n) {
         const std::string s(name);
         if (s == "laminate" || s == "ply_table") return fail(c, "field '" + s + "'" + LAYUP_OWNS);
         if (s == "ply_thickness" || s == "ply_angle") return layup_set_field(c, s == "ply_angle", v, n);
+    }
+    if (name && std::string(name) == "ply_shear_table") {
+        if (c->psh.npt == 0) return fail(c, "field 'ply_shear_table' exists once a table is set (femo_set_ply_shear_table)");
+        if (!v) return fail(c, "null values");
+        return femo_set_ply_shear_table(c, v, c->psh.npt, n);
     }
     if (name && std::string(name) == "laminate") {
         if (!c->laminate) return fail(c, "field 'laminate' exists in laminate mode only (femo_set_laminate)");
@@ -2259,6 +2284,7 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
             c->clt.reset();
             c->clt_sym.reset();
             c->ply = femo_ctx::Ply();                          // the recovery points belong to the laminate
+            c->psh = femo_ctx::PlyShear();
             c->lay = femo_ctx::Layup();                        // ... and so does the layup
             operator_changed(c);
             ++c->opt_version;
@@ -2375,6 +2401,57 @@ int femo_set_ply_failure_params(femo_ctx* c, double rho) {
     return 0;
 }
 
+static const char* const LAYUP_OWNS_SHEAR = ": the shear table belongs to the active layup and its shear strengths (femo_set_layup_shear_strength); set "
+                                            "'ply_angle', or remove the strengths with femo_set_layup_shear_strength(ctx, 0, NULL)";
+
+int femo_set_ply_shear_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->lay.active && c->lay.has_shear) return fail(c, std::string("femo_set_ply_shear_table") + LAYUP_OWNS_SHEAR);
+    const double rho = c->psh.rho;
+    if (!table && n == 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->psh = femo_ctx::PlyShear();
+        c->psh.rho = rho;
+        return 0;
+    }
+    char buf[240];
+    if (!c->laminate) return fail(c, "ply shear table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
+    if (npt < 1 || npt > PLY_MAX) {
+        snprintf(buf, sizeof buf, "ply shear table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
+        return fail(c, buf);
+    }
+    const int64_t len = (int64_t)PSH_W * npt * c->nel;
+    if (!table || n != len) {
+        snprintf(buf, sizeof buf, "ply shear table: expected %d values per recovery point [Gs (2x2), F55, F44] x %d points x %d cells = %lld, got %lld%s",
+                 PSH_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
+        return fail(c, buf);
+    }
+    const int64_t per = (int64_t)PSH_W * npt;
+    for (int64_t i = 0; i < len; ++i)
+        if (!std::isfinite(table[i])) {
+            const int64_t e = i / per, r = i - e * per;
+            snprintf(buf, sizeof buf, "ply shear table: value %d of recovery point %d of cell %lld is not finite", (int)(r % PSH_W), (int)(r / PSH_W),
+                     (long long)e);
+            return fail(c, buf);
+        }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->psh.tab.grow((size_t)len));
+    HIPCHK(c, c->psh.tabT.grow((size_t)len));
+    HIPCHK(c, hipMemcpy(c->psh.tab, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->psh.tab, c->psh.tabT.get(), c->nel,
+                       (int)per);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->psh.npt = npt;
+    return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
+}
+
+int femo_set_ply_shear_params(femo_ctx* c, double rho) {
+    if (!(rho > 0.0) || !std::isfinite(rho)) return fail(c, "ply_shear_failure: rho must be finite and > 0");
+    c->psh.rho = rho;
+    return 0;
+}
+
 // ---- layups (layup.h): the laminate and the ply table built on the device from ply thicknesses and angles
 // 0: not a layup argument (or no layup is active); 1: "ply_thickness"; 2: "ply_angle"
 static int layup_wrt(const femo_ctx* c, const std::string& s) {
@@ -2425,6 +2502,27 @@ static int layup_check(femo_ctx* c, const double* t, const double* th, int nply)
 static int layup_build(femo_ctx* c) {
     hipLaunchKernelGGL(k_layup_build, dim3(nblk(c->nel, LAY_BLOCK)), dim3(LAY_BLOCK), 0, c->stream, layup_dev(c, c->lay.t, c->lay.th), c->clt.get(),
                        c->clt_sym.get(), c->ply.tab.get(), c->ply.tabT.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// the shear table of a layup that carries shear strengths (one recovery point per ply), enqueued on the stream; the ply
+// thicknesses do not enter, so only a change of the angles or of the strengths comes here
+static int layup_shear_build(femo_ctx* c) {
+    if (!c->lay.has_shear) return 0;
+    const size_t len = (size_t)PSH_W * c->lay.nply * c->nel;
+    HIPCHK(c, c->psh.tab.grow(len));
+    HIPCHK(c, c->psh.tabT.grow(len));
+    hipLaunchKernelGGL(k_layup_shear_build, dim3(nblk(c->nel, LAY_BLOCK)), dim3(LAY_BLOCK), 0, c->stream, layup_dev(c, c->lay.t, c->lay.th),
+                       (const double*)c->lay.sf, c->psh.tab.get(), c->psh.tabT.get());
+    HIPCHK(c, hipGetLastError());
+    c->psh.npt = c->lay.nply;
+    return 0;
+}
+
+// out (nel nply, cell-major, device) += (d shear table / d ply_angle)^T sbar, per degree
+static int layup_shear_vjp_dev(femo_ctx* c, const double* sbar, double* out) {
+    hipLaunchKernelGGL(k_layup_shear_vjp, dim3(nblk(c->nel, LAY_BLOCK)), dim3(LAY_BLOCK), 0, c->stream, layup_dev(c, c->lay.t, c->lay.th), sbar, out);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -2515,9 +2613,16 @@ int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfa
     std::swap(lay.t, lay.tn);
     std::swap(lay.th, lay.thn);
     if (lay.nply != nply) lay.has_rho = false;             // the densities belong to the plies they were given for
+    if (lay.nply != nply && lay.has_shear) {               // ... and so do the shear strengths, with the table built from them
+        const double rho = c->psh.rho;
+        lay.has_shear = false;
+        c->psh = femo_ctx::PlyShear();
+        c->psh.rho = rho;
+    }
     lay.nply = nply; lay.surfaces = surfaces; lay.npt = npt; lay.c_drill = c_drill;
     lay.active = true;
     if (int rc = layup_build(c)) return rc;
+    if (int rc = layup_shear_build(c)) return rc;
     c->laminate = true;
     operator_changed(c, !entering);
     ++c->opt_version;
@@ -2550,6 +2655,43 @@ int femo_set_layup_density(femo_ctx* c, int32_t nply, const double* rho) {
     return 0;                                              // the operator does not see the densities: factor and Jacobi diagonal stay
 }
 
+int femo_set_layup_shear_strength(femo_ctx* c, int32_t nply, const double* S) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& lay = c->lay;
+    if (!lay.active) return fail(c, "femo_set_layup_shear_strength: no layup is active (femo_set_layup)");
+    if (nply == 0 && !S) {                                 // remove the strengths, and the table that was built from them
+        if (lay.has_shear) {
+            const double rho = c->psh.rho;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            lay.has_shear = false;
+            c->psh = femo_ctx::PlyShear();
+            c->psh.rho = rho;
+        }
+        return 0;
+    }
+    char buf[200];
+    if (nply != lay.nply) {
+        snprintf(buf, sizeof buf, "femo_set_layup_shear_strength: the layup has %d plies, got %d pairs of strengths", lay.nply, (int)nply);
+        return fail(c, buf);
+    }
+    if (!S) return fail(c, "femo_set_layup_shear_strength: null values (S: nply x [S13, S23])");
+    std::vector<double> sf(2 * (size_t)nply);
+    for (int k = 0; k < nply; ++k)
+        for (int j = 0; j < 2; ++j) {
+            const double s = S[2 * k + j];
+            if (!std::isfinite(s) || !(s > 0.0)) {
+                snprintf(buf, sizeof buf, "femo_set_layup_shear_strength: the strength %s of ply %d is not finite and > 0", j ? "S23" : "S13", k);
+                return fail(c, buf);
+            }
+            sf[2 * k + j] = 1.0 / (s * s);
+        }
+    HIPCHK(c, lay.sf.grow(sf.size()));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(lay.sf, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
+    lay.has_shear = true;
+    return layup_shear_build(c);                           // the operator does not see the strengths: factor and Jacobi diagonal stay
+}
+
 static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n) {
     auto& lay = c->lay;
     const int64_t len = (int64_t)c->nel * lay.nply;
@@ -2564,6 +2706,8 @@ static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n) 
     if (int rc = layup_check(c, angle ? lay.t.get() : cand.get(), angle ? cand.get() : lay.th.get(), lay.nply)) return rc;
     std::swap(angle ? lay.th : lay.t, cand);
     if (int rc = layup_build(c)) return rc;
+    if (angle)
+        if (int rc = layup_shear_build(c)) return rc;
     operator_changed(c, true);
     ++c->opt_version;
     return 0;
@@ -2980,6 +3124,69 @@ static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
     return ply_gather_sum(c, out);
 }
 
+// ---- interlaminar shear failure aggregate and field (ply_shear.h); slots, combine, eslot and gather are the ply failure's
+static int shear_need_table(femo_ctx* c, const char* who) {
+    if (c->psh.npt > 0) return 0;
+    return fail(c, std::string(who) + ": no ply shear table is set (femo_set_ply_shear_table, laminate mode)");
+}
+
+// the refusals every derivative entry point makes for the aggregate before it does anything else
+static int shear_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
+    if (fn != "ply_shear_failure") return 0;
+    if (shear_need_table(c, "ply_shear_failure")) return 2;
+    if (arg == "uhat") return fail(c, "ply_shear_failure: the shape derivative (uhat) of this output is not provided");
+    return 0;
+}
+
+// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
+static int shear_value_launch(femo_ctx* c) {
+    auto& ps = c->psh;
+    const int g = nblk(c->nel, PLY_BLOCK);
+    HIPCHK(c, ps.part.grow((size_t)3 * g));
+    HIPCHK(c, ps.res.grow(4));
+    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
+                (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ps.part.get());
+    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ps.part, stress_alpha_ref(c), ps.npt, ps.rho, ps.res.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
+static int shear_value_dev(femo_ctx* c, double out4[4]) {
+    if (shear_need_table(c, "ply_shear_failure")) return 2;
+    if (shear_value_launch(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->psh.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
+    if (!std::isfinite(out4[2])) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "ply_shear_failure: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
+                                  "non-finite state or failure index", out4[0], out4[3], c->psh.rho);
+        return fail(c, msg);
+    }
+    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
+    return 0;
+}
+
+// (d / d w) into out (ndof) or (d / d table) into out (6 npt nel, cell-major).  cbar null: of the aggregate K over the selected
+// sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
+static int shear_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, double* out) {
+    auto& ps = c->psh;
+    if (!cbar && shear_value_launch(c)) return 1;
+    const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+    if (!wrt_state) {
+        ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_DTABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
+                    (const double*)c->w, (const double*)ps.res, cbar, (const int*)nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    if (int rc = ply_eslot(c)) return rc;
+    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_DW, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
+                (const double*)c->w, (const double*)ps.res, cbar, (const int*)c->ply.eslot, c->ybuf.get());
+    return ply_gather_sum(c, out);
+}
+
 // ---- mass and volume from the layup (layup_mass.h): outputs of the layup itself, not of the laminate, and independent of the state
 static bool layup_mass_name(const femo_ctx* c, const std::string& fn) {
     return c->lay.active && (fn == "layup_mass" || fn == "layup_volume");
@@ -3203,6 +3410,12 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         *value = v[2];
         return 0;
     }
+    if (s == "ply_shear_failure") {
+        double v[4];
+        if (int rc = shear_value_dev(c, v)) return rc;
+        *value = v[2];
+        return 0;
+    }
     if (const int slot = disp_agg_slot(s); slot >= 0) {
         double v[4];
         if (int rc = disp_agg_value_dev(c, s, slot, v)) return rc;
@@ -3263,6 +3476,18 @@ static int shape_gradient_dev(femo_ctx* c, int mode, const double* w, const doub
 static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string& wrt, double* out, int64_t n) {
     // the layup's own outputs first: the composition below reaches the layup through the laminate and the table, which these never see
     if (layup_mass_name(c, fn)) return layup_mass_grad_dev(c, fn, wrt, out, n);
+    if (const int lw = layup_wrt(c, wrt); lw && fn == "ply_shear_failure") {
+        // the shear table of a layup sees the ply angles alone: d/d ply_angle = (d shear table / d ply_angle)^T [d/d ply_shear_table];
+        // the ply_thickness partial is exact zeros (its total comes through the laminate and the adjoint)
+        if (shear_need_table(c, "ply_shear_failure")) return 2;
+        if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+        HIPCHK(c, hipGetLastError());
+        if (lw == 1 || !c->lay.has_shear) return 0;
+        HIPCHK(c, c->lay.sbar.grow((size_t)PSH_W * c->psh.npt * c->nel));
+        if (int rc = shear_grad_dev(c, false, nullptr, c->lay.sbar)) return rc;
+        return layup_shear_vjp_dev(c, c->lay.sbar, out);
+    }
     if (const int lw = layup_wrt(c, wrt)) {
         // the composition d/dx = (d laminate / dx)^T [d/d laminate] + (d table / dx)^T [d/d ply_table], on device buffers
         if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
@@ -3289,6 +3514,12 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
         if (wrt == "disp_solid" || wrt == "ply_table") return ply_grad_dev(c, wrt == "disp_solid", out);
         HIPCHK(c, hipGetLastError());
         return 0;                                             // laminate, thickness, E, nu, density, F_solid: no explicit dependence
+    }
+    if (fn == "ply_shear_failure") {
+        if (int rc = shear_gate(c, fn, wrt)) return rc;
+        if (wrt == "disp_solid" || wrt == "ply_shear_table") return shear_grad_dev(c, wrt == "disp_solid", nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;                                             // laminate, ply_table, thickness, E, nu, density, F_solid: no explicit dependence
     }
     if (const int slot = disp_agg_slot(fn); slot >= 0) {      // nodal values, not integrals: the state is the only argument they see
         if (wrt == "disp_solid") return disp_agg_grad_dev(c, fn, slot, out);
@@ -3361,7 +3592,7 @@ static int dRdarg_T_dev(femo_ctx* c, const std::string& arg, const double* lam, 
     else if (arg == "E") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_E, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "nu") ELEM_LAUNCH(c, k_dRdfield_T, COMMA_NU, g, EB, m, f, c->tab, c->w, lam, scale, out);
     else if (arg == "F_solid") ELEM_LAUNCH(c, k_dRdf_T, NOEXTRA, g, EB, m, f, c->tab, lam, -scale, out);
-    else if (arg == "density" || arg == "ply_table") { /* R depends on neither */ }
+    else if (arg == "density" || arg == "ply_table" || arg == "ply_shear_table") { /* R depends on none of them */ }
     else if (arg == "uhat") { if (shape_gradient_dev(c, 0, c->w, lam, scale, out)) return 1; }
     else return fail(c, "(dR/d" + arg + ")^T is not implemented in this build");
     HIPCHK(c, hipGetLastError());
@@ -3398,6 +3629,7 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
         if (ply_need_table(c, "ply_failure")) return 2;
         if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
     }
+    if (int rc = shear_gate(c, fn, a)) return rc;
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     if (layup_mass_name(c, fn)) {                                           // no state dependence: lambda = 0, the total is the partial
@@ -3515,6 +3747,8 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
             if (ply_need_table(c, "ply_failure")) return 2;
             if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
         }
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
@@ -3627,7 +3861,7 @@ static int residual_jvp_dev(femo_ctx* c, const std::string& arg, const double* v
     const int64_t n = c->ndof;
     const int vg = vec_grid(n);
     const bool lam3 = c->laminate && (arg == "thickness" || arg == "E" || arg == "nu");      // the laminate replaces them inside R
-    if (lam3 || arg == "density" || arg == "ply_table") {
+    if (lam3 || arg == "density" || arg == "ply_table" || arg == "ply_shear_table") {
         hipLaunchKernelGGL(k_fill, dim3(vg), dim3(256), 0, c->stream, out, 0.0, n);
         HIPCHK(c, hipGetLastError());
         return 0;
@@ -3749,6 +3983,8 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
             if (ply_need_table(c, "ply_failure")) return 2;
             if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
         }
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     const int keep_sel = c->csel;
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
@@ -5349,15 +5585,18 @@ static int field_vjp_dev(femo_ctx* c, double zf, const std::string& wrt, const d
 // wrt is an argument the ply failure field is differentiated by in reverse, and n its length (n < 0: not checked).  *lw: layup_wrt's
 // 1 or 2; the products and the totals reach the layup through the table (layup_ok), the sparse Jacobian refuses it as the stress
 // fields do.  The shape derivative is refused like the aggregate's and the forward mode's.
-static int ply_field_rev_arg(femo_ctx* c, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
+static int point_field_rev_arg(femo_ctx* c, const char* field, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
     *lw = layup_wrt(c, wrt);
     if (*lw && !layup_ok) return layup_field_refused(c, wrt);
     int64_t len;
     if (wrt == "disp_solid") len = c->ndof;
     else if (!field_ptr(c, wrt.c_str(), &len) || wrt == "dirichlet") return fail(c, "unknown argument '" + wrt + "'");
-    if (wrt == "uhat") return fail(c, "ply_failure_field: the shape derivative (uhat) of this output is not provided");
+    if (wrt == "uhat") return fail(c, std::string(field) + ": the shape derivative (uhat) of this output is not provided");
     if (n >= 0 && len != n) return fail(c, "buffer has the wrong length for '" + wrt + "'");
     return 0;
+}
+static int ply_field_rev_arg(femo_ctx* c, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
+    return point_field_rev_arg(c, "ply_failure_field", wrt, n, layup_ok, lw);
 }
 
 // entries per row of the partial Jacobian of the ply failure field (0: the field does not depend on wrt)
@@ -5395,21 +5634,29 @@ static int ply_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, co
     return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
 }
 
-static int ply_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    if (ply_need_table(c, "ply_failure_field")) return 2;
+// The products of a (nel, npt) field of recovery points with nbar cotangents: shared by "ply_failure_field" and
+// "ply_shear_failure_field".  need_table refuses without a table, arg_vjp is the field's own product for one device cotangent.
+typedef int (*point_field_arg_vjp)(femo_ctx*, const std::string&, int, const double*, double*, int64_t);
+static int point_field_output_vjp(femo_ctx* c, const char* field, int (*need_table)(femo_ctx*, const char*), const int* npt,
+                                  point_field_arg_vjp arg_vjp, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    if (need_table(c, field)) return 2;
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nel * npt entries");
     int lw;
-    if (int rc = ply_field_rev_arg(c, a, n, true, &lw)) return rc;
-    const size_t nc = (size_t)c->nel * c->ply.npt;
+    if (int rc = point_field_rev_arg(c, field, a, n, true, &lw)) return rc;
+    const size_t nc = (size_t)c->nel * *npt;
     DevBuf<double> d;
     HIPCHK(c, d.alloc((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)));
     double* o = d + (size_t)nbar * nc;
     if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(c, "copy of the cotangents failed");
     for (int64_t k = 0; k < nbar; ++k)                   // one cotangent at a time: row k is the single call on cbar[k] bit for bit
-        if (int rc = ply_field_arg_vjp_dev(c, a, lw, d + k * nc, o + k * n, n)) return rc;
+        if (int rc = arg_vjp(c, a, lw, d + k * nc, o + k * n, n)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+static int ply_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    return point_field_output_vjp(c, "ply_failure_field", ply_need_table, &c->ply.npt, ply_field_arg_vjp_dev, a, cbar, nbar, out, n);
 }
 
 static int ply_field_jacobian_nnz(femo_ctx* c, const std::string& a, int64_t* nnz) {
@@ -5504,10 +5751,90 @@ static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cb
     return rc;
 }
 
+// ---- reverse mode of the interlaminar shear field (ply_shear.h: the gradient modes with a cotangent in place of the KS weight), under
+// the name "ply_shear_failure_field".  Forward mode and the sparse Jacobian are not provided.
+static int shear_field_not_provided(femo_ctx* c, const char* who) {
+    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of 'ply_shear_failure_field' are not provided "
+                                      "(femo_field_output_vjp, femo_field_total_gradients)");
+}
+
+// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
+// the table cotangent through the layup's pull-back for the ply angles, exact zeros for every other argument
+static int shear_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    if (wrt == "disp_solid" || wrt == "ply_shear_table") return shear_grad_dev(c, wrt == "disp_solid", cbar, out);
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    HIPCHK(c, hipGetLastError());
+    if (lw != 2 || !c->lay.has_shear) return 0;
+    HIPCHK(c, c->lay.sbar.grow((size_t)PSH_W * c->psh.npt * c->nel));
+    if (int rc = shear_grad_dev(c, false, cbar, c->lay.sbar)) return rc;
+    return layup_shear_vjp_dev(c, c->lay.sbar, out);
+}
+
+static int shear_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    return point_field_output_vjp(c, "ply_shear_failure_field", shear_need_table, &c->psh.npt, shear_field_arg_vjp_dev, a, cbar, nbar, out, n);
+}
+
+// out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k for the shear field, as ply_field_total_gradients: a solve runs for the
+// laminate, the load and the layup only; for the layup lbar_k = -(dR / d laminate)^T lambda_k goes through the layup's pull-back and the
+// shear table cotangent through its own (ply angles).
+static int shear_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
+                                       double* relres) {
+    if (shear_need_table(c, "ply_shear_failure_field")) return 2;
+    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nel * npt entries");
+    if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
+    int lw;
+    if (int rc = point_field_rev_arg(c, "ply_shear_failure_field", a, n, true, &lw)) return rc;
+    const bool solve = lw || a == "laminate" || a == "F_solid";
+    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * c->psh.npt, ng = (size_t)std::max<int64_t>(n, 1);
+    HIPCHK(c, c->mr_io.grow((size_t)nbar * (2 * nd + ng + nc)));
+    double* Bd = c->mr_io;
+    double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * ng;
+    std::vector<double*> B(nbar), X(nbar);
+    for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    int rc = 0;
+    if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
+    if (solve) {
+        for (int k = 0; k < nbar && !rc; ++k) rc = shear_grad_dev(c, true, Cd + k * nc, B[k]);                   // (d field / d w)^T cbar_k
+        if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_k
+    } else {
+        for (int k = 0; k < nbar; ++k) {
+            if (iters) iters[k] = 0;
+            if (relres) relres[k] = 0.0;
+        }
+    }
+    for (int k = 0; k < nbar && !rc; ++k) {
+        double* g = Gd + (size_t)k * n;
+        rc = shear_field_arg_vjp_dev(c, a, lw, Cd + k * nc, g, n);                                               // (d field / d arg)^T cbar_k
+        if (!rc && solve) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                             // - (dR/d arg)^T lambda_k
+    }
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, Gd, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
+    }
+    return rc;
+}
+
+int femo_ply_shear_failure_field(femo_ctx* c, double* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (shear_need_table(c, "femo_ply_shear_failure_field")) return 2;
+    const int64_t len = (int64_t)c->nel * c->psh.npt;
+    if (!out || n != len) return fail(c, "femo_ply_shear_failure_field: the field has nel * npt entries");
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)len));
+    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->psh.tabT,
+                c->psh.npt, c->psh.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, d.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const double* cbar, int64_t nbar, double* out, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
+    if (fname == "ply_shear_failure_field") return shear_field_output_vjp(c, a, cbar, nbar, out, n);
     if (fname == "ply_failure_field") return ply_field_output_vjp(c, a, cbar, nbar, out, n);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
@@ -5528,6 +5855,7 @@ int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wr
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
     if (fname == "ply_failure_field") return ply_field_jacobian_nnz(c, a, nnz);
+    if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
@@ -5542,6 +5870,7 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     int64_t want;
     if (fname == "ply_failure_field") return ply_field_jacobian(c, a, rowptr, colidx, vals, nnz);
+    if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
     if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
@@ -5578,6 +5907,7 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     const std::string fname(name ? name : ""), a(arg ? arg : "");
     double zf;
     if (fname == "ply_failure_field") return ply_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
+    if (fname == "ply_shear_failure_field") return shear_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
@@ -5611,6 +5941,7 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
 static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
     double zf;
     if (field_zf(name, &zf)) return (int64_t)c->nvc * c->nel;
+    if (name == "ply_shear_failure_field") { shear_field_not_provided(c, "forward mode"); return -1; }
     if (name != "ply_failure_field") { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
     if (ply_need_table(c, "ply_failure_field")) return -2;
     return (int64_t)c->nel * c->ply.npt;
@@ -5818,6 +6149,15 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
                 cbar_set = true;
             }
             return s == "ply_field_vjp" ? ply_field_vjp_dev(c, false, c->mr_io, c->tmp) : ply_field_vjp_dev(c, true, c->mr_io, c->mr_io.get() + nc);
+        }
+        // interlaminar shear: the value pass with its combine, the state gradient as femo_dfunctional enqueues it (value pass,
+        // PS_DW, gather) and the table product (value pass, PS_DTABLE)
+        if (s == "ply_shear_value" || s == "ply_shear_dw" || s == "ply_shear_dtable") {
+            if (shear_need_table(c, "femo_bench_kernel")) return 2;
+            if (s == "ply_shear_value") return shear_value_launch(c);
+            if (s == "ply_shear_dw") return shear_grad_dev(c, true, nullptr, c->tmp);
+            HIPCHK(c, c->psh.gtab.grow((size_t)PSH_W * c->psh.npt * c->nel));
+            return shear_grad_dev(c, false, nullptr, c->psh.gtab);
         }
         return fail(c, "unknown kernel '" + s + "'");
     };

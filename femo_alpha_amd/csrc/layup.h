@@ -18,6 +18,7 @@
 #pragma once
 #include "shell_device.h"
 #include "ply_failure.h"
+#include "ply_shear.h"
 
 namespace femo {
 
@@ -411,6 +412,50 @@ k_layup_vjp(LayupDev L, const double* __restrict__ lbar, const double* __restric
                 g[k] = LAY_RAD * acc;
                 z0 = z1;
             }
+        }
+    }
+    __syncthreads();
+    lay_slab_add(sh, out, L.nel, L.nply);
+}
+
+// ---- the interlaminar shear table of the layup (ply_shear.h; femo_set_layup_shear_strength): one recovery point per ply,
+// Gs = diag(G13, G23) R(theta) with R = [[m, n], [-n, m]] (laminate._r_gamma), F55 = 1 / S13^2, F44 = 1 / S23^2.  The constitutive
+// first-order-shear recovery is constant within a ply, so the ply thicknesses do not enter.  sf: [F55, F44] per ply.
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_shear_build(LayupDev L, const double* __restrict__ sf, double* __restrict__ tab, double* __restrict__ tabT) {
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    const size_t nel = (size_t)L.nel;
+    if (e >= L.nel) return;
+    for (int k = 0; k < L.nply; ++k) {
+        const double* pc = L.pc + k * LAY_PC;
+        double s, c;
+        sincos(L.th[k * nel + e] * LAY_RAD, &s, &c);
+        const double v[PSH_W] = {pc[4] * c, pc[4] * s, -pc[5] * s, pc[5] * c, sf[2 * k], sf[2 * k + 1]};
+        double* row = tab + ((size_t)e * L.nply + k) * PSH_W;
+        double* col = tabT + (size_t)k * PSH_W * nel + e;
+#pragma unroll
+        for (int j = 0; j < PSH_W; ++j) {
+            row[j] = v[j];
+            col[j * nel] = v[j];
+        }
+    }
+}
+
+// out (nel nply, cell-major) += (d shear table / d theta)^T tbar, per degree; tbar (6 nply nel, cell-major).  dR / dtheta =
+// [[-n, m], [-m, -n]]; the strength entries do not depend on the angle.
+__global__ void __launch_bounds__(LAY_BLOCK)
+k_layup_shear_vjp(LayupDev L, const double* __restrict__ tbar, double* __restrict__ out) {
+    __shared__ double sh[LAY_BLOCK * LAY_LD];
+    const int e = blockIdx.x * LAY_BLOCK + threadIdx.x;
+    const size_t nel = (size_t)L.nel;
+    if (e < L.nel) {
+        double* g = sh + threadIdx.x * LAY_LD;
+        const double* tb = tbar + (size_t)e * L.nply * PSH_W;
+        for (int k = 0; k < L.nply; ++k) {
+            const double* pc = L.pc + k * LAY_PC;
+            double s, c;
+            sincos(L.th[k * nel + e] * LAY_RAD, &s, &c);
+            g[k] = LAY_RAD * (pc[4] * (-s * tb[k * PSH_W] + c * tb[k * PSH_W + 1]) + pc[5] * (-c * tb[k * PSH_W + 2] - s * tb[k * PSH_W + 3]));
         }
     }
     __syncthreads();

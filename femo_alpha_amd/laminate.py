@@ -24,6 +24,7 @@ import numpy as np
 K_SHEAR = 0.833          # linear_shell_model.py:146
 LAM_W = 32               # [A (9), B (9), D (9), A_s (4), c_drill] per cell
 PLY_W = 16               # [G (9), z, F1, F2, F11, F22, F66, F12] per recovery point (femo_set_ply_table)
+PSH_W = 6                # [Gs (4), F55, F44] per recovery point (femo_set_ply_shear_table)
 
 
 def _t_eps(theta_deg):
@@ -192,6 +193,42 @@ def ply_table(E1, E2, G12, nu12, t, theta, strengths, surfaces=("bot", "top"), j
         dz[:, s, :] = a * dzi[:-1] + b * dzi[1:]
     out = out.reshape(nel, nply * ns, PLY_W)
     return (out, dz.reshape(nply * ns, nply)) if jacobian else out
+
+
+def shear_strength(S13, S23):
+    """The two coefficients (F55, F44) = (1 / S13^2, 1 / S23^2) of the interlaminar shear failure index
+    FI = F55 t13^2 + F44 t23^2 from the transverse shear strengths (positive).  Arguments broadcast; the coefficients are the last
+    axis."""
+    S13, S23 = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (S13, S23)))
+    return np.stack([1.0 / S13 ** 2, 1.0 / S23 ** 2], axis=-1)
+
+
+def ply_shear_table(G13, G23, theta, strengths):
+    """Recovery points of the interlaminar shear outputs (femo_set_ply_shear_table): (nel, nply, 6), one point per ply,
+    [Gs (2x2 row-major), F55, F44] with Gs = diag(G13, G23) R(theta) (R: ``_r_shear``), which maps the cell-mean transverse shear
+    strains of the frame to the ply-axis stresses (t13, t23) -- the constitutive first-order-shear recovery, constant within a ply,
+    so the ply thicknesses do not enter.  G13, G23, theta: (nply,) or (nel, nply), plies bottom to top; ``strengths``: the
+    coefficients of ``shear_strength``, (2,), (nply, 2) or (nel, nply, 2)."""
+    G13, G23, theta = np.broadcast_arrays(*(np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (G13, G23, theta)))
+    nel, nply = theta.shape
+    R = _r_shear(theta)
+    out = np.empty((nel, nply, PSH_W))
+    out[..., 0], out[..., 1] = G13 * R[..., 0, 0], G13 * R[..., 0, 1]
+    out[..., 2], out[..., 3] = G23 * R[..., 1, 0], G23 * R[..., 1, 1]
+    out[..., 4:6] = np.broadcast_to(np.asarray(strengths, dtype=np.float64), (nel, nply, 2))
+    return out
+
+
+def ply_shear_table_dtheta(G13, G23, theta):
+    """d Gs / d theta (nel, nply, 2, 2), per degree, of the Gs = diag(G13, G23) R(theta) that ``ply_shear_table`` stores: the only
+    entries of that table that depend on the ply angles (dR / dtheta = [[-n, m], [-m, -n]])."""
+    G13, G23, theta = np.broadcast_arrays(*(np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (G13, G23, theta)))
+    th = np.deg2rad(theta)
+    m, n = np.cos(th), np.sin(th)
+    d = np.empty(theta.shape + (2, 2))
+    d[..., 0, 0], d[..., 0, 1] = -G13 * n, G13 * m
+    d[..., 1, 0], d[..., 1, 1] = -G23 * m, -G23 * n
+    return np.deg2rad(1.0) * d
 
 
 def offset(clt, o):

@@ -111,7 +111,8 @@ class RMShellModel:
         # are built from them on the device.  t and theta give the initial layup ((nply,) or (nel, nply) in caller cell order); with
         # recovery points (surfaces, default bot / top of every ply) the output "ply_failure" exists.  They take the place of the
         # laminate= and ply_table= arguments of evaluate and of ply_failure=npt here.  The outputs "layup_volume" and, with the (nply,)
-        # ply densities density=[...], "layup_mass" are functions of "ply_thickness" and "uhat" alone.
+        # ply densities density=[...], "layup_mass" are functions of "ply_thickness" and "uhat" alone.  With the (nply, 2) transverse
+        # shear strengths shear_strength=[[S13, S23], ...] the output "ply_shear_failure" exists, with the arguments of "ply_failure".
         self.layup = None
         if layup is not None:
             if not self.laminate or self.ply_failure is not None:
@@ -236,6 +237,10 @@ class RMShellModel:
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         if self.layup is not None and shell_pde.ply_npt:
             fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, None, rho=self.rho), arguments=["disp_solid"] + lam_args)
+        if self.layup is not None and shell_pde.layup_shear:
+            # shear_strength=[...] in the layup: the interlaminar shear aggregate, with the arguments ply_failure has on this route
+            fea.add_output(name="ply_shear_failure", form=shell_pde.ply_shear_failure(w, uhat, None, rho=self.rho),
+                           arguments=["disp_solid"] + lam_args)
         if self.layup is not None:
             if shell_pde.layup_density:
                 fea.add_output(name="layup_mass", form=shell_pde.layup_mass(uhat, ply_t), arguments=["ply_thickness", "uhat"])
@@ -262,6 +267,8 @@ class RMShellModel:
                              function_space=("DG", 1), record=False, vtk=True)
         if self.layup is not None and shell_pde.ply_npt:
             self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, None)
+        if self.layup is not None and shell_pde.layup_shear:
+            self.ply_shear_failure_field_form = shell_pde.ply_shear_failure_field(w, uhat, None)
         if self.ply_failure is not None:
             # (nel, npt) flattened, differentiated through FEA.field_tangents (forward) and FEA.field_gradients (reverse: local failure
             # constraints in groups of four adjoint solves); registering it as a field output of the CSDL model is a separate step

@@ -48,9 +48,10 @@ class RMShellPDE:
         # one-ply placeholder (1 mm of a unit-modulus isotropic ply) that the model's "laminate" input replaces.
         self.laminate = bool(laminate)
         self.VL = None
-        # layup=dict(plies, t, theta[, surfaces, c_drill, density]) (laminate mode; ShellContext.set_layup, solver cell order): the
+        # layup=dict(plies, t, theta[, surfaces, c_drill, density, shear_strength]) (laminate mode; ShellContext.set_layup, solver cell order): the
         # laminate and the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the
-        # recovery points, hence "ply_failure", follow from the layup's surfaces, and "layup_mass" from its (nply,) ply densities
+        # recovery points, hence "ply_failure", follow from the layup's surfaces, "layup_mass" from its (nply,) ply densities, and
+        # "ply_shear_failure" from its (nply, 2) transverse shear strengths [S13, S23]
         self.layup = layup
         self.VY = None
         if layup is not None:
@@ -59,8 +60,10 @@ class RMShellPDE:
             t = np.asarray(layup["t"], dtype=np.float64)
             nply = t.shape[-1] if t.ndim else 1
             surfaces = tuple(layup.get("surfaces", ("bot", "top")))
-            self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"), density=layup.get("density"))
+            self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"), density=layup.get("density"),
+                               shear_strength=layup.get("shear_strength"))
             self.layup_density = layup.get("density") is not None
+            self.layup_shear = layup.get("shear_strength") is not None
             self.VY = FunctionSpace(self.ctx, "VY", width=nply)
             self.ply_thickness_init = self.ctx.get_field("ply_thickness")
             self.ply_angle_init = self.ctx.get_field("ply_angle")
@@ -148,6 +151,18 @@ class RMShellPDE:
         ``dx``: None for the whole mesh, or the index of a tagged sub-domain."""
         self.ctx.set_ply_failure_params(rho)
         return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
+
+    def ply_shear_failure(self, w, uhat, ply_shear_table, dx=None, rho=100.0):
+        """KS aggregate of the interlaminar shear failure index over the recovery points of the shear table (include/femo_hip.h,
+        femo_set_ply_shear_table; under a layup with shear strengths the table is the layup's: pass None); ``dx``: None for the whole
+        mesh, or the index of a tagged sub-domain."""
+        self.ctx.set_ply_shear_params(rho)
+        return Form(self.ctx, "ply_shear_failure", subdomain=-1 if dx is None else int(dx))
+
+    def ply_shear_failure_field(self, w, uhat, ply_shear_table):
+        """The (nel, npt) field of the interlaminar shear failure index per cell and recovery point as a field form, in reverse mode
+        only: ``computeMatVecProductBwd(computePartials(form, f), cbar)`` and ``FEA.field_gradients``."""
+        return FieldForm(self.ctx, "ply_shear_failure_field")
 
     def max_disp(self, w, dx=None, slot=0, rho=100.0, scaler=1.0, direction=None, nodes="vertices"):
         """Smooth maximum over the selected nodes of scaler |u_i| (or, with ``direction`` d, of scaler d.u_i; scaler < 0: a smooth minimum
