@@ -35,6 +35,8 @@ SIGNATURES = {
     "femo_set_ply_failure_params": (C.c_int, [C.c_void_p, C.c_double]),
     "femo_set_layup": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, C.c_int32, C.c_double, _c_double_p, _c_double_p]),
     "femo_set_layup_density": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p]),
+    "femo_set_layup_reference": (C.c_int, [C.c_void_p, C.c_double, _c_double_p, C.c_int64]),
+    "femo_get_layup_reference": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), _c_double_p, C.c_int64]),
     "femo_layup_jvp": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, _c_double_p, C.c_int64, _c_double_p, _c_double_p]),
     "femo_layup_vjp": (C.c_int, [C.c_void_p, C.c_char_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64]),
     "femo_ply_failure_field": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),

@@ -166,19 +166,22 @@ class ShellContext:
 
     LAYUP_SURFACES = {"bot": 1, "mid": 2, "top": 4}
 
-    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None, shear_strength=None):
+    def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None, shear_strength=None,
+                  reference=None, offset=None):
         """Layup mode (femo_set_layup): the laminate and the ply table are built on the device from ply thicknesses ``t`` and ply
         angles ``theta`` (degrees from E0), both (nel, nply) in solver cell order or (nply,) for the same layup in every cell; plies
         bottom to top.  ``plies``: one dict per ply, or one for all, with E1, E2, G12, nu12, G13, G23 and either the strengths
         Xt, Xc, Yt, Yc, S (and optionally f12) of ``laminate.tsai_wu`` or its six coefficients as ``F``; or an (nply, 12) array
         [E1, E2, G12, nu12, G13, G23, F1, F2, F11, F22, F66, F12].  ``surfaces``: recovery points of every ply out of "bot", "mid",
-        "top", in that order; () for none (no ply table).  ``c_drill=None`` takes the reference's 12 max(D) of this initial layup
-        once; the mode then holds it constant.  ``plies=None`` leaves the mode and keeps the laminate and the table as ordinary
-        values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points.
+        "top", in that order; () for none (no ply table).  ``c_drill=None`` takes the reference's 12 max(D) of this initial layup,
+        about its reference surface, once; the mode then holds it constant.  ``plies=None`` leaves the mode and keeps the laminate
+        and the table as ordinary values.  Afterwards "ply_thickness" and "ply_angle" are fields and arguments of the scalar derivative entry points.
         ``density``: the (nply,) ply densities of the functional "layup_mass" (``set_layup_density``); None leaves whatever densities
         the context holds (a layup of another ply count drops them).  ``shear_strength``: the (nply, 2) or (2,) transverse shear
         strengths [S13, S23] of the outputs "ply_shear_failure" / "ply_shear_failure_field" (``set_layup_shear_strength``); None
-        likewise leaves what the context holds."""
+        likewise leaves what the context holds.  ``reference`` / ``offset``: the reference surface of the layup
+        (``set_layup_reference``), "mid", "bot", "top" or a number, and per-cell lengths in solver cell order; ``reference=None``
+        leaves the surface the mode holds -- the mid-surface when the mode is entered -- and ``offset`` then has to be None too."""
         if plies is None:
             self._chk(self.lib.femo_set_layup(self._h, 0, None, 0, 0.0, None, None))
             return
@@ -193,15 +196,60 @@ class ShellContext:
         nel = self.mesh.nel
         t = np.ascontiguousarray(np.broadcast_to(t.reshape(-1, nply), (nel, nply)))
         theta = np.ascontiguousarray(np.broadcast_to(theta.reshape(-1, nply), (nel, nply)))
+        active = int(self.lib.femo_field_size(self._h, b"ply_thickness")) >= 0
+        if reference is None:
+            if offset is not None:
+                raise ValueError("set_layup: offset needs a reference ('mid' for a shift of the mid-surface model)")
+            r, off = self.get_layup_reference() if active else (0.0, None)
+        else:
+            r, off = self._layup_reference(reference, offset)
         if c_drill is None:
             # 12 max(D) over all entries of all cells (laminate.pack); D does not depend on the shear moduli
-            D = lam.clt_from_plies(pc[:, 0], pc[:, 1], pc[:, 2], pc[:, 3], pc[:, 4], pc[:, 5], t, theta)[2]
+            D = lam.clt_from_plies(pc[:, 0], pc[:, 1], pc[:, 2], pc[:, 3], pc[:, 4], pc[:, 5], t, theta, reference=r,
+                                   offset=0.0 if off is None else off)[2]
             c_drill = 12.0 * float(np.max(D))
         self._chk(self.lib.femo_set_layup(self._h, int(nply), dptr(pc), int(sum(bits)), float(c_drill), dptr(t), dptr(theta)))
+        if reference is not None:
+            # its arguments have passed the checks of the library above, so the layup and its surface arrive together
+            self._chk(self.lib.femo_set_layup_reference(self._h, r, None if off is None else dptr(off), 0 if off is None else off.size))
         if density is not None:
             self.set_layup_density(density)
         if shear_strength is not None:
             self.set_layup_shear_strength(shear_strength)
+
+    def _layup_reference(self, reference, offset):
+        """(r, offsets (nel,) or None) of a reference surface, checked as femo_set_layup_reference checks them."""
+        from .laminate import reference_position
+        r = reference_position(reference)
+        if offset is None:
+            return r, None
+        off = self._vec(offset)
+        nel = self.mesh.nel
+        if off.size not in (1, nel):
+            raise ValueError(f"layup reference: the offset has length {nel} (nel; one value broadcasts), got {off.size}")
+        bad = np.flatnonzero(~np.isfinite(off))
+        if bad.size:
+            raise ValueError(f"layup reference: the offset of cell {int(bad[0])} is not finite")
+        return r, np.ascontiguousarray(np.broadcast_to(off, (nel,)))
+
+    def set_layup_reference(self, reference, offset=None):
+        """The reference surface of the active layup (femo_set_layup_reference): the surface the mesh stands for.  ``reference``:
+        "mid", "bot", "top", or the number r that places it r H_e below the mid-surface of a cell of total thickness H_e (bot = 1/2,
+        top = -1/2); ``offset``: a further length c_e per cell ((nel,) in solver cell order, or one value), None for none.  The ply
+        interfaces are z_i = sum_{j<i} t_j - (1/2 - r) H_e + c_e; the laminate and the z of the ply table are rebuilt about the
+        surface, and the next solve re-factorises.  The surface stays through new thicknesses, angles and layups until the mode is
+        left.  c_drill, a constant of the mode, stays as it is."""
+        from .laminate import reference_position
+        r = reference_position(reference)
+        off = None if offset is None else self._vec(offset)
+        self._chk(self.lib.femo_set_layup_reference(self._h, r, None if off is None else dptr(off), 0 if off is None else off.size))
+
+    def get_layup_reference(self):
+        """(r, offsets (nel,)) of the active layup's reference surface (femo_get_layup_reference)."""
+        r = C.c_double()
+        off = np.empty(self.mesh.nel)
+        self._chk(self.lib.femo_get_layup_reference(self._h, C.byref(r), dptr(off), off.size))
+        return float(r.value), off
 
     def set_layup_density(self, rho=None):
         """Ply densities of the functional "layup_mass" (femo_set_layup_density): (nply,) values, finite and >= 0, the same in every

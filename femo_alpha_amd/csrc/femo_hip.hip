@@ -161,6 +161,11 @@ struct femo_ctx {
         bool has_shear = false;
         DevBuf<double> sf;          // nply x [F55, F44] = [1 / S13^2, 1 / S23^2]
         DevBuf<double> sbar;        // shear table cotangent of the chain rule
+        // the reference surface (femo_set_layup_reference): it lies r H_e + off[e] below the mid-surface; it lives and leaves with
+        // the mode, whatever the ply count
+        double r = 0.0;
+        bool has_off = false;
+        DevBuf<double> off;         // nel values
     } lay;
     // max-displacement aggregates of the static state (femo_set_disp_aggregate; disp_aggregate.h): four parameter slots, and the node
     // mask of every selection that has been asked for, kept until the cell tags change
@@ -2460,7 +2465,8 @@ static int layup_wrt(const femo_ctx* c, const std::string& s) {
 }
 
 static LayupDev layup_dev(const femo_ctx* c, const double* t, const double* th) {
-    return LayupDev{t, th, c->lay.pc, c->nel, c->lay.nply, c->lay.surfaces, c->lay.npt, c->lay.c_drill};
+    return LayupDev{t, th, c->lay.pc, c->nel, c->lay.nply, c->lay.surfaces, c->lay.npt, c->lay.c_drill, 0.5 - c->lay.r,
+                    c->lay.has_off ? c->lay.off.get() : nullptr};
 }
 
 // host values (nel x nply, cell-major; one value broadcasts) into the ply-major device buffer dst
@@ -2690,6 +2696,59 @@ int femo_set_layup_shear_strength(femo_ctx* c, int32_t nply, const double* S) {
     HIPCHK(c, hipMemcpy(lay.sf, sf.data(), sf.size() * sizeof(double), hipMemcpyHostToDevice));
     lay.has_shear = true;
     return layup_shear_build(c);                           // the operator does not see the strengths: factor and Jacobi diagonal stay
+}
+
+int femo_set_layup_reference(femo_ctx* c, double r, const double* offset, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& lay = c->lay;
+    if (!lay.active) return fail(c, "femo_set_layup_reference: no layup is active (femo_set_layup)");
+    char buf[200];
+    if (!std::isfinite(r)) return fail(c, "femo_set_layup_reference: the position r of the reference surface is not finite");
+    if (!offset) n = 0;
+    if (n != 0 && n != 1 && n != (int64_t)c->nel) {
+        snprintf(buf, sizeof buf, "femo_set_layup_reference: the offset has length %lld (nel; 1 broadcasts; NULL / 0: none), got %lld", (long long)c->nel,
+                 (long long)n);
+        return fail(c, buf);
+    }
+    for (int64_t e = 0; e < n; ++e)
+        if (!std::isfinite(offset[e])) {
+            snprintf(buf, sizeof buf, "femo_set_layup_reference: the offset of cell %lld is not finite", (long long)e);
+            return fail(c, buf);
+        }
+    if (n > 0) {
+        HIPCHK(c, lay.off.grow((size_t)c->nel));
+        HIPCHK(c, hipStreamSynchronize(c->stream));            // kernels in flight may still read the offsets
+        if (n == 1 && c->nel != 1) hipLaunchKernelGGL(k_fill, dim3(vec_grid(c->nel)), dim3(256), 0, c->stream, lay.off.get(), offset[0], (int64_t)c->nel);
+        else HIPCHK(c, hipMemcpy(lay.off, offset, (size_t)c->nel * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipGetLastError());
+    }
+    lay.has_off = n > 0;
+    lay.r = r;
+    if (int rc = layup_build(c)) return rc;                // the shear table does not see the reference surface
+    operator_changed(c, true);
+    ++c->opt_version;
+    return 0;
+}
+
+int femo_get_layup_reference(femo_ctx* c, double* r, double* offset, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& lay = c->lay;
+    if (!lay.active) return fail(c, "femo_get_layup_reference: no layup is active (femo_set_layup)");
+    if (offset && n != (int64_t)c->nel) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "femo_get_layup_reference: the offset has length %lld (nel), got %lld", (long long)c->nel, (long long)n);
+        return fail(c, buf);
+    }
+    if (r) *r = lay.r;
+    if (offset) {
+        if (lay.has_off) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipMemcpy(offset, lay.off, (size_t)c->nel * sizeof(double), hipMemcpyDeviceToHost));
+        } else {
+            std::fill(offset, offset + c->nel, 0.0);
+        }
+    }
+    return 0;
 }
 
 static int layup_set_field(femo_ctx* c, bool angle, const double* v, int64_t n) {

@@ -2,7 +2,9 @@
 // ply angles, with the chain rule forward and back, gfx950, fp64.
 //
 // Conventions of femo_alpha_amd/laminate.py (clt_from_plies, ply_table), followed operation by operation:
-//   plies bottom to top, interfaces z_i = sum_{j<i} t_j - H / 2, H = sum t;  angles in degrees from E0;
+//   plies bottom to top, interfaces z_i = sum_{j<i} t_j - (1/2 - r) H + c_e, H = sum t;  angles in degrees from E0;
+//   the reference surface (femo_set_layup_reference) lies r H + c_e below the mid-surface: r = 0 is the mid-surface, 1/2 the bottom,
+//   -1/2 the top; c_e is data, and it is added only where it is given, so the default performs the mid-surface operations;
 //   T(theta): the strain transformation (_t_eps),  G = Q T,  Qbar = T^T Q T = T^T G,  Qsbar = R^T diag(G13, G23) R;
 //   A = sum (z1 - z0) Qbar,  B = -1/2 sum (z1^2 - z0^2) Qbar,  D = 1/3 sum (z1^3 - z0^3) Qbar,  A_s = K_SHEAR sum t Qsbar;
 //   recovery points ply by ply from the bottom, inside a ply the surfaces bot, mid, top: z_p = z0, (z0 + z1) / 2, z1.
@@ -12,7 +14,7 @@
 // copies of t and theta are ply-major ([k][nel], as tabT, xyz and cells are stored): the 64 cells of a wave read 512 contiguous bytes
 // per ply.  The per-ply constants are the same for every cell and come through the scalar path.  Nothing is indexed by a runtime ply
 // number in registers: a first pass over the plies forms H (and its tangent), a second one everything else, and the pull-back to the
-// thicknesses runs top to bottom with a running suffix sum (d z_i / d t_j = -1/2 + [j < i]).  Vectors of the ABI (directions,
+// thicknesses runs top to bottom with a running suffix sum (d z_i / d t_j = [j < i] - (1/2 - r)).  Vectors of the ABI (directions,
 // gradients, laminate cotangents) are cell-major; a block moves its slab of them through LDS (odd row stride), so that global
 // memory sees contiguous runs on both sides.
 #pragma once
@@ -35,7 +37,15 @@ struct LayupDev {
     const double* pc;       // [nply][LAY_PC]
     int nel, nply, surfaces, npt;
     double c_drill;
+    double zr;              // 1/2 - r of the reference surface, formed on the host
+    const double* off;      // [nel] c_e of the reference surface; null: zero
 };
+
+// the interface above the running thickness sum cs of a cell of total thickness H, about the reference surface; ce = off[e]
+__device__ __forceinline__ double lay_z(const LayupDev& L, double cs, double H, double ce) {
+    const double z = cs - L.zr * H;
+    return L.off ? z + ce : z;
+}
 
 // upper triangle of a symmetric 3 x 3 block: 00 01 02 11 12 22
 __device__ __forceinline__ constexpr int lay_sym(int i, int j) { return i <= j ? (i == 0 ? j : i == 1 ? j + 2 : 5) : lay_sym(j, i); }
@@ -185,7 +195,8 @@ k_layup_build(LayupDev L, double* __restrict__ clt, double* __restrict__ clt_sym
 #pragma unroll
         for (int i = 0; i < 6; ++i) A[i] = B[i] = D[i] = 0.0;
         S[0] = S[1] = S[2] = 0.0;
-        double cs = 0.0, z0 = -0.5 * H;
+        const double ce = L.off ? L.off[e] : 0.0;
+        double cs = 0.0, z0 = lay_z(L, 0.0, H, ce);
         int p = 0;
         for (int k = 0; k < L.nply; ++k) {
             const double* pc = L.pc + k * LAY_PC;
@@ -193,7 +204,7 @@ k_layup_build(LayupDev L, double* __restrict__ clt, double* __restrict__ clt_sym
             LayPly P;
             lay_ply(pc, L.th[k * nel + e], P);
             cs += tk;
-            const double z1 = cs - 0.5 * H;
+            const double z1 = lay_z(L, cs, H, ce);
             const double a = z1 - z0, b = -0.5 * (z1 * z1 - z0 * z0), d = (z1 * z1 * z1 - z0 * z0 * z0) / 3.0;
 #pragma unroll
             for (int i = 0; i < 6; ++i) { A[i] += a * P.Qb[i]; B[i] += b * P.Qb[i]; D[i] += d * P.Qb[i]; }
@@ -251,7 +262,8 @@ k_layup_jvp(LayupDev L, const double* __restrict__ V, double* __restrict__ dlam,
         double* dt_row = dtab ? dtab + (dir * nel + e) * (size_t)L.npt * PLY_W : nullptr;
         double H = 0.0, dH = 0.0;
         for (int k = 0; k < L.nply; ++k) { H += L.t[k * nel + e]; dH += v[k]; }
-        double cs = 0.0, dcs = 0.0, z0 = -0.5 * H, dz0 = -0.5 * dH;
+        const double ce = L.off ? L.off[e] : 0.0;
+        double cs = 0.0, dcs = 0.0, z0 = lay_z(L, 0.0, H, ce), dz0 = -L.zr * dH;
         int p = 0;
         for (int k = 0; k < L.nply; ++k) {
             const double* pc = L.pc + k * LAY_PC;
@@ -259,10 +271,10 @@ k_layup_jvp(LayupDev L, const double* __restrict__ V, double* __restrict__ dlam,
             LayPly P;
             lay_ply(pc, L.th[k * nel + e], P);
             cs += tk;
-            const double z1 = cs - 0.5 * H;
+            const double z1 = lay_z(L, cs, H, ce);
             if (WRT == LAY_T) {
                 dcs += v[k];
-                const double dz1 = dcs - 0.5 * dH;
+                const double dz1 = dcs - L.zr * dH;
                 const double a = dz1 - dz0, b = -(z1 * dz1 - z0 * dz0), d = z1 * z1 * dz1 - z0 * z0 * dz0;
 #pragma unroll
                 for (int i = 0; i < 6; ++i) { A[i] += a * P.Qb[i]; B[i] += b * P.Qb[i]; D[i] += d * P.Qb[i]; }
@@ -353,17 +365,18 @@ k_layup_vjp(LayupDev L, const double* __restrict__ lbar, const double* __restric
         const int ns = L.npt / L.nply;
         double H = 0.0;
         for (int k = 0; k < L.nply; ++k) H += L.t[k * nel + e];
+        const double ce = L.off ? L.off[e] : 0.0;
         if (WRT == LAY_T) {
-            // top to bottom: sfx = sum of the interface cotangents above the ply's own thickness, d z_i / d t_j = -1/2 + [j < i]
+            // top to bottom: sfx = sum of the interface cotangents above the ply's own thickness, d z_i / d t_j = [j < i] - (1/2 - r)
             double cs = H, sfx = 0.0;
             for (int k = L.nply - 1; k >= 0; --k) {
                 const double* pc = L.pc + k * LAY_PC;
                 const double tk = L.t[k * nel + e];
                 LayPly P;
                 lay_ply(pc, L.th[k * nel + e], P);
-                const double z1 = cs - 0.5 * H;
+                const double z1 = lay_z(L, cs, H, ce);
                 cs -= tk;
-                const double z0 = (k == 0 ? 0.0 : cs) - 0.5 * H;
+                const double z0 = lay_z(L, k == 0 ? 0.0 : cs, H, ce);
                 double a = 0.0, b = 0.0, d = 0.0;
 #pragma unroll
                 for (int i = 0; i < 6; ++i) { a += Ab[i] * P.Qb[i]; b += Bb[i] * P.Qb[i]; d += Db[i] * P.Qb[i]; }
@@ -383,9 +396,9 @@ k_layup_vjp(LayupDev L, const double* __restrict__ lbar, const double* __restric
                 g[k] = sfx + K_SHEAR * s;
                 sfx += lo;
             }
-            for (int k = 0; k < L.nply; ++k) g[k] -= 0.5 * sfx;       // sfx: the sum over every interface
+            for (int k = 0; k < L.nply; ++k) g[k] -= L.zr * sfx;      // sfx: the sum over every interface
         } else {
-            double cs = 0.0, z0 = -0.5 * H;
+            double cs = 0.0, z0 = lay_z(L, 0.0, H, ce);
             int p = 0;
             for (int k = 0; k < L.nply; ++k) {
                 const double* pc = L.pc + k * LAY_PC;
@@ -395,7 +408,7 @@ k_layup_vjp(LayupDev L, const double* __restrict__ lbar, const double* __restric
                 double dG[3][3], dQb[6], dQs[3];
                 lay_dply(pc, P, dG, dQb, dQs);
                 cs += tk;
-                const double z1 = cs - 0.5 * H;
+                const double z1 = lay_z(L, cs, H, ce);
                 double a = 0.0, b = 0.0, d = 0.0;
 #pragma unroll
                 for (int i = 0; i < 6; ++i) { a += Ab[i] * dQb[i]; b += Bb[i] * dQb[i]; d += Db[i] * dQb[i]; }

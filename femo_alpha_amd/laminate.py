@@ -8,14 +8,17 @@ the C ABI.
 Conventions (include/femo_hip.h, femo_set_laminate):
   * Voigt strains eps = (e00, e11, 2 e01), kappa = (k00, k11, 2 k01), gamma = (g0, g1) in the local frame of every point:
     laminate axis 1 lies along E0, from vertex 0 toward vertex 1 of the cell.
-  * Plies are listed bottom to top (z from -H/2 to H/2 along the cell normal); angles in degrees, measured from E0 toward E1.
+  * Plies are listed bottom to top (z from -H/2 to H/2 along the cell normal by default); angles in degrees, measured from E0 toward
+    E1.
   * ``A_s = K_SHEAR * sum_k Qs_k t_k`` with the project's shear correction 0.833, so one isotropic ply of thickness h gives the
     single-layer law: (h C, 0, h^3 / 12 C, 0.833 G h I).
   * The strain at height z above the reference surface is eps - z kappa (u(z) = u_mid - z E2 x theta, linear_shell_model.py:392-398),
     so B = -int z Qbar dz: a ply above the mid-surface contributes a negative B.
   * A reference-plane offset -- the mid-surface o above the reference surface (the reference's ``shl_offset``; its single layer on
     top of the reference surface, ``getSingleLayerCLT`` with BOT, is o = h / 2) -- is the transform A' = A, B' = B - o A,
-    D' = D - o (B + B^T) + o^2 A (``offset``).
+    D' = D - o (B + B^T) + o^2 A (``offset``).  ``clt_from_plies``, ``clt_dtheta`` and ``ply_table`` build about such a surface
+    directly (``reference``, ``offset``: o = r H + c, ``_interfaces``), with the thickness Jacobians of the shift included; the device
+    counterpart is femo_set_layup_reference.
 """
 from __future__ import annotations
 
@@ -67,17 +70,18 @@ def ply_stiffness(E1, E2, G12, nu12, G13, G23, theta):
     return Qbar, Qsbar
 
 
-def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacobian=False):
+def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacobian=False, reference="mid", offset=0.0):
     """Classical lamination theory.  Every argument is an array of shape (nply,) (one layup for all cells) or (nel, nply); plies bottom
     to top, ``theta`` in degrees from E0.  Returns (A, B, D, A_s) of shapes (nel, 3, 3) x 3 and (nel, 2, 2) (nel = 1 for a single
     layup); with ``jacobian=True`` also (dA, dB, dD, dA_s), the derivatives with respect to the ply thicknesses, shapes
-    (nel, nply, 3, 3) x 3 and (nel, nply, 2, 2) -- the chain from d/d laminate to d/d t."""
+    (nel, nply, 3, 3) x 3 and (nel, nply, 2, 2) -- the chain from d/d laminate to d/d t.
+    ``reference`` / ``offset``: the reference surface the laminate is built about (``_interfaces``); the default is the
+    mid-surface.  ``offset`` is data: the Jacobians differentiate the thickness-dependent part r H of the shift only."""
     args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, G13, G23, t, theta)]
     args = np.broadcast_arrays(*args)
     E1, E2, G12, nu12, G13, G23, t, theta = args
     Qb, Qs = ply_stiffness(E1, E2, G12, nu12, G13, G23, theta)          # (nel, nply, 3, 3), (nel, nply, 2, 2)
-    H = t.sum(axis=1, keepdims=True)
-    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H    # (nel, nply + 1) ply interfaces
+    z = _interfaces(t, reference, offset)                                             # (nel, nply + 1) ply interfaces
     z0, z1 = z[:, :-1], z[:, 1:]
     A = np.einsum("ek,ekij->eij", z1 - z0, Qb)
     # the strain at height z is eps - z kappa (u(z) = u_mid - z E2 x theta, linear_shell_model.py:392-398): B = -int z Qbar dz
@@ -87,7 +91,7 @@ def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacob
     if not jacobian:
         return A, B, D, As
     nply = t.shape[1]
-    dz = _dz_interfaces(nply)                                                                     # (nply + 1, nply) [i, j]
+    dz = _dz_interfaces(nply, reference)                                                          # (nply + 1, nply) [i, j]
     dz0, dz1 = dz[:-1], dz[1:]                                                                    # (nply, nply) [k, j]
     dA = np.einsum("kj,ekab->ejab", dz1 - dz0, Qb)
     dB = np.einsum("ek,kj,ekab->ejab", z0, dz0, Qb) - np.einsum("ek,kj,ekab->ejab", z1, dz1, Qb)
@@ -96,9 +100,39 @@ def clt_from_plies(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, jacob
     return (A, B, D, As), (dA, dB, dD, dAs)
 
 
-def _dz_interfaces(nply):
-    """dz_i / dt_j = -1/2 + [j < i] of the nply + 1 ply interfaces z_i = sum_{j < i} t_j - H / 2, (nply + 1, nply)."""
-    return -0.5 + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)
+REFERENCES = {"mid": 0.0, "bot": 0.5, "top": -0.5}
+
+
+def reference_position(reference):
+    """The number r of a reference surface: its position below the mid-surface in units of the cell's total thickness H.
+    "mid" = 0, "bot" = 1/2, "top" = -1/2, or any finite number."""
+    if isinstance(reference, str):
+        if reference not in REFERENCES:
+            raise ValueError(f"reference: 'mid', 'bot', 'top' or a number, got {reference!r}")
+        return REFERENCES[reference]
+    r = float(reference)
+    if not np.isfinite(r):
+        raise ValueError(f"reference: a finite number, got {reference!r}")
+    return r
+
+
+def _interfaces(t, reference="mid", offset=0.0):
+    """The nply + 1 ply interfaces z_i = sum_{j < i} t_j - (1/2 - r) H + c of the (nel, nply) thicknesses ``t`` about the reference
+    surface r = ``reference_position(reference)``, c = ``offset`` (a scalar or one length per cell), (nel, nply + 1).  The reference
+    surface lies o = r H + c below the mid-surface (the ``o`` of ``offset``): "bot" has z_0 = c, "top" z_nply = c.  c is added only
+    where it is given, so the default performs the operations of the mid-surface convention z_i = sum_{j < i} t_j - H / 2."""
+    H = t.sum(axis=1, keepdims=True)
+    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - (0.5 - reference_position(reference)) * H
+    c = np.asarray(offset, dtype=np.float64)
+    if c.ndim == 0 and c == 0.0:
+        return z
+    return z + (c.reshape(-1, 1) if c.ndim else c)
+
+
+def _dz_interfaces(nply, reference="mid", offset=0.0):
+    """dz_i / dt_j = [j < i] - (1/2 - r) of the nply + 1 ply interfaces of ``_interfaces``, (nply + 1, nply); ``offset`` is data and
+    does not enter."""
+    return -(0.5 - reference_position(reference)) + (np.arange(nply)[None, :] < np.arange(nply + 1)[:, None]).astype(np.float64)
 
 
 def _dt_eps(theta_deg):
@@ -129,15 +163,14 @@ def ply_stiffness_dtheta(E1, E2, G12, nu12, G13, G23, theta):
     return np.deg2rad(1.0) * dQb, np.deg2rad(1.0) * dQs
 
 
-def clt_dtheta(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR):
+def clt_dtheta(E1, E2, G12, nu12, G13, G23, t, theta, k_shear=K_SHEAR, reference="mid", offset=0.0):
     """(dA, dB, dD, dA_s): the derivatives of ``clt_from_plies`` with respect to the ply angles, per degree, shapes
     (nel, nply, 3, 3) x 3 and (nel, nply, 2, 2) -- entry [e, k] is the derivative with respect to the angle of ply k of cell e.
-    Arguments as for ``clt_from_plies``."""
+    Arguments as for ``clt_from_plies``, the reference surface included."""
     args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, G13, G23, t, theta)]
     E1, E2, G12, nu12, G13, G23, t, theta = np.broadcast_arrays(*args)
     dQb, dQs = ply_stiffness_dtheta(E1, E2, G12, nu12, G13, G23, theta)
-    H = t.sum(axis=1, keepdims=True)
-    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H
+    z = _interfaces(t, reference, offset)
     z0, z1 = z[:, :-1], z[:, 1:]
     w = lambda x: x[:, :, None, None]
     return w(z1 - z0) * dQb, -0.5 * w(z1 ** 2 - z0 ** 2) * dQb, w(z1 ** 3 - z0 ** 3) * dQb / 3.0, k_shear * w(t) * dQs
@@ -162,23 +195,22 @@ def tsai_wu(Xt, Xc, Yt, Yc, S, f12=-0.5):
     return np.stack([1.0 / Xt - 1.0 / Xc, 1.0 / Yt - 1.0 / Yc, F11, F22, 1.0 / S ** 2, f12 * np.sqrt(F11 * F22)], axis=-1)
 
 
-def ply_table(E1, E2, G12, nu12, t, theta, strengths, surfaces=("bot", "top"), jacobian=False):
+def ply_table(E1, E2, G12, nu12, t, theta, strengths, surfaces=("bot", "top"), jacobian=False, reference="mid", offset=0.0):
     """Recovery points of the ply failure outputs (femo_set_ply_table): (nel, npt, 16) with npt = nply * len(surfaces), per point
     [G (3x3 row-major), z, F1, F2, F11, F22, F66, F12].  Ply arguments as for ``clt_from_plies``: (nply,) or (nel, nply), plies bottom
     to top, z from -H/2; ``strengths``: the coefficients of ``tsai_wu``, (6,), (nply, 6) or (nel, nply, 6).  Point order: ply by ply
     from the bottom, inside a ply the ``surfaces`` as listed ("bot", "mid", "top" of the ply).  G = Q T(theta) maps the frame strains
     eps - z kappa to the ply-axis stresses (Q: the reduced stiffness in ply axes, T: ``_t_eps``).
     ``jacobian=True`` also returns dz (npt, nply) = d z_p / d t_j, the same for every cell: z is the only entry of the table that
-    depends on the ply thicknesses."""
+    depends on the ply thicknesses.  ``reference`` / ``offset``: the reference surface z is measured from (``_interfaces``)."""
     args = [np.atleast_2d(np.asarray(x, dtype=np.float64)) for x in (E1, E2, G12, nu12, t, theta)]
     E1, E2, G12, nu12, t, theta = np.broadcast_arrays(*args)
     nel, nply = t.shape
     Q, _ = ply_stiffness(E1, E2, G12, nu12, G12, G12, np.zeros_like(theta))         # theta = 0: Q in ply axes
     G = np.einsum("ekil,eklj->ekij", Q, _t_eps(theta))
     F = np.broadcast_to(np.asarray(strengths, dtype=np.float64), (nel, nply, 6))
-    H = t.sum(axis=1, keepdims=True)
-    z = np.concatenate([np.zeros_like(H), np.cumsum(t, axis=1)], axis=1) - 0.5 * H    # (nel, nply + 1) ply interfaces
-    dzi = _dz_interfaces(nply)
+    z = _interfaces(t, reference, offset)                                             # (nel, nply + 1) ply interfaces
+    dzi = _dz_interfaces(nply, reference)
     pick = {"bot": (1.0, 0.0), "mid": (0.5, 0.5), "top": (0.0, 1.0)}
     ns = len(surfaces)
     out = np.empty((nel, nply, ns, PLY_W))

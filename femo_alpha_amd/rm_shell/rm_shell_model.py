@@ -113,6 +113,8 @@ class RMShellModel:
         # laminate= and ply_table= arguments of evaluate and of ply_failure=npt here.  The outputs "layup_volume" and, with the (nply,)
         # ply densities density=[...], "layup_mass" are functions of "ply_thickness" and "uhat" alone.  With the (nply, 2) transverse
         # shear strengths shear_strength=[[S13, S23], ...] the output "ply_shear_failure" exists, with the arguments of "ply_failure".
+        # reference="mid" | "bot" | "top" | r and offset (a length, or (nel,) in caller cell order) choose the reference surface the mesh
+        # stands for (ShellContext.set_layup_reference); the default is the mid-surface.
         self.layup = None
         if layup is not None:
             if not self.laminate or self.ply_failure is not None:
@@ -121,6 +123,9 @@ class RMShellModel:
             nply = t.shape[-1] if t.ndim else 1
             to_solver = lambda a: np.broadcast_to(a.reshape(-1, nply), (mesh.nel, nply))[self.cell_of_new]
             self.layup = dict(layup, t=to_solver(t), theta=to_solver(theta))
+            if layup.get("offset") is not None and np.ndim(layup["offset"]):
+                # the per-cell offsets of the reference surface arrive in caller cell order, as t and theta do
+                self.layup["offset"] = np.broadcast_to(np.asarray(layup["offset"], dtype=np.float64).ravel(), (mesh.nel,))[self.cell_of_new]
             self.nply = nply
         # max_disp=dict(...) or a list of up to four: one max-displacement output per dict (RMShellPDE.max_disp) with the keys rho,
         # scaler, direction, nodes, name (default "max_disp", "max_disp1", ...) and tag (a key of mesh_tags; none: the whole mesh).  The

@@ -48,7 +48,7 @@ class RMShellPDE:
         # one-ply placeholder (1 mm of a unit-modulus isotropic ply) that the model's "laminate" input replaces.
         self.laminate = bool(laminate)
         self.VL = None
-        # layup=dict(plies, t, theta[, surfaces, c_drill, density, shear_strength]) (laminate mode; ShellContext.set_layup, solver cell order): the
+        # layup=dict(plies, t, theta[, surfaces, c_drill, density, shear_strength, reference, offset]) (laminate mode; ShellContext.set_layup, solver cell order): the
         # laminate and the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the
         # recovery points, hence "ply_failure", follow from the layup's surfaces, "layup_mass" from its (nply,) ply densities, and
         # "ply_shear_failure" from its (nply, 2) transverse shear strengths [S13, S23]
@@ -61,7 +61,8 @@ class RMShellPDE:
             nply = t.shape[-1] if t.ndim else 1
             surfaces = tuple(layup.get("surfaces", ("bot", "top")))
             self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"), density=layup.get("density"),
-                               shear_strength=layup.get("shear_strength"))
+                               shear_strength=layup.get("shear_strength"), reference=layup.get("reference"),
+                               offset=layup.get("offset"))
             self.layup_density = layup.get("density") is not None
             self.layup_shear = layup.get("shear_strength") is not None
             self.VY = FunctionSpace(self.ctx, "VY", width=nply)

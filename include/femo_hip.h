@@ -207,7 +207,8 @@ int femo_set_layup_shear_strength(femo_ctx* ctx, int32_t nply, const double* S);
  * (femo_alpha_amd/csrc/layup.h) -- new; the conventions are those of femo_alpha_amd/laminate.py (clt_from_plies, ply_table):
  *   - nply plies (1..32), listed bottom to top along the cell normal, the same materials in every cell: plies is nply x 12,
  *     [E1, E2, G12, nu12, G13, G23, F1, F2, F11, F22, F66, F12] (F*: the Tsai-Wu coefficients of laminate.tsai_wu);
- *   - t and theta: nel x nply, cell-major; interfaces z_i = sum_{j<i} t_j - H / 2; angles in degrees from E0 toward E1;
+ *   - t and theta: nel x nply, cell-major; interfaces z_i = sum_{j<i} t_j - H / 2 about the mid-surface, the default reference surface
+ *     (femo_set_layup_reference below chooses another); angles in degrees from E0 toward E1;
  *   - A = sum (z1 - z0) Qbar, B = -1/2 sum (z1^2 - z0^2) Qbar, D = 1/3 sum (z1^3 - z0^3) Qbar, A_s = 0.833 sum t Qsbar, and
  *     c_drill (> 0), a constant of the mode that every derivative holds fixed;
  *   - surfaces: a mask of 1 (bot), 2 (mid), 4 (top) of every ply; the recovery points run ply by ply from the bottom, inside a ply in
@@ -250,6 +251,25 @@ int femo_set_layup_shear_strength(femo_ctx* ctx, int32_t nply, const double* S);
  *     (femo_total_jvp: unless dW is asked for), and in a grouped call their columns stay out of the grouped sweeps;
  *   - the value and the thickness gradient use no atomics and fixed summation orders: two identical calls return the same bits.  The
  *     shape derivative accumulates on the vertices with the atomics of the other outputs' shape derivatives.
+ * The reference surface of the layup (femo_set_layup_reference) -- new: the surface the mesh stands for, and about which the laminate
+ * and the z of the table are built.  It is given by a number r, its position below the mid-surface in units of the cell's total
+ * thickness H_e (0: the mid-surface, 1/2: the bottom, -1/2: the top; any finite value), and an optional length c_e per cell:
+ *     o_e = r H_e + c_e                               how far the reference surface lies below the mid-surface
+ *     z_i = sum_{j<i} t_j - (1/2 - r) H_e + c_e       bottom: z_0 = c_e, top: z_nply = c_e
+ *     d z_i / d t_j = [j < i] - (1/2 - r)             c_e is data, not an argument
+ *   - A, B, D and column 9 of the table follow from these z_i as above; A, A_s, G, the strength coefficients, the shear table,
+ *     "layup_mass" and "layup_volume" do not see the reference surface.  A symmetric stack about its bottom or top has B != 0.  One
+ *     isotropic ply about its bottom gives A = h C, B = -h^2 / 2 C, D = h^3 / 3 C, the reference's single layer with BOT;
+ *   - offset: n == nel values, n == 1 (the same in every cell), or NULL / 0 (none).  A layup must be active, r and every offset finite
+ *     (the error names the first offending cell; a length error names both lengths).  A refused call changes nothing;
+ *   - an accepted call rebuilds the laminate and the table and counts as a change of the operator, as a new "ply_thickness" does: the
+ *     next solve re-factorises.  c_drill is a constant of the mode and stays;
+ *   - the reference surface belongs to the mode, not to the plies: femo_set_field of "ply_thickness" / "ply_angle" and a further
+ *     femo_set_layup, of any ply count, keep it; leaving the mode (either way below) returns to the mid-surface;
+ *   - femo_layup_jvp / femo_layup_vjp and every derivative entry point that reaches the layup differentiate about the chosen surface,
+ *     for both arguments; r = 0 without offsets performs the operations of the mid-surface convention, bit for bit;
+ *   - femo_get_layup_reference: r, and the nel offsets (zeros where none were given); either pointer may be NULL;
+ *   - not provided: the offset as a differentiable argument, and a reference surface outside the layup mode.
  * femo_set_layup(ctx, 0, NULL, 0, 0, NULL, NULL) leaves the mode and keeps the last laminate and table as ordinary values;
  * femo_set_laminate(ctx, NULL, 0) drops the layup together with the laminate.
  * femo_layup_jvp: ndir directions V (ndir x n, n = nel nply) -> dlaminate (ndir x 32 nel) and dtable (ndir x 16 npt nel); either may be
@@ -257,6 +277,8 @@ int femo_set_layup_shear_strength(femo_ctx* ctx, int32_t nply, const double* S);
  * calls return the same bits. */
 int femo_set_layup(femo_ctx* ctx, int32_t nply, const double* plies, int32_t surfaces, double c_drill, const double* t, const double* theta);
 int femo_set_layup_density(femo_ctx* ctx, int32_t nply, const double* rho);
+int femo_set_layup_reference(femo_ctx* ctx, double r, const double* offset, int64_t n);
+int femo_get_layup_reference(femo_ctx* ctx, double* r, double* offset, int64_t n);
 int femo_layup_jvp(femo_ctx* ctx, const char* wrt, int32_t ndir, const double* V, int64_t n, double* dlaminate, double* dtable);
 int femo_layup_vjp(femo_ctx* ctx, const char* wrt, const double* laminate_bar, const double* table_bar, double* out, int64_t n);
 
