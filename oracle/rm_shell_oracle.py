@@ -196,6 +196,41 @@ def _unit(v):
     return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
 
+# _ABSOLUTE: the keyword ``absolute`` of load_vector, dcompliance_du, dcompliance_dh, dRdfield_T and dRdf_T.  With absolute=True the
+# method applies np.abs to every operand of its einsums (B, dC, the shape-function tables, the measure, lam_e, w_e, f, h) and returns the
+# sum of the absolute values of the terms it otherwise adds with their signs: the scale an error of that sum is relative to
+# (tests/parity_metrics.py: term_scaled).  With absolute=False the operands pass through unchanged.
+def _same(v):
+    return v
+
+
+def _det(A):
+    """np.linalg.det; stacks of 3 x 3 in numpy.longdouble, which LAPACK does not take, by cofactors."""
+    if A.dtype != np.longdouble:
+        return np.linalg.det(A)
+    return (A[..., 0, 0] * (A[..., 1, 1] * A[..., 2, 2] - A[..., 1, 2] * A[..., 2, 1])
+            - A[..., 0, 1] * (A[..., 1, 0] * A[..., 2, 2] - A[..., 1, 2] * A[..., 2, 0])
+            + A[..., 0, 2] * (A[..., 1, 0] * A[..., 2, 1] - A[..., 1, 1] * A[..., 2, 0]))
+
+
+def _inv(A):
+    """np.linalg.inv; stacks of 2 x 2 and 3 x 3 in numpy.longdouble by the adjugate."""
+    if A.dtype != np.longdouble:
+        return np.linalg.inv(A)
+    out = np.empty_like(A)
+    if A.shape[-1] == 2:
+        d = A[..., 0, 0] * A[..., 1, 1] - A[..., 0, 1] * A[..., 1, 0]
+        out[..., 0, 0], out[..., 1, 1], out[..., 0, 1], out[..., 1, 0] = A[..., 1, 1] / d, A[..., 0, 0] / d, -A[..., 0, 1] / d, -A[..., 1, 0] / d
+        return out
+    d = _det(A)
+    for i in range(3):
+        for j in range(3):
+            r, c = [k for k in range(3) if k != j], [k for k in range(3) if k != i]      # cofactor (j, i)
+            minor = A[..., r[0], c[0]] * A[..., r[1], c[1]] - A[..., r[0], c[1]] * A[..., r[1], c[0]]
+            out[..., i, j] = (-1) ** (i + j) * minor / d
+    return out
+
+
 class ShellOracle:
     """Float64 CPU restatement of the reference shell path on a ``ShellMesh``-like object
     (attributes nodes, cells, cell_p2, nV, nP2, ndof, ndof_u, is_quad)."""
@@ -230,6 +265,9 @@ class ShellOracle:
         # defaults follow FEA.add_input init values, rm_shell_model.py:209-214
         self.h = np.full(nT, 1e-3); self.E = np.ones(nT); self.nu = np.ones(nT) * 0.3
         self.rho = np.ones(nT); self.f = np.ones((nF, 3)); self.uhat = np.zeros((mesh.nn, 3))
+        # dtype of the arrays the methods fill (B, C, the global accumulators).  tests/rowscaled_cases.py raises it to numpy.longdouble on a
+        # copy whose nodes, fields and inputs are cast to longdouble as well: the same formulas evaluated in extended precision
+        self.acc = np.float64
 
     def _set_rule(self, nquad, rule=None, nred=0):
         """Quadrature rule and shape tables: ``nquad`` x ``nquad`` Gauss points on quadrilaterals, the symmetric rule of DEGREE ``nquad``
@@ -300,9 +338,9 @@ class ShellOracle:
         E0 = _unit(Jg[..., 0])
         E1 = _cross(E2, E0)
         G = np.einsum("eqik,eqil->eqkl", Jg, Jg)
-        Kinv = np.einsum("eqkl,eqil->eqki", np.linalg.inv(G), Jg)     # (ne,nq,2,3) pseudo-inverse
+        Kinv = np.einsum("eqkl,eqil->eqki", _inv(G), Jg)                  # (ne,nq,2,3) pseudo-inverse
         # derivative of the unit normal along x_j (non-zero only on warped quads)
-        W = np.zeros(Jg.shape[:2] + (3, 3))
+        W = np.zeros(Jg.shape[:2] + (3, 3), dtype=self.acc)
         if self.mesh.is_quad:
             c = 0.25 * (X[:, 0] - X[:, 1] + X[:, 2] - X[:, 3])         # d2x / dxi deta
             c = np.broadcast_to(c[:, None, :], a.shape)
@@ -314,8 +352,8 @@ class ShellOracle:
         gradM = np.einsum("eqki,qbk->eqbi", Kinv, dN1)                 # (ne,nq,nvc,3) surface gradient of M_b
         Gu = np.einsum("ebi,eqbj->eqij", U, gradM)
         F = np.eye(3) + Gu
-        Finv = np.linalg.inv(F)
-        Ju = np.linalg.det(F)
+        Finv = _inv(F)
+        Ju = _det(F)
         return dict(X=X, Jg=Jg, det=det, E0=E0, E1=E1, E2=E2, Kinv=Kinv, W=W, Finv=Finv, Ju=Ju,
                     gradM=gradM, F=F)
 
@@ -333,7 +371,7 @@ class ShellOracle:
         m = np.stack([np.einsum("eqj,eqbj->eqb", E0, gxM), np.einsum("eqj,eqbj->eqb", E1, gxM)], axis=-1)
         Wp = np.einsum("eqik,eqkj->eqij", g["W"], Finv)
         wl = [np.einsum("eqj,eqij->eqi", E0, Wp), np.einsum("eqj,eqij->eqi", E1, Wp)]   # w_J
-        B = np.zeros((ne, nq, 9, self.ldof))
+        B = np.zeros((ne, nq, 9, self.ldof), dtype=self.acc)
         Bu = B[..., : 3 * npc].reshape(ne, nq, 9, npc, 3)
         Bt = B[..., 3 * npc:].reshape(ne, nq, 9, nvc, 3)
         e0, e1, e2 = E0[:, :, None, :], E1[:, :, None, :], E2[:, :, None, :]
@@ -397,7 +435,7 @@ class ShellOracle:
             cd = zero
         else:
             raise ValueError(deriv)
-        C = np.zeros(wdet.shape + (9, 9))
+        C = np.zeros(wdet.shape + (9, 9), dtype=self.acc)
         C[..., 0:3, 0:3] = Cm * wdetS[..., None, None]         # membrane: no J(uhat)  (:278-279)
         C[..., 3:6, 3:6] = Cb * wdetS[..., None, None]         # bending : no J(uhat)  (:281-282)
         sw = cs * Ju * wdetS
@@ -537,20 +575,22 @@ class ShellOracle:
         """Prescribed state g of the penalty term beta/h_E |..| (w - g).v (linear_shell_model.py:323-333); None = zero."""
         self.g_dirichlet = None if g is None else np.asarray(g, dtype=np.float64).copy()
 
-    def load_vector(self):
-        """F_a = int f . N_a J dx (linear_shell_model.py:320), plus P g when the penalty term carries prescribed values."""
-        Fv = np.zeros(self.mesh.ndof)
+    def load_vector(self, absolute=False):
+        """F_a = int f . N_a J dx (linear_shell_model.py:320), plus P g when the penalty term carries prescribed values.
+        ``absolute``: the same sum with every term replaced by its absolute value (_ABSOLUTE)."""
+        a = np.abs if absolute else _same
+        Fv = np.zeros(self.mesh.ndof, dtype=self.acc)
         if getattr(self, "g_dirichlet", None) is not None:
             for d, blk in self._penalty_blocks():
-                Fv[d] += blk @ self.g_dirichlet[d]
+                Fv[d] += a(blk) @ a(self.g_dirichlet[d])
         for sl in self._chunks():
             g = self._geometry(sl, self.N1, self.dN1)
-            wj = self.wts[None, :] * g["det"] * g["Ju"]
+            wj = a(self.wts[None, :] * g["det"] * g["Ju"])
             if self.ewp:
-                fq = np.repeat(self.f[sl][:, None, :], self.nq, axis=1)
+                fq = np.repeat(a(self.f[sl])[:, None, :], self.nq, axis=1)
             else:
-                fq = np.einsum("qb,ebc->eqc", self.N1, self.f[self.mesh.cells[sl]])
-            Fe = np.einsum("eq,qa,eqc->eac", wj, self.N2, fq).reshape(fq.shape[0], -1)
+                fq = np.einsum("qb,ebc->eqc", a(self.N1), a(self.f[self.mesh.cells[sl]]))
+            Fe = np.einsum("eq,qa,eqc->eac", wj, a(self.N2), fq).reshape(fq.shape[0], -1)
             np.add.at(Fv, self.dofs[sl][:, : 3 * self.npc].ravel(), Fe.ravel())
         if self.strong_dofs.size:
             Fv[self.strong_dofs] = 0.0
@@ -558,7 +598,7 @@ class ShellOracle:
 
     def apply_K(self, x, with_penalty=True):
         """y = K x element by element (no global matrix)."""
-        y = np.zeros(self.mesh.ndof)
+        y = np.zeros(self.mesh.ndof, dtype=self.acc)
         for sl in self._chunks():
             Ke = self.element_matrices(sl)
             ye = np.einsum("eij,ej->ei", Ke, x[self.dofs[sl]])
@@ -600,9 +640,10 @@ class ShellOracle:
         return lam
 
     # ------------------------------------------------------------------ outputs
-    def _u_at_qp(self, w, sl):
+    def _u_at_qp(self, w, sl, absolute=False):
+        a = np.abs if absolute else _same
         ue = w[self.dofs[sl][:, : 3 * self.npc]].reshape(-1, self.npc, 3)
-        return np.einsum("qa,eac->eqc", self.N2, ue)
+        return np.einsum("qa,eac->eqc", a(self.N2), a(ue))
 
     def regularization(self):
         val = 0.0
@@ -636,25 +677,27 @@ class ShellOracle:
     def elastic_energy(self, w):
         return 0.5 * float(w @ self.apply_K(w, with_penalty=False))
 
-    def dcompliance_du(self, w):
-        out = np.zeros(self.mesh.ndof)
+    def dcompliance_du(self, w, absolute=False):
+        a = np.abs if absolute else _same
+        out = np.zeros(self.mesh.ndof, dtype=self.acc)
         for sl in self._chunks():
             g = self._geometry(sl, self.N1, self.dN1)
-            u = self._u_at_qp(w, sl)
-            ge = 2.0 * np.einsum("eq,qa,eqc->eac", self.wts[None, :] * g["det"] * g["Ju"], self.N2, u)
+            u = self._u_at_qp(w, sl, absolute)
+            ge = 2.0 * np.einsum("eq,qa,eqc->eac", a(self.wts[None, :] * g["det"] * g["Ju"]), a(self.N2), u)
             np.add.at(out, self.dofs[sl][:, : 3 * self.npc].ravel(), ge.ravel())
         return out
 
-    def dcompliance_dh(self, w=None):
-        out = np.zeros(self.h.size)
+    def dcompliance_dh(self, w=None, absolute=False):
+        a = np.abs if absolute else _same
+        out = np.zeros(self.h.size, dtype=self.acc)
         for sl in self._chunks():
             g = self._geometry(sl, self.N1, self.dN1)
-            wd = self.wts[None, :] * g["det"]
+            wd = a(self.wts[None, :] * g["det"])
             if self.ewm:
-                out[sl] += REG_ALPHA1 * self.h[sl] * wd.sum(axis=1)
+                out[sl] += REG_ALPHA1 * a(self.h[sl]) * wd.sum(axis=1)
             else:
-                gh = np.einsum("eqbi,eb->eqi", g["gradM"], self.h[self.mesh.cells[sl]])
-                ge = REG_ALPHA1 * np.einsum("eq,eqbi,eqi->eb", wd, g["gradM"], gh)
+                gh = np.einsum("eqbi,eb->eqi", a(g["gradM"]), a(self.h[self.mesh.cells[sl]]))
+                ge = REG_ALPHA1 * np.einsum("eq,eqbi,eqi->eb", wd, a(g["gradM"]), gh)
                 np.add.at(out, self.mesh.cells[sl].ravel(), ge.ravel())
         return out
 
@@ -748,35 +791,39 @@ class ShellOracle:
         return out
 
     # ------------------------------------------------------------------ (dR/d arg)^T lambda
-    def dRdfield_T(self, name, w, lam):
+    def dRdfield_T(self, name, w, lam, absolute=False):
         """(dR/d field)^T lam for field in {'h','E','nu'} -- what
-        ``computeMatVecProductBwd(dRdf, lambda)`` returns (state_operation.py:180-184)."""
-        out = np.zeros(self.h.size)
+        ``computeMatVecProductBwd(dRdf, lambda)`` returns (state_operation.py:180-184).
+        ``absolute``: the same sum with every term replaced by its absolute value (_ABSOLUTE)."""
+        a = np.abs if absolute else _same
+        out = np.zeros(self.h.size, dtype=self.acc)
         for sl in self._chunks():
             B, g = self._B(sl)
-            dC = self._C(sl, g, deriv=name)
-            sw = np.einsum("eqij,ej->eqi", B, w[self.dofs[sl]])
-            sl_ = np.einsum("eqij,ej->eqi", B, lam[self.dofs[sl]])
+            B = a(B)
+            dC = a(self._C(sl, g, deriv=name))
+            sw = np.einsum("eqij,ej->eqi", B, a(w[self.dofs[sl]]))
+            sl_ = np.einsum("eqij,ej->eqi", B, a(lam[self.dofs[sl]]))
             dens = np.einsum("eqi,eqij,eqj->eq", sl_, dC, sw)
             if self.ewm:
                 out[sl] += dens.sum(axis=1)
             else:
-                np.add.at(out, self.mesh.cells[sl].ravel(), np.einsum("eq,qb->eb", dens, self.N1).ravel())
+                np.add.at(out, self.mesh.cells[sl].ravel(), np.einsum("eq,qb->eb", dens, a(self.N1)).ravel())
         return out
 
-    def dRdf_T(self, lam):
-        """(dR/df)^T lam = - int M_b (lam_u) J dx, node-major xyz like ``F_solid``."""
-        out = np.zeros_like(self.f)
+    def dRdf_T(self, lam, absolute=False):
+        """(dR/df)^T lam = - int M_b (lam_u) J dx, node-major xyz like ``F_solid``.  ``absolute``: + int |M_b| |lam_u| |J| dx."""
+        a = np.abs if absolute else _same
+        out = np.zeros(self.f.shape, dtype=self.acc)
         for sl in self._chunks():
             g = self._geometry(sl, self.N1, self.dN1)
-            wj = self.wts[None, :] * g["det"] * g["Ju"]
-            lu = self._u_at_qp(lam, sl)
+            wj = a(self.wts[None, :] * g["det"] * g["Ju"])
+            lu = self._u_at_qp(lam, sl, absolute)
             if self.ewp:
                 out[sl] -= np.einsum("eq,eqc->ec", wj, lu)
             else:
-                ge = -np.einsum("eq,qb,eqc->ebc", wj, self.N1, lu)
+                ge = -np.einsum("eq,qb,eqc->ebc", wj, a(self.N1), lu)
                 np.add.at(out, self.mesh.cells[sl].ravel(), ge.reshape(-1, 3))
-        return out.ravel()
+        return (-out if absolute else out).ravel()
 
     # ------------------------------------------------------------------ the parity triple
     def forward_adjoint(self):

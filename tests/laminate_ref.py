@@ -28,7 +28,7 @@ class LaminateOracle(ShellOracle):
         wdetS = self.wts_strain[None, :] * g["det"]
         Ju = g["Ju"]
         hK2 = self.hK[sl] ** 2
-        C = np.zeros(wdet.shape + (9, 9))
+        C = np.zeros(wdet.shape + (9, 9), dtype=self.acc)
         C[..., 0:3, 0:3] = A[:, None] * wdetS[..., None, None]
         C[..., 0:3, 3:6] = B[:, None] * wdetS[..., None, None]
         C[..., 3:6, 0:3] = B[:, None] * wdetS[..., None, None]
@@ -37,17 +37,20 @@ class LaminateOracle(ShellOracle):
         C[..., 8, 8] = (cd / hK2)[:, None] * Ju * wdet
         return C
 
-    def dRdlam_T(self, w, lam):
-        """(nel, 32): lam^T (dK / d laminate_e[k]) w, with the law acting through the symmetric parts."""
-        out = np.zeros((self.mesh.nel, 32))
+    def dRdlam_T(self, w, lam, absolute=False):
+        """(nel, 32): lam^T (dK / d laminate_e[k]) w, with the law acting through the symmetric parts.
+        ``absolute``: the same sums with every term replaced by its absolute value (oracle/rm_shell_oracle.py: _ABSOLUTE)."""
+        a = np.abs if absolute else (lambda v: v)
+        out = np.zeros((self.mesh.nel, 32), dtype=self.acc)
         d = self.dofs
         for sl in self._chunks():
             B, g = self._B(sl)
-            sw = np.einsum("eqik,ek->eqi", B, w[d[sl]])
-            sl_ = np.einsum("eqik,ek->eqi", B, lam[d[sl]])
-            wdet = self.wts[None, :] * g["det"]
-            wdetS = self.wts_strain[None, :] * g["det"]
-            Ju = g["Ju"]
+            B = a(B)
+            sw = np.einsum("eqik,ek->eqi", B, a(w[d[sl]]))
+            sl_ = np.einsum("eqik,ek->eqi", B, a(lam[d[sl]]))
+            wdet = a(self.wts[None, :] * g["det"])
+            wdetS = a(self.wts_strain[None, :] * g["det"])
+            Ju = a(g["Ju"])
 
             def outer(a, b, wt):                      # sum_q wt 1/2 (a_i b_j + a_j b_i)
                 o = np.einsum("eq,eqi,eqj->eij", wt, a, b)

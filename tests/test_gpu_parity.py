@@ -47,10 +47,13 @@ def _marker(kind):
     return CLAMP if kind.startswith("plate") or kind == "tee" else (lambda x: np.less(x[1], 1e-12))
 
 
-def _pair(kind, ewm=False, ewp=False, uhat=False, bc="penalty", beta=1e15, seed=0):
-    from femo_alpha_amd.backend import ShellContext
+def _pair(kind, ewm=False, ewp=False, uhat=False, bc="penalty", beta=1e15, seed=0, element=None, device=True):
+    """``element``: the mesh of ``kind`` with that ShellElement in place of CG2CG1.  ``device=False``: the oracle alone (no context is
+    created, ``c`` is None): what the CPU tests of the reference's own rounding floor build their cases with."""
     from oracle.rm_shell_oracle import ShellOracle, degree4_rule
     m = _mesh(kind)
+    if element is not None:
+        m = ShellMesh(m.nodes, m.cells, element)
     rng = np.random.default_rng(seed)
     nT = m.nel if ewm else m.nn
     nF = m.nel if ewp else m.nn
@@ -65,6 +68,9 @@ def _pair(kind, ewm=False, ewp=False, uhat=False, bc="penalty", beta=1e15, seed=
     o = ShellOracle(m, element_wise_material=ewm, elementwise_pressure=ewp, penalty_facets=pf, strong_dofs=sd, beta=beta)
     o.set_fields(h=fields["thickness"], E=fields["E"], nu=fields["nu"], rho=fields["density"], f=fields["F_solid"],
                  uhat=fields.get("uhat"))
+    if not device:
+        return m, o, None, rng
+    from femo_alpha_amd.backend import ShellContext
     c = ShellContext(m, element_wise_material=ewm, elementwise_pressure=ewp)
     for k, v in fields.items():
         c.set_field(k, v)
