@@ -101,7 +101,7 @@ SYM_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-fopenmp"]
 
 def symbolic_digest() -> str:
     h = hashlib.sha256(" ".join(SYM_FLAGS).encode())
-    for d in (os.path.join(CSRC, "symbolic.cpp"), os.path.join(INCLUDE, "femo_symbolic.h")):
+    for d in (os.path.join(CSRC, "symbolic.cpp"), os.path.join(CSRC, "child_maps.h"), os.path.join(INCLUDE, "femo_symbolic.h")):
         h.update(os.path.basename(d).encode())
         with open(d, "rb") as fh:
             h.update(fh.read())

@@ -91,7 +91,7 @@ class ShellContext:
     def set_option(self, key, value):
         """Schedule switches and failure policy of this context (femo_set_option; include/femo_hip.h documents every name and its
         default).  Failure policy: 'strict', 'allow_pivot_repair'.  Factorisation schedule: 'trailing', 'left_min', 'left_max',
-        'super_panel', 'super_panel_cnt', 'lookahead', 'lookahead_cnt', 'fused_schur', 'fuse_rows', 'fuse_rows_cnt', 'fuse_rows_np',
+        'super_panel', 'super_panel_cnt', 'lookahead', 'lookahead_cnt', 'fused_schur', 'gather_mono', 'fuse_rows', 'fuse_rows_cnt', 'fuse_rows_np',
         'rows_fine_wg', 'narrow_fine_wg', 'diag_v1', 'diag_v1_cnt', 'xinv_small_cnt', 'grid_chunk',
         'assemble_fc', 'precond_nquad', 'equilibrate'.  Sweeps and solves: 'sweep_graph', 'sweep_ahead', 'sweep_w', 'sweep_butterfly',
         'bnd_tiled_nb', 'multi_rhs', 'apply_lanes', 'stale_factor', 'stale_rel'.  Before the frontal plan is set: 'wide_np', 'wide_cnt',

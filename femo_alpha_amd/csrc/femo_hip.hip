@@ -19,6 +19,7 @@
 #include "disp_aggregate.h"
 #include "csr_map.h"
 #include "hip_handles.h"
+#include "child_maps.h"
 
 #include <hip/hip_runtime.h>
 
@@ -232,6 +233,9 @@ struct femo_ctx {
         int sweep_graph = 0;                        // the preconditioner application of the PCG loop replayed as a HIP graph
         int diag_v1_cnt = 512;                      // levels of at least this many fronts: k_diag_block (80 KB of LDS, two workgroups per CU)
         int fused_schur = 1;          // left-looking levels: the Schur update gathers its block from the children
+        // the gathers of the extend-add (k_extend_gather, k_trailing_mfma<true>, k_trailing_fine<true>) address a front whose two children
+        // have increasing row maps per column (gather_mono_prepare / gather_mono_fetch, frontal.h); 0: the general gather on every front.  Same factor, bit for bit
+        int gather_mono = 1;
         // Experiment: factorise D K D with D = diag(K)^-1/2 (1) or its nearest powers of two (2) and apply
         // D (L L^T)^-1 D.  Measured: no change in what one application of the factor leaves -- every operation of
         // a Cholesky factorisation and of the sweeps commutes with a power-of-two scaling, so mode 2 reproduces mode 0 bit for bit
@@ -305,6 +309,7 @@ struct femo_ctx {
         std::vector<int> h_nf, h_npiv, h_level_off, h_level_nodes, h_level_maxnp, h_level_maxnb;
         std::vector<char> h_level_wide;              // level takes the wide solve kernels (and keeps S in Sinv)
         DevBuf<int> nf, npiv, dofs, upmap, parent, left, right, level_nodes, elem_front, elem_map, info, cinv0, cinv1;
+        DevBuf<int> cmono;                    // [2 ntree]: the "increasing" flags of the fronts' children (child_maps.h), then as many zeros (option "gather_mono" 0)
         DevBuf<long long> poff, soff, doff, linvoff, xoff;
         DevBuf<double> P, S, Linv, X, Xtmp, Swork;
         DevBuf<int> fel_off, fel;                    // elements of every level-0 front, by position in the level (front-centric assembly)
@@ -829,6 +834,7 @@ static FrontDev front_dev(const femo_ctx* c) {
     fd.dofs = c->fr.dofs; fd.upmap = c->fr.upmap; fd.parent = c->fr.parent; fd.child[0] = c->fr.left; fd.child[1] = c->fr.right;
     fd.linvoff = c->fr.linvoff; fd.xoff = c->fr.xoff; fd.P = c->fr.P; fd.S = c->fr.S; fd.Linv = c->fr.Linv; fd.X = c->fr.X; fd.Xtmp = c->fr.Xtmp;
     fd.cinv[0] = c->fr.cinv0; fd.cinv[1] = c->fr.cinv1;
+    fd.cmono = c->fr.cmono + (c->opt.gather_mono ? 0 : c->fr.ntree);
     return fd;
 }
 
@@ -3023,6 +3029,7 @@ int femo_set_option(femo_ctx* c, const char* key, double value) {
     else if (k == "fuse_rows_cnt") o.fuse_rows_cnt = v;
     else if (k == "fuse_rows_np") o.fuse_rows_np = v;
     else if (k == "fused_schur") o.fused_schur = v != 0;
+    else if (k == "gather_mono") o.gather_mono = v != 0;
     else if (k == "precond_nquad") { if (v != 0 && (v < 2 || v > 6)) return fail(c, "precond_nquad: 0 (the operator's rule) or 2..6"); o.precond_nquad = v; operator_changed(c); }
     else if (k == "equilibrate") { if (v < 0 || v > 2) return fail(c, "equilibrate: 0 off, 1 diag^-1/2, 2 nearest powers of two"); o.equilibrate = v; operator_changed(c); }
     else if (k == "grid_chunk") { if (v < 1 || v > 65535) return fail(c, "grid_chunk must be in 1..65535"); o.grid_chunk = v; }
@@ -4253,6 +4260,13 @@ int femo_set_frontal_plan(femo_ctx* c, int32_t ntree, int32_t nlevels, const int
             }
         }
         UPI(fr.cinv0, inv0.data(), ndofs_total); UPI(fr.cinv1, inv1.data(), ndofs_total);
+        // ... and whether each child's rows land in increasing order (then the gathers address the child per column): the flags,
+        // followed by a row of zeros for option "gather_mono" 0
+        std::vector<int32_t> mono(2 * (size_t)ntree, 0);
+        femo::child_maps_increasing(ntree, npiv, nf, dof_off, parent, left, right, up_map, mono.data());
+        for (int t = 0; t < ntree; ++t)              // gather_mono_fetch keeps byte offsets into a child's Schur block in 32 bits
+            if (parent[t] >= 0 && nf[t] - npiv[t] > (1 << 14)) mono[parent[t]] = 0;
+        UPI(fr.cmono, mono.data(), 2 * (size_t)ntree);
     }
     {
         // front-centric assembly: the elements of every level-0 front, by position in the level

@@ -42,6 +42,7 @@ struct FrontDev {
     const int* parent;
     const int* child[2];        // left / right
     const int* cinv[2];         // per front row: the row of the left / right child's front that lands there, or -1
+    const int* cmono;           // per front: bit 0 / 1 = the left / right child's rows land in increasing rows (child_maps.h); 0 = general gather
     const long long* linvoff;   // doubles, [ntree+1]
     const long long* xoff;      // doubles, [ntree+1]: where the front's X = L11^-1 starts (fronts of the wide levels)
     double* P;
@@ -414,6 +415,36 @@ k_extend_gather(FrontDev fd, const int* __restrict__ level_nodes, int first, con
     const int r = r0 + lr;
     const int ra0 = rmap[0][lr], ra1 = rmap[1][lr];
     double v[TS / 4];
+    if (fd.cmono[p] == 3) {
+        // Both children land in increasing rows (child_maps.h): for cc <= r the child rows are ordered as they stand, the entry is
+        // S_c[(row's - np_c) + nb_c (column's - np_c)].  A wave holds ONE column per k (lc0 is the wave's number), so the column term
+        // is scalar arithmetic on the child's base pointer and a thread adds one row offset, the same for all its 16 entries.
+        // Absent rows and columns are clamped to the first entry of the child's block and the value is zeroed afterwards: no select
+        // on an address, all loads in flight before the first use.  cc <= r needs testing only in the tiles on the diagonal.
+        const bool diag = ti == tj;
+        double g[2][TS / 4];
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+            const FrontView& fc = sd ? f1 : f0;
+            const int npc = fc.np, nbc = fc.nf - fc.np;
+            const int ra = sd ? ra1 : ra0;                        // -1 beyond the front and where the child is not there
+            const unsigned rowb = 8u * (unsigned)(max(ra, npc) - npc);
+            bool cok[TS / 4];
+#pragma unroll
+            for (int k = 0; k < TS / 4; ++k) {
+                const int lc = lc0 + 4 * k;
+                const int b = __builtin_amdgcn_readfirstlane(cmap[sd][lc]);
+                cok[k] = b >= 0 && c0 + lc < c_end;
+                const char* cb = reinterpret_cast<const char*>(fc.S + (size_t)nbc * (size_t)(max(b, npc) - npc));
+                g[sd][k] = *reinterpret_cast<const double*>(cb + rowb);
+            }
+#pragma unroll
+            for (int k = 0; k < TS / 4; ++k)
+                if (!(ra >= 0 && cok[k] && (!diag || c0 + lc0 + 4 * k <= r))) g[sd][k] = 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < TS / 4; ++k) v[k] = (0.0 + g[0][k]) + g[1][k];      // the sums of the general gather below, term by term
+    } else {
 #pragma unroll
     for (int k = 0; k < TS / 4; ++k) {
         const int lc = lc0 + 4 * k, cc = c0 + lc;
@@ -424,6 +455,7 @@ k_extend_gather(FrontDev fd, const int* __restrict__ level_nodes, int first, con
             if (ra1 >= 0 && b1 >= 0) x += f1.col(min(ra1, b1))[max(ra1, b1)];
         }
         v[k] = x;
+    }
     }
 #pragma unroll
     for (int k = 0; k < TS / 4; ++k) {
@@ -1340,6 +1372,159 @@ __device__ __host__ inline TrailRange trail_range(int schur, int C0, int K0, int
     return r;
 }
 
+// ---- the gather of the rank-k updates: what a lane's entries of a not yet existing tile are -- the sum of the entries of the two
+// children's Schur complements that land there.  The lane holds NR rows r[b] and NA x 4 columns cc[a][reg] of the front t (the D
+// layout of the MFMA blocks of its wave); the launch owns the columns [col_lo, col_hi).  Out: per entry g0 + g1, the left child's
+// entry plus the right child's, 0 where a child has none or the entry is not in the lower triangle (r < cc) or outside the front.
+// Child rows are boundary rows of the child (>= its pivot count npc), so an entry sits in the child's Schur block
+// S_c[(hi - npc) + nbc (lo - npc)], hi >= lo the child rows of the pair.
+
+// Both children land in increasing rows (FrontDev::cmono, child_maps.h): for r >= cc the child rows are ordered as they stand,
+// hi = the row's, lo = the column's.  The byte offset of an entry is then a term of the column alone (8 per lane and child) plus
+// one of the row alone (NR per lane and child), one 32-bit addition per entry on top of the child's uniform base pointer; whether
+// the entry exists is a row predicate AND a column predicate; r >= cc needs testing only in the tiles on the diagonal (DIAG).
+// Absent rows and columns are clamped to the first entry of the child's block, so that every address is a valid one, and the value
+// is zeroed afterwards.  All of it is integer arithmetic on purpose -- masks of all ones / all zeros made with shifts, applied with
+// AND / OR: a select on an address or on a loaded value makes the compiler branch around the load behind a full wait.
+// A block of at most 2^14 rows keeps the offsets inside 32 bits (femo_set_frontal_plan clears the flag beyond).
+// In two steps, so that a wave of k_trailing_mfma can finish one block row (a) of its tile -- 16 loads, sums, stores -- before it
+// fetches the next: all 32 entries of both children in flight beside the 32 accumulator registers do not fit 128 registers.
+// The maps are read once, for both block rows, before the first store.
+template <int NA, int NR>
+struct GatherMono {
+    const char* Sc[2];                 // the children's Schur blocks
+    unsigned colb[2][NA][4], rowb[2][NR];
+    // bit 4 a + reg of em[sd][b]: child sd has the entry (r[b], cc[a][reg]) -- a row that lands on the row AND one that lands on the
+    // column, inside the launch's columns and, on the diagonal tiles, r >= cc.  One register per (child, row), not one per entry
+    unsigned em[2][NR];
+};
+
+template <int NA, int NR, bool DIAG>
+__device__ __forceinline__ void gather_mono_prepare(const FrontDev& fd, int t, long long dp, int nf, int col_lo, int col_hi, const int (&r)[NR],
+                                                    const int (&cc)[NA][4], GatherMono<NA, NR>& gm) {
+    int outm[NA][4];                                               // -1: the column is outside the launch's [col_lo, col_hi)
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) outm[a][reg] = ((cc[a][reg] - col_lo) | (col_hi - 1 - cc[a][reg])) >> 31;
+#pragma unroll
+    for (int sd = 0; sd < 2; ++sd) {
+        const int ch = fd.child[sd][t];
+        const int chs = ch >= 0 ? ch : t;                          // no such child: every entry is absent, and Sc[0] is a safe address
+        const int nochild = ch >> 31;
+        const int npc = fd.npiv[chs], nbc = fd.nf[chs] - npc;
+        gm.Sc[sd] = reinterpret_cast<const char*>(fd.S + fd.soff[chs]);
+        const char* inv = reinterpret_cast<const char*>(fd.cinv[sd] + dp);        // uniform base, 32-bit byte offsets
+        unsigned colbits = 0u;
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int y = *reinterpret_cast<const int*>(inv + 4u * (unsigned)min(cc[a][reg], nf - 1)) | nochild | outm[a][reg];   // -1: none
+                colbits |= ((unsigned)~y >> 31) << (4 * a + reg);
+                gm.colb[sd][a][reg] = __umul24(8u * (unsigned)nbc, (unsigned)(max(y, npc) - npc));
+            }
+#pragma unroll
+        for (int b = 0; b < NR; ++b) {
+            const int x = *reinterpret_cast<const int*>(inv + 4u * (unsigned)min(r[b], nf - 1)) | nochild | ((nf - 1 - r[b]) >> 31);   // -1: none
+            gm.em[sd][b] = colbits & (unsigned)~(x >> 31);
+            gm.rowb[sd][b] = 8u * (unsigned)(max(x, npc) - npc);
+        }
+    }
+    if (DIAG) {
+#pragma unroll
+        for (int b = 0; b < NR; ++b) {
+            unsigned tri = 0u;                                     // bit 4 a + reg: r[b] >= cc[a][reg]
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) tri |= ((unsigned)(cc[a][reg] - 1 - r[b]) >> 31) << (4 * a + reg);
+            gm.em[0][b] &= tri; gm.em[1][b] &= tri;
+        }
+    }
+}
+
+// block row a: out[b][reg] = g0 + g1
+template <int NA, int NR>
+__device__ __forceinline__ void gather_mono_fetch(const GatherMono<NA, NR>& gm, int a, double (&out)[NR][4]) {
+    double g[2][NR][4];
+#pragma unroll
+    for (int sd = 0; sd < 2; ++sd)
+#pragma unroll
+        for (int b = 0; b < NR; ++b)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) g[sd][b][reg] = *reinterpret_cast<const double*>(gm.Sc[sd] + (gm.colb[sd][a][reg] + gm.rowb[sd][b]));
+#pragma unroll
+    for (int b = 0; b < NR; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            double gs[2];
+#pragma unroll
+            for (int sd = 0; sd < 2; ++sd) {
+                const int m = (int)(gm.em[sd][b] << (31 - (4 * a + reg))) >> 31;                 // all ones: the entry exists
+                gs[sd] = __hiloint2double(__double2hiint(g[sd][b][reg]) & m, __double2loint(g[sd][b][reg]) & m);
+            }
+            out[b][reg] = gs[0] + gs[1];
+        }
+}
+
+// Any other front: the child rows of a pair in either order, min / max per entry.
+template <int NA, int NR>
+__device__ __forceinline__ void gather_tile_any(const FrontDev& fd, int t, long long dp, int nf, const int (&r)[NR], const int (&cc)[NA][4],
+                                                const bool (&ccok)[NA][4], double (&cv)[NA][NR][4]) {
+    int rr[2][NR], cr[2][NA][4];
+    const double* Sc[2];
+    int npc[2], nbc[2];
+#pragma unroll
+    for (int sd = 0; sd < 2; ++sd) {
+        const int ch = fd.child[sd][t];
+        const int chs = ch >= 0 ? ch : t;
+        npc[sd] = fd.npiv[chs]; nbc[sd] = fd.nf[chs] - npc[sd];
+        Sc[sd] = fd.S + fd.soff[chs];
+#pragma unroll
+        for (int b = 0; b < NR; ++b) {
+            rr[sd][b] = fd.cinv[sd][dp + min(r[b], nf - 1)];
+            if (ch < 0 || r[b] >= nf) rr[sd][b] = -1;
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                cr[sd][a][reg] = fd.cinv[sd][dp + min(cc[a][reg], nf - 1)];
+                if (ch < 0 || !ccok[a][reg]) cr[sd][a][reg] = -1;
+            }
+    }
+    double g0[NA][NR][4], g1[NA][NR][4];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < NR; ++b)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const bool tri = r[b] >= cc[a][reg];
+                {
+                    const int x = rr[0][b], y = cr[0][a][reg];
+                    const bool ok = tri && x >= 0 && y >= 0;
+                    const int lo = min(x, y) - npc[0], hi = max(x, y) - npc[0];
+                    g0[a][b][reg] = Sc[0][ok ? hi + (size_t)nbc[0] * lo : 0];
+                    if (!ok) g0[a][b][reg] = 0.0;
+                }
+                {
+                    const int x = rr[1][b], y = cr[1][a][reg];
+                    const bool ok = tri && x >= 0 && y >= 0;
+                    const int lo = min(x, y) - npc[1], hi = max(x, y) - npc[1];
+                    g1[a][b][reg] = Sc[1][ok ? hi + (size_t)nbc[1] * lo : 0];
+                    if (!ok) g1[a][b][reg] = 0.0;
+                }
+            }
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < NR; ++b)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) cv[a][b][reg] = g0[a][b][reg] + g1[a][b][reg];
+}
+
 // GATHER (levels above the leaves, the launch that touches its columns first): the tile of C does not exist yet -- it is
 // the sum of the children's Schur-complement entries that land there (the extend-add of these columns, left out of
 // k_extend_gather), gathered here and written once.  `mask`: strong-BC pivots get their unit diagonal, as in the extend-add.
@@ -1482,6 +1667,76 @@ k_trailing_mfma(FrontDev fd, const int* __restrict__ level_nodes, int first, int
         const int cc = cj + wc + 16 * a + l4 + 4 * reg;
         return cok[a][reg] ? fv.col(cc) : fv.P - (nf - 1);
     };
+    // Where the launch's columns live: all in the Schur arena (col_lo >= np: the Schur updates of the left-looking levels, entry
+    // (r, c) at S + (r - np) + (nf - np) (c - np)), all in the panel store (col_hi <= np: P + r + ldp c), or both (-1: col_ptr per
+    // entry).  The one-store cases keep byte offsets in 32 bits, guarded by the size of the block.
+    const int st_side = (col_lo >= np && nf - np <= (1 << 14)) ? 1 : (col_hi <= np && (size_t)ldp * (size_t)np < (size_t)(1u << 28)) ? 0 : -1;
+    const int st_ld = st_side == 1 ? nf - np : ldp, st_c0 = st_side == 1 ? np : 0;
+    char* const st_base = reinterpret_cast<char*>(st_side == 1 ? fv.S : fv.P);
+    // block row a of the wave's quarter: strong-BC pivots get their unit diagonal (gathering launches), C = cva - D is stored
+    auto finish = [&](int a, const double (&cva)[2][4]) {
+        double x[2][4];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) x[b][reg] = cva[b][reg];
+        if (GATHER && mask && bx == 0) {                       // diagonal entries exist only in the tiles on the diagonal (a uniform branch)
+            const int* gd = fd.dofs + fd.doff[t];
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
+                    const int r = ri + wr + 16 * b + l15;
+                    if (r == cc && cok[a][reg] && cc < np && mask[gd[r]]) x[b][reg] = 1.0;
+                }
+        }
+        if (st_side >= 0) {
+            // all of the launch's columns in one store: a uniform base and 32-bit byte offsets, a column term plus a row term
+            unsigned co[4], ro[2];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) co[reg] = 8u * (unsigned)st_ld * (unsigned)(cj + wc + 16 * a + l4 + 4 * reg - st_c0);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) ro[b] = 8u * (unsigned)(ri + wr + 16 * b + l15 - st_c0);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
+                    const int r = ri + wr + 16 * b + l15;
+                    if (cok[a][reg] && r < nf && r >= cc) *reinterpret_cast<double*>(st_base + (co[reg] + ro[b])) = x[b][reg] - acc[a][b][reg];
+                }
+            return;
+        }
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int cc = cj + wc + 16 * a + l4 + 4 * reg;
+                const int r = ri + wr + 16 * b + l15;
+                if (cok[a][reg] && r < nf && r >= cc) col_ptr(a, reg)[r] = x[b][reg] - acc[a][b][reg];
+            }
+    };
+    int gr[2], gc[2][4];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) gr[b] = ri + wr + 16 * b + l15;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) gc[a][reg] = cj + wc + 16 * a + l4 + 4 * reg;
+    if (GATHER && fd.cmono[t] == 3) {
+        // both children land in increasing rows: per-column addressing, one block row at a time (gather_mono_*)
+        GatherMono<2, 2> gm;
+        if (bx == 0) gather_mono_prepare<2, 2, true>(fd, t, fd.doff[t], nf, col_lo, col_hi, gr, gc, gm);
+        else gather_mono_prepare<2, 2, false>(fd, t, fd.doff[t], nf, col_lo, col_hi, gr, gc, gm);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            double cva[2][4];
+            gather_mono_fetch<2, 2>(gm, a, cva);
+            finish(a, cva);
+        }
+        return;
+    }
     double cv[2][2][4];
     if (!GATHER) {
         double* cp[2][4];
@@ -1500,89 +1755,9 @@ k_trailing_mfma(FrontDev fd, const int* __restrict__ level_nodes, int first, int
                     const bool ok = cok[a][reg] && r < nf && r >= cc;
                     cv[a][b][reg] = cp[a][reg][ok ? r : nf - 1];
                 }
-    } else {
-        // rows of the two children's fronts that land on this lane's two rows and eight columns (-1: none): boundary rows
-        // of the children (>= their pivot count), so every entry sits in a child's Schur block S_c[(hi - np_c) + nb_c (lo - np_c)]
-        const long long dp = fd.doff[t];
-        int rr[2][2], cr[2][2][4];
-        const double* Sc[2];
-        int npc[2], nbc[2];
+    } else gather_tile_any<2, 2>(fd, t, fd.doff[t], nf, gr, gc, cok, cv);      // the sum of the two children's entries that land on this lane's two rows and eight columns
 #pragma unroll
-        for (int sd = 0; sd < 2; ++sd) {
-            const int ch = fd.child[sd][t];
-            const int chs = ch >= 0 ? ch : t;
-            npc[sd] = fd.npiv[chs]; nbc[sd] = fd.nf[chs] - npc[sd];
-            Sc[sd] = fd.S + fd.soff[chs];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int r = ri + wr + 16 * b + l15;
-                rr[sd][b] = fd.cinv[sd][dp + min(r, nf - 1)];
-                if (ch < 0 || r >= nf) rr[sd][b] = -1;
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                    cr[sd][a][reg] = fd.cinv[sd][dp + min(cc, nf - 1)];
-                    if (ch < 0 || !cok[a][reg]) cr[sd][a][reg] = -1;
-                }
-        }
-        double g0[2][2][4], g1[2][2][4];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                    const int r = ri + wr + 16 * b + l15;
-                    const bool tri = r >= cc;
-                    {
-                        const int x = rr[0][b], y = cr[0][a][reg];
-                        const bool ok = tri && x >= 0 && y >= 0;
-                        const int lo = min(x, y) - npc[0], hi = max(x, y) - npc[0];
-                        g0[a][b][reg] = Sc[0][ok ? hi + (size_t)nbc[0] * lo : 0];
-                        if (!ok) g0[a][b][reg] = 0.0;
-                    }
-                    {
-                        const int x = rr[1][b], y = cr[1][a][reg];
-                        const bool ok = tri && x >= 0 && y >= 0;
-                        const int lo = min(x, y) - npc[1], hi = max(x, y) - npc[1];
-                        g1[a][b][reg] = Sc[1][ok ? hi + (size_t)nbc[1] * lo : 0];
-                        if (!ok) g1[a][b][reg] = 0.0;
-                    }
-                }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) cv[a][b][reg] = g0[a][b][reg] + g1[a][b][reg];
-        if (mask && bx == 0) {                                // diagonal entries exist only in the tiles on the diagonal
-            const int* gd = fd.dofs + dp;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                        const int r = ri + wr + 16 * b + l15;
-                        if (r == cc && cok[a][reg] && cc < np && mask[gd[r]]) cv[a][b][reg] = 1.0;
-                    }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int cc = cj + wc + 16 * a + l4 + 4 * reg;
-                const int r = ri + wr + 16 * b + l15;
-                if (cok[a][reg] && r < nf && r >= cc) col_ptr(a, reg)[r] = cv[a][b][reg] - acc[a][b][reg];
-            }
+    for (int a = 0; a < 2; ++a) finish(a, cv[a]);
 }
 
 // ---- the narrow (schur 0) update cut finer, for launches that do not fill the chip.  At the top of the tree a narrow update is a
@@ -1656,29 +1831,25 @@ k_trailing_fine(FrontDev fd, const int* __restrict__ level_nodes, int first, int
         for (int reg = 0; reg < 4; ++reg) cv[reg] = *cp[reg];
     } else {
         const long long dp = fd.doff[t];
-        double g[2][4];
+        int gr[1] = {r}, gc[1][4];
+        bool ccok[1][4];
+        double g[1][1][4];
 #pragma unroll
-        for (int sd = 0; sd < 2; ++sd) {
-            const int ch = fd.child[sd][t];
-            const int chs = ch >= 0 ? ch : t;
-            const int npc = fd.npiv[chs], nbc = fd.nf[chs] - npc;
-            const double* Sc = fd.S + fd.soff[chs];
-            const int x = (ch >= 0 && r < nf) ? fd.cinv[sd][dp + r] : -1;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int cc = cj + wc + l4 + 4 * reg;
-                const int y = (ch >= 0 && cok[reg]) ? fd.cinv[sd][dp + cc] : -1;
-                const bool ok = cok[reg] && x >= 0 && y >= 0;
-                const int lo = min(x, y) - npc, hi = max(x, y) - npc;
-                g[sd][reg] = Sc[ok ? hi + (size_t)nbc * lo : 0];
-                if (!ok) g[sd][reg] = 0.0;
-            }
+        for (int reg = 0; reg < 4; ++reg) {
+            gc[0][reg] = cj + wc + l4 + 4 * reg;
+            ccok[0][reg] = gc[0][reg] >= col_lo && gc[0][reg] < col_hi;
         }
+        if (fd.cmono[t] == 3) {                                  // both children land in increasing rows: per-column addressing
+            GatherMono<1, 1> gm;
+            if (bx == 0) gather_mono_prepare<1, 1, true>(fd, t, dp, nf, col_lo, col_hi, gr, gc, gm);
+            else gather_mono_prepare<1, 1, false>(fd, t, dp, nf, col_lo, col_hi, gr, gc, gm);
+            gather_mono_fetch<1, 1>(gm, 0, g[0]);
+        } else gather_tile_any<1, 1>(fd, t, dp, nf, gr, gc, ccok, g);
         const int* gd = fd.dofs + dp;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int cc = cj + wc + l4 + 4 * reg;
-            cv[reg] = g[0][reg] + g[1][reg];
+            cv[reg] = g[0][0][reg];
             if (mask && r == cc && cok[reg] && cc < np && mask[gd[r]]) cv[reg] = 1.0;
         }
     }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/femo_symbolic.h"
+#include "child_maps.h"
 
 namespace {
 
@@ -522,6 +523,16 @@ int femo_tail_delay_plan_build(femo_plan** out, int32_t nel, int32_t nP2, int32_
     p->i64["tail_delay_dofs"] = std::move(td_dofs); p->i32["tail_delay_saved"] = std::move(td_saved);
     p->i64["tail_delay_flops3"] = std::move(td_flops3);
     *out = p;
+    return 0;
+}
+
+int femo_child_maps_increasing(int32_t ntree, const int32_t* npiv, const int32_t* nf, const int64_t* dof_off, const int32_t* parent,
+                               const int32_t* left, const int32_t* right, const int32_t* up_map, int32_t* flags) {
+    if (ntree < 1 || !npiv || !nf || !dof_off || !parent || !left || !right || !up_map || !flags) {
+        g_error = "femo_child_maps_increasing: bad arguments";
+        return 1;
+    }
+    femo::child_maps_increasing(ntree, npiv, nf, dof_off, parent, left, right, up_map, flags);      // the rule: child_maps.h
     return 0;
 }
 

@@ -30,6 +30,12 @@ TAIL_DELAY_SIGNATURES = {
     "femo_tail_delay_plan_build": (C.c_int, SIGNATURES["femo_plan_build_ex2"][1] + [C.c_int32]),
 }
 
+# the "increasing" flag of the extend-add gathers (its own table, as above)
+_i64p = C.POINTER(C.c_int64)
+CHILD_MAPS_SIGNATURES = {
+    "femo_child_maps_increasing": (C.c_int, [C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+}
+
 ARRAYS = ("lo", "hi", "left", "right", "parent", "depth", "height", "eorder", "epos", "owner", "piv_nodes", "piv_off",
           "bnd_nodes", "bnd_off", "npiv", "nf", "dof_off", "front_dofs", "up_map", "elem_front", "elem_map", "level_nodes",
           "level_off", "tail_delay_dofs", "tail_delay_saved", "tail_delay_flops3")
@@ -40,7 +46,7 @@ def load():
     if _lib is None:
         path = _build.build_symbolic() if _build.symbolic_needs_build() else _build.SYM_LIB
         lib = C.CDLL(path)
-        for name, (res, args) in {**SIGNATURES, **TAIL_DELAY_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **TAIL_DELAY_SIGNATURES, **CHILD_MAPS_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib
@@ -101,3 +107,17 @@ def plan_arrays(mesh, leaf_size, min_depth=0, axis_rule=0, gap=0.0, node_order=0
             out[k] = from_lib[out[k]].astype(out[k].dtype)
         out["owner"] = out["owner"][to_lib]
     return out
+
+
+def child_maps_increasing(plan):
+    """Per front of ``plan``: bit 0 / bit 1 = the left / right child's boundary rows land here in strictly increasing rows
+    (femo_child_maps_increasing, include/femo_symbolic.h; the numpy statement is solver.symbolic.child_maps_increasing)."""
+    lib = load()
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    npiv, nf, parent, left, right, up = (i32(getattr(plan, k)) for k in ("npiv", "nf", "parent", "left", "right", "up_map"))
+    dof_off = np.ascontiguousarray(plan.dof_off, dtype=np.int64)
+    flags = np.empty(int(plan.ntree), dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(_i32p)
+    if lib.femo_child_maps_increasing(int(plan.ntree), p(npiv), p(nf), dof_off.ctypes.data_as(_i64p), p(parent), p(left), p(right), p(up), p(flags)):
+        raise RuntimeError(lib.femo_plan_last_error().decode())
+    return flags

@@ -448,6 +448,30 @@ def build_plan(mesh, leaf_size=12, impl="native", axis_rule=None, gap=None, node
     return plan
 
 
+def child_maps_increasing(plan, impl="native"):
+    """The "increasing" flag of the extend-add gathers, per front: bit 0 / bit 1 = the boundary rows of the left / right child land in
+    this front in strictly increasing rows (``up_map`` of the child over its rows [npiv, nf)); a missing child counts as increasing.
+    The gathering kernels address such a front per column (option ``gather_mono``); any other front takes the general gather.
+    ``impl="native"``: femo_child_maps_increasing of libfemo_symbolic.so (csrc/child_maps.h, the rule femo_set_frontal_plan applies);
+    ``impl="python"``: the numpy statement of it below."""
+    if impl == "native":
+        from . import _native
+        return _native.child_maps_increasing(plan)
+    flags = np.full(int(plan.ntree), 3, dtype=np.int32)
+    for t in range(int(plan.ntree)):
+        p = int(plan.parent[t])
+        if p < 0:
+            continue
+        rows = np.asarray(plan.up_map[plan.dof_off[t] + plan.npiv[t]:plan.dof_off[t + 1]], dtype=np.int64)
+        if np.all(np.diff(rows) > 0):
+            continue
+        if plan.left[p] == t:
+            flags[p] &= ~1
+        elif plan.right[p] == t:
+            flags[p] &= ~2
+    return flags
+
+
 def rank_plan(mesh, T: Tree, rank, nranks):
     return _rank_plan(mesh, T, rank, nranks)
 

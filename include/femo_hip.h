@@ -349,6 +349,9 @@ int femo_set_solver(femo_ctx* ctx, int preconditioner, double rtol, int32_t maxi
  *   schedule run the bulk of an update on a second stream beside the next panel;
  *   "fused_schur" (default 1): Schur complements are gathered from the children by the rank-k update that touches them
  *   first instead of by the extend-add;
+ *   "gather_mono" (default 1): the kernels that gather a front from its children's Schur complements address a front whose
+ *   two children land in increasing rows (every front of the package's default plan) per column, without ordering each pair of
+ *   child rows; 0: the general gather everywhere.  The factor is the same bit for bit;
  *   "fuse_rows" (default 1), "fuse_rows_cnt" (2048), "fuse_rows_np" (256): levels of at least that many fronts whose widest front has at most
  *   that many pivots form the rows under a diagonal block inside the diagonal-block kernel;
  *   "rows_fine_wg" (96), "narrow_fine_wg" (128): launches of at most that many workgroups take the kernels with 16 rows / a 16 x 16 block per wave;

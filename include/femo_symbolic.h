@@ -75,6 +75,13 @@ int femo_plan_build_ex2(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, i
 int femo_tail_delay_plan_build(femo_plan** out, int32_t nel, int32_t nP2, int32_t nV, int32_t npc, int32_t ndpc, const int32_t* cell_p2,
                                const double* cent, const double* cext, const int32_t* cell_dofs, int32_t leaf_size, int32_t min_depth,
                                int32_t axis_rule, double gap_coeff, int32_t node_order, int32_t tail_max);
+/* The "increasing" flag of the extend-add gathers of the numeric phase, per front: bit 0 = the boundary rows of the LEFT child land in
+ * this front in strictly increasing rows ("up_map" of the child over its rows [npiv, nf)), bit 1 = those of the RIGHT child; a missing
+ * child counts as increasing.  For an entry (r >= c) of such a front the child's rows (x, y) that land there satisfy x >= y, which is
+ * what the gathering kernels' per-column addressing needs (option "gather_mono" of femo_hip.h; every other front takes the general
+ * gather).  femo_set_frontal_plan computes the same flags from the same rule (csrc/child_maps.h).  flags: ntree entries. */
+int femo_child_maps_increasing(int32_t ntree, const int32_t* npiv, const int32_t* nf, const int64_t* dof_off, const int32_t* parent,
+                               const int32_t* left, const int32_t* right, const int32_t* up_map, int32_t* flags);
 /* number of entries of a named array (-1: no such array); 4 or 8 bytes per entry (0: no such array) */
 int64_t femo_plan_size(const femo_plan* p, const char* name);
 int femo_plan_itemsize(const femo_plan* p, const char* name);

@@ -48,6 +48,7 @@ for name, m, marker, strong in cases:
                     rows_fine_wg=int(rng.choice([0, 64, 96, 100000])), narrow_fine_wg=int(rng.choice([0, 16, 128, 100000])), fuse_rows=int(rng.integers(0, 2)), sweep_ahead=int(rng.integers(0, 4)), sweep_graph=int(rng.integers(0, 2)), fuse_rows_cnt=int(rng.choice([1, 512])), fuse_rows_np=int(rng.choice([128, 256, 100000])), diag_v1_cnt=int(rng.choice([1, 512])), lookahead=int(rng.integers(0, 2)), lookahead_cnt=int(rng.choice([4, 16, 1000])),
                     fused_schur=int(rng.integers(0, 2)), diag_v1=int(rng.integers(0, 3)), grid_chunk=int(rng.choice([3, 17, 65535])), xinv_small_cnt=int(rng.choice([0, 32, 100000])),
                     sweep_w=int(rng.integers(0, 2)), assemble_fc=int(rng.choice([0, 1, 2])))
+        post["gather_mono"] = int(rng.integers(0, 2))               # the per-column gather of increasing fronts, or the general one everywhere
         pre = dict(wide_cnt=int(rng.choice([0, 8, 512, 100000])), wide_np=int(rng.choice([64, 512])), swork_slots=int(rng.choice([2, 100, 8192])),
                    tail_max=int(rng.choice([0, 16, 32])))          # the tail-delay pass of the symbolic plan: off, and two lengths
         leaf = int(rng.choice([4, 8, 12, 20]))
