@@ -323,6 +323,15 @@ class ShellContext:
         self._chk(self.lib.femo_ply_failure_field(self._h, dptr(out), out.size))
         return out.reshape(self.mesh.nel, -1)
 
+    def ply_strength_index_field(self):
+        """(nel, npt): the load-proportional strength index r = 1 / (strength ratio) of the ply table, the largest over the cell's
+        quadrature points per recovery point (femo_ply_strength_index_field): the load may grow by 1 / r until the Tsai-Wu index of
+        ``ply_failure_field`` reaches one.  Needs a table whose quadratic form is positive semidefinite."""
+        n = int(self.lib.femo_field_size(self._h, b"ply_table"))
+        out = np.empty(max(n, 0) // 16)
+        self._chk(self.lib.femo_ply_strength_index_field(self._h, dptr(out), out.size))
+        return out.reshape(self.mesh.nel, -1)
+
     def set_ply_shear_table(self, table=None, npt=None):
         """Recovery points of the interlaminar shear outputs (femo_set_ply_shear_table; laminate mode): ``table`` is the
         (nel, npt, 6) array of ``laminate.ply_shear_table`` in solver cell order (or flat, with ``npt`` given); ``None`` removes it.
@@ -776,8 +785,8 @@ class ShellContext:
         ``field_size_of(name)`` entries (nvc * nel for the DG1 stress fields; nel * npt, cell-major like
         ``ply_failure_field().ravel()``, for 'ply_failure_field'), or several as rows of a 2-D array (the result has the same number
         of rows).  Points of zero stress contribute zero (a subgradient); an entry of the ply failure field is differentiated at
-        its first maximiser, the branch the forward mode takes.  'ply_failure_field' also takes wrt 'ply_table' and, under an
-        active layup, 'ply_thickness' / 'ply_angle'."""
+        its first maximiser, the branch the forward mode takes.  'ply_failure_field' and 'ply_strength_index_field' also take wrt
+        'ply_table' and, under an active layup, 'ply_thickness' / 'ply_angle'."""
         cb = np.ascontiguousarray(cbar, dtype=np.float64)
         one = cb.ndim == 1
         cb = self._cotangent_rows(name, cb)
@@ -804,7 +813,7 @@ class ShellContext:
     def field_total_gradients(self, name, cbars, arg):
         """Total derivatives d (cbar_k . field) / d arg through the solved state for the rows cbar_k of ``cbars`` -- one grouped
         adjoint solve (femo_field_total_gradients).  Returns (gradients (nbar, n), iterations, relative residuals).  A row has
-        ``field_size_of(name)`` entries.  'ply_failure_field' takes arg 'laminate', 'ply_table', 'F_solid', 'thickness', 'E', 'nu',
+        ``field_size_of(name)`` entries.  'ply_failure_field' (and 'ply_strength_index_field' likewise) takes arg 'laminate', 'ply_table', 'F_solid', 'thickness', 'E', 'nu',
         'density' (no solve runs where the residual does not depend on the argument: iterations 0) and, under an active layup,
         'ply_thickness' / 'ply_angle', composed on the device: k local failure constraints cost ceil(k / 4) grouped solves."""
         cb = self._cotangent_rows(name, np.ascontiguousarray(cbars, dtype=np.float64))
@@ -828,9 +837,9 @@ class ShellContext:
         return cb.reshape(-1, nc)
 
     def field_size_of(self, name):
-        """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field' and
-        'ply_shear_failure_field' (the recovery points of their own tables)."""
-        if name == "ply_failure_field":
+        """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field',
+        'ply_strength_index_field' and 'ply_shear_failure_field' (the recovery points of their own tables)."""
+        if name in ("ply_failure_field", "ply_strength_index_field"):
             return max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // 16
         if name == "ply_shear_failure_field":
             return max(int(self.lib.femo_field_size(self._h, b"ply_shear_table")), 0) // 6

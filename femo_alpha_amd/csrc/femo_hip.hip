@@ -14,6 +14,7 @@
 #include "ply_shear.h"
 #include "field_jvp.h"
 #include "ply_field_rev.h"
+#include "ply_strength.h"
 #include "layup.h"
 #include "layup_mass.h"
 #include "disp_aggregate.h"
@@ -40,7 +41,7 @@ constexpr int WIDE_NP_DEFAULT = 512;    // option "wide_np" overrides it for the
 constexpr int WIDE_CNT_DEFAULT = 512;   // option "wide_cnt": levels with at most this many fronts also take the wide (many workgroups per
                                         // front) solve kernels -- one workgroup per front cannot pull a level's factor out of HBM
 
-#define FEMO_VERSION 102
+#define FEMO_VERSION 103
 
 static std::string g_create_error;
 
@@ -143,6 +144,14 @@ struct femo_ctx {
         DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
         DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_shear_dtable")
     } psh;
+    // load-proportional ply strength index (ply_strength.h): the table is ply's; slots and results are its own, so that a call never
+    // disturbs the shift ply_failure's gradients read
+    struct PlyStrength {
+        bool psd_ok = false;        // the table has passed k_ply_psd_check since it was last uploaded or built by femo_set_layup
+        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
+        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_strength_dtable")
+        DevBuf<int> first;          // k_ply_psd_check: the first offending recovery point
+    } pst;
     // layup mode (femo_set_layup; layup.h): the laminate and the ply table are built on the device from ply thicknesses and angles
     struct Layup {
         bool active = false;
@@ -657,6 +666,10 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_PS_FIELD , PS_FIELD
 #define COMMA_PS_DW , PS_DW
 #define COMMA_PS_DTABLE , PS_DTABLE
+#define COMMA_PSI_VALUE , PSI_VALUE
+#define COMMA_PSI_FIELD , PSI_FIELD
+#define COMMA_PSI_DW , PSI_DW
+#define COMMA_PSI_DTABLE , PSI_DTABLE
 
 static const int EB = 128;   // element kernels: threads per block (one element per thread)
 
@@ -2295,6 +2308,7 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
             c->clt.reset();
             c->clt_sym.reset();
             c->ply = femo_ctx::Ply();                          // the recovery points belong to the laminate
+            c->pst.psd_ok = false;
             c->psh = femo_ctx::PlyShear();
             c->lay = femo_ctx::Layup();                        // ... and so does the layup
             operator_changed(c);
@@ -2372,6 +2386,7 @@ int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n)
     if (!table && n == 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->ply = femo_ctx::Ply();
+        c->pst.psd_ok = false;
         return 0;
     }
     char buf[240];
@@ -2403,6 +2418,7 @@ int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ply.npt = npt; c->ply.rho = rho;
+    c->pst.psd_ok = false;                                     // a new table: the strength index checks it when first asked for
     return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
 }
 
@@ -2633,6 +2649,7 @@ int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfa
     }
     lay.nply = nply; lay.surfaces = surfaces; lay.npt = npt; lay.c_drill = c_drill;
     lay.active = true;
+    c->pst.psd_ok = false;                                 // new strength coefficients: the strength index checks them when first asked for
     if (int rc = layup_build(c)) return rc;
     if (int rc = layup_shear_build(c)) return rc;
     c->laminate = true;
@@ -3253,6 +3270,91 @@ static int shear_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, doubl
     return ply_gather_sum(c, out);
 }
 
+// ---- load-proportional ply strength index (ply_strength.h) on the ply failure's table; eslot and gather are the ply failure's, the
+// slots and the results its own
+static bool strength_name(const std::string& fn) { return fn == "ply_strength_index"; }
+
+// a table, and one whose quadratic form is positive semidefinite: checked on the device once per upload or femo_set_layup, when one
+// of these outputs is first asked for; the error names the first offending cell and point
+static int strength_need_table(femo_ctx* c, const char* who) {
+    if (ply_need_table(c, who)) return 2;
+    if (c->pst.psd_ok) return 0;
+    const long long np = (long long)c->nel * c->ply.npt;
+    int first = INT32_MAX;
+    HIPCHK(c, c->pst.first.grow(1));
+    HIPCHK(c, hipMemcpyAsync(c->pst.first, &first, sizeof first, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_ply_psd_check, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ply.tab, np, c->pst.first.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&first, c->pst.first, sizeof first, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (first == INT32_MAX) {
+        c->pst.psd_ok = true;
+        return 0;
+    }
+    char buf[320];
+    snprintf(buf, sizeof buf, "%s: the quadratic form of recovery point %d of cell %d is not positive semidefinite (F11, F22, F66 >= 0 and "
+                              "F12^2 <= F11 F22): the strength index needs a >= 0; 'ply_failure' takes this table", who, first % c->ply.npt,
+             first / c->ply.npt);
+    return fail(c, buf);
+}
+
+// the refusals every derivative entry point makes for the aggregate before it does anything else
+static int strength_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
+    if (!strength_name(fn)) return 0;
+    if (int rc = strength_need_table(c, "ply_strength_index")) return rc;
+    if (arg == "uhat") return fail(c, "ply_strength_index: the shape derivative (uhat) of this output is not provided");
+    return 0;
+}
+
+// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
+static int strength_value_launch(femo_ctx* c) {
+    auto& ps = c->pst;
+    const int g = nblk(c->nel, PLY_BLOCK);
+    HIPCHK(c, ps.part.grow((size_t)3 * g));
+    HIPCHK(c, ps.res.grow(4));
+    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
+                (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ps.part.get());
+    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ps.part, stress_alpha_ref(c), c->ply.npt, c->ply.rho, ps.res.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
+static int strength_value_dev(femo_ctx* c, double out4[4]) {
+    if (int rc = strength_need_table(c, "ply_strength_index")) return rc;
+    if (strength_value_launch(c)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->pst.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
+    if (!std::isfinite(out4[2])) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "ply_strength_index: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
+                                  "non-finite state or strength index", out4[0], out4[3], c->ply.rho);
+        return fail(c, msg);
+    }
+    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
+    return 0;
+}
+
+// (d / d w) into out (ndof) or (d / d table) into out (16 npt nel, cell-major).  cbar null: of the aggregate K over the selected
+// sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
+static int strength_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, double* out) {
+    auto& ps = c->pst;
+    if (!cbar && strength_value_launch(c)) return 1;
+    const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+    if (!wrt_state) {
+        ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_DTABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
+                    (const double*)c->w, (const double*)ps.res, cbar, (const int*)nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    if (int rc = ply_eslot(c)) return rc;
+    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_DW, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
+                (const double*)c->w, (const double*)ps.res, cbar, (const int*)c->ply.eslot, c->ybuf.get());
+    return ply_gather_sum(c, out);
+}
+
 // ---- mass and volume from the layup (layup_mass.h): outputs of the layup itself, not of the laminate, and independent of the state
 static bool layup_mass_name(const femo_ctx* c, const std::string& fn) {
     return c->lay.active && (fn == "layup_mass" || fn == "layup_volume");
@@ -3482,6 +3584,12 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         *value = v[2];
         return 0;
     }
+    if (strength_name(s)) {
+        double v[4];
+        if (int rc = strength_value_dev(c, v)) return rc;
+        *value = v[2];
+        return 0;
+    }
     if (const int slot = disp_agg_slot(s); slot >= 0) {
         double v[4];
         if (int rc = disp_agg_value_dev(c, s, slot, v)) return rc;
@@ -3586,6 +3694,12 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
         if (wrt == "disp_solid" || wrt == "ply_shear_table") return shear_grad_dev(c, wrt == "disp_solid", nullptr, out);
         HIPCHK(c, hipGetLastError());
         return 0;                                             // laminate, ply_table, thickness, E, nu, density, F_solid: no explicit dependence
+    }
+    if (strength_name(fn)) {
+        if (int rc = strength_gate(c, fn, wrt)) return rc;
+        if (wrt == "disp_solid" || wrt == "ply_table") return strength_grad_dev(c, wrt == "disp_solid", nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;                                             // laminate, thickness, E, nu, density, F_solid, ply_shear_table: no explicit dependence
     }
     if (const int slot = disp_agg_slot(fn); slot >= 0) {      // nodal values, not integrals: the state is the only argument they see
         if (wrt == "disp_solid") return disp_agg_grad_dev(c, fn, slot, out);
@@ -3696,6 +3810,7 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
         if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
     }
     if (int rc = shear_gate(c, fn, a)) return rc;
+    if (int rc = strength_gate(c, fn, a)) return rc;
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     if (layup_mass_name(c, fn)) {                                           // no state dependence: lambda = 0, the total is the partial
@@ -3815,6 +3930,8 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
         }
     for (int i = 0; i < nfun; ++i)
         if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
@@ -4051,6 +4168,8 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
         }
     for (int i = 0; i < nfun; ++i)
         if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     const int keep_sel = c->csel;
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
@@ -5773,13 +5892,17 @@ static int ply_field_jacobian(femo_ctx* c, const std::string& a, int64_t* rowptr
 // out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k for the ply failure field.  R sees the laminate and the load alone in
 // laminate mode: for every other argument no solve runs (iterations 0, residuals 0).  The layup: lbar_k = -(dR / d laminate)^T lambda_k
 // and tbar_k = (d field / d table)^T cbar_k go through ONE pull-back, the composition of dfunctional_dev / dRdarg_T_dev.
-static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
-                                     double* relres) {
-    if (ply_need_table(c, "ply_failure_field")) return 2;
+// Shared by the fields on the ply table, "ply_failure_field" and "ply_strength_index_field": vjp is the field's own product with one
+// device cotangent (table = false: the state, true: the table), arg_vjp its product for any admitted argument.
+typedef int (*ply_table_field_vjp)(femo_ctx*, bool, const double*, double*);
+static int ply_table_field_total_gradients(femo_ctx* c, const char* field, int (*need_table)(femo_ctx*, const char*), ply_table_field_vjp vjp,
+                                           point_field_arg_vjp arg_vjp, int32_t nbar, const double* cbar, const std::string& a, double* out,
+                                           int64_t n, int32_t* iters, double* relres) {
+    if (int rc = need_table(c, field)) return rc;
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nel * npt entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
     int lw;
-    if (int rc = ply_field_rev_arg(c, a, n, true, &lw)) return rc;
+    if (int rc = point_field_rev_arg(c, field, a, n, true, &lw)) return rc;
     const bool solve = lw || a == "laminate" || a == "F_solid";
     const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * c->ply.npt, ng = (size_t)std::max<int64_t>(n, 1);
     const int64_t nl = (int64_t)LAM_W * c->nel;
@@ -5795,7 +5918,7 @@ static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cb
     int rc = 0;
     if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
     if (solve) {
-        for (int k = 0; k < nbar && !rc; ++k) rc = ply_field_vjp_dev(c, false, Cd + k * nc, B[k]);               // (d field / d w)^T cbar_k
+        for (int k = 0; k < nbar && !rc; ++k) rc = vjp(c, false, Cd + k * nc, B[k]);                             // (d field / d w)^T cbar_k
         if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_k
     } else {
         for (int k = 0; k < nbar; ++k) {
@@ -5808,11 +5931,11 @@ static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cb
         if (lw) {                                         // the stream orders the reuse of lbar and tbar
             hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 0.0, nl);
             rc = dRdarg_T_dev(c, "laminate", X[k], -1.0, c->lay.lbar, nl);
-            if (!rc) rc = ply_field_vjp_dev(c, true, Cd + k * nc, c->lay.tbar);
+            if (!rc) rc = vjp(c, true, Cd + k * nc, c->lay.tbar);
             if (!rc) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, g, 0.0, n);
             if (!rc) rc = layup_vjp_dev(c, lw, c->lay.lbar, c->lay.tbar, g);
         } else {
-            rc = ply_field_arg_vjp_dev(c, a, 0, Cd + k * nc, g, n);                                              // (d field / d arg)^T cbar_k
+            rc = arg_vjp(c, a, 0, Cd + k * nc, g, n);                                                            // (d field / d arg)^T cbar_k
             if (!rc && solve) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                         // - (dR/d arg)^T lambda_k
         }
     }
@@ -5822,6 +5945,58 @@ static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cb
         if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
     }
     return rc;
+}
+
+static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
+                                     double* relres) {
+    return ply_table_field_total_gradients(c, "ply_failure_field", ply_need_table, ply_field_vjp_dev, ply_field_arg_vjp_dev, nbar, cbar, a, out, n,
+                                           iters, relres);
+}
+
+// ---- reverse mode of the ply strength index field (ply_strength.h: the gradient modes with a cotangent in place of the KS weight,
+// at the maximiser), under the name "ply_strength_index_field".  Forward mode and the sparse Jacobian are not provided.
+static int strength_field_not_provided(femo_ctx* c, const char* who) {
+    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of 'ply_strength_index_field' are not provided "
+                                      "(femo_field_output_vjp, femo_field_total_gradients)");
+}
+
+static int strength_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return strength_grad_dev(c, !table, cbar, out); }
+
+// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
+// the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
+static int strength_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    if (wrt == "disp_solid" || wrt == "ply_table") return strength_grad_dev(c, wrt == "disp_solid", cbar, out);
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    HIPCHK(c, hipGetLastError());
+    if (!lw) return 0;
+    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
+    if (int rc = strength_grad_dev(c, false, cbar, c->lay.tbar)) return rc;
+    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
+}
+
+static int strength_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    return point_field_output_vjp(c, "ply_strength_index_field", strength_need_table, &c->ply.npt, strength_field_arg_vjp_dev, a, cbar, nbar, out, n);
+}
+
+static int strength_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n,
+                                          int32_t* iters, double* relres) {
+    return ply_table_field_total_gradients(c, "ply_strength_index_field", strength_need_table, strength_field_vjp_dev, strength_field_arg_vjp_dev,
+                                           nbar, cbar, a, out, n, iters, relres);
+}
+
+int femo_ply_strength_index_field(femo_ctx* c, double* out, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = strength_need_table(c, "femo_ply_strength_index_field")) return rc;
+    const int64_t len = (int64_t)c->nel * c->ply.npt;
+    if (!out || n != len) return fail(c, "femo_ply_strength_index_field: the field has nel * npt entries");
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)len));
+    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
+                c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, d.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- reverse mode of the interlaminar shear field (ply_shear.h: the gradient modes with a cotangent in place of the KS weight), under
@@ -5908,6 +6083,7 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
     if (fname == "ply_shear_failure_field") return shear_field_output_vjp(c, a, cbar, nbar, out, n);
+    if (fname == "ply_strength_index_field") return strength_field_output_vjp(c, a, cbar, nbar, out, n);
     if (fname == "ply_failure_field") return ply_field_output_vjp(c, a, cbar, nbar, out, n);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
@@ -5929,6 +6105,7 @@ int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wr
     double zf;
     if (fname == "ply_failure_field") return ply_field_jacobian_nnz(c, a, nnz);
     if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
+    if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
@@ -5944,6 +6121,7 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     int64_t want;
     if (fname == "ply_failure_field") return ply_field_jacobian(c, a, rowptr, colidx, vals, nnz);
     if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
+    if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
     if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
@@ -5981,6 +6159,7 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     double zf;
     if (fname == "ply_failure_field") return ply_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
     if (fname == "ply_shear_failure_field") return shear_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
+    if (fname == "ply_strength_index_field") return strength_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
@@ -6015,6 +6194,7 @@ static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
     double zf;
     if (field_zf(name, &zf)) return (int64_t)c->nvc * c->nel;
     if (name == "ply_shear_failure_field") { shear_field_not_provided(c, "forward mode"); return -1; }
+    if (name == "ply_strength_index_field") { strength_field_not_provided(c, "forward mode"); return -1; }
     if (name != "ply_failure_field") { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
     if (ply_need_table(c, "ply_failure_field")) return -2;
     return (int64_t)c->nel * c->ply.npt;
@@ -6231,6 +6411,15 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             if (s == "ply_shear_dw") return shear_grad_dev(c, true, nullptr, c->tmp);
             HIPCHK(c, c->psh.gtab.grow((size_t)PSH_W * c->psh.npt * c->nel));
             return shear_grad_dev(c, false, nullptr, c->psh.gtab);
+        }
+        // ply strength index: the passes of the shear outputs above, on the ply table; "ply_dtable" is the table product of
+        // "ply_failure" (value pass, PF_DTABLE), the counterpart to measure "ply_strength_dtable" against
+        if (s == "ply_strength_value" || s == "ply_strength_dw" || s == "ply_strength_dtable" || s == "ply_dtable") {
+            if (int rc = s == "ply_dtable" ? ply_need_table(c, "femo_bench_kernel") : strength_need_table(c, "femo_bench_kernel")) return rc;
+            if (s == "ply_strength_value") return strength_value_launch(c);
+            if (s == "ply_strength_dw") return strength_grad_dev(c, true, nullptr, c->tmp);
+            HIPCHK(c, c->pst.gtab.grow((size_t)PLY_W * c->ply.npt * c->nel));
+            return s == "ply_dtable" ? ply_grad_dev(c, false, c->pst.gtab) : strength_grad_dev(c, false, nullptr, c->pst.gtab);
         }
         return fail(c, "unknown kernel '" + s + "'");
     };

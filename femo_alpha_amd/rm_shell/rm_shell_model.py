@@ -67,7 +67,8 @@ def createCustomMeasure(mesh: ShellMesh, dim, SubdomainFunc, measure: str, tag: 
 class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
-                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None, max_disp=None):
+                 device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None, max_disp=None,
+                 ply_strength=False):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -130,6 +131,13 @@ class RMShellModel:
         # max_disp=dict(...) or a list of up to four: one max-displacement output per dict (RMShellPDE.max_disp) with the keys rho,
         # scaler, direction, nodes, name (default "max_disp", "max_disp1", ...) and tag (a key of mesh_tags; none: the whole mesh).  The
         # slot is the position in the list.
+        # ply_strength=True (opt-in; with ply_failure=npt or a layup): the output "ply_strength_index", the KS aggregate of the
+        # load-proportional strength index r = 1 / (strength ratio) on the same ply table, with the arguments "ply_failure" has
+        self.ply_strength = bool(ply_strength)
+        if self.ply_strength and self.ply_failure is None and layup is None:
+            raise ValueError("ply_strength needs a ply table: ply_failure=npt or a layup")
+        if self.ply_strength and layup is not None and not len(tuple(layup.get("surfaces", ("bot", "top")))):
+            raise ValueError("ply_strength needs a ply table: this layup has no recovery points (surfaces)")
         self.max_disp = None
         if max_disp is not None:
             specs = [dict(max_disp)] if isinstance(max_disp, dict) else [dict(d) for d in max_disp]
@@ -242,6 +250,9 @@ class RMShellModel:
         fea.add_output(name="pnorm_stress", form=pnorm_stress_form, arguments=["thickness", "disp_solid", "E", "nu", "uhat"])
         if self.layup is not None and shell_pde.ply_npt:
             fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, None, rho=self.rho), arguments=["disp_solid"] + lam_args)
+        if self.layup is not None and shell_pde.ply_npt and self.ply_strength:
+            fea.add_output(name="ply_strength_index", form=shell_pde.ply_strength_index(w, uhat, None, rho=self.rho),
+                           arguments=["disp_solid"] + lam_args)
         if self.layup is not None and shell_pde.layup_shear:
             # shear_strength=[...] in the layup: the interlaminar shear aggregate, with the arguments ply_failure has on this route
             fea.add_output(name="ply_shear_failure", form=shell_pde.ply_shear_failure(w, uhat, None, rho=self.rho),
@@ -254,6 +265,9 @@ class RMShellModel:
             ply = Function(shell_pde.VP).bind("ply_table")
             fea.add_input("ply_table", ply, init_val=shell_pde.ply_table_init)
             fea.add_output(name="ply_failure", form=shell_pde.ply_failure(w, uhat, ply, rho=self.rho), arguments=["disp_solid", "ply_table"])
+            if self.ply_strength:
+                fea.add_output(name="ply_strength_index", form=shell_pde.ply_strength_index(w, uhat, ply, rho=self.rho),
+                               arguments=["disp_solid", "ply_table"])
         if self.mesh_tags is not None:
             self.set_up_subdomains(self.mesh_tags)
             for tag, i in self.association_table.items():
@@ -278,6 +292,8 @@ class RMShellModel:
             # (nel, npt) flattened, differentiated through FEA.field_tangents (forward) and FEA.field_gradients (reverse: local failure
             # constraints in groups of four adjoint solves); registering it as a field output of the CSDL model is a separate step
             self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, ply)
+        if self.ply_strength and (self.ply_failure is not None or shell_pde.ply_npt):
+            self.ply_strength_index_field_form = shell_pde.ply_strength_index_field(w, uhat, None)
         self.fea = fea
 
     def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None,

@@ -153,6 +153,19 @@ class RMShellPDE:
         self.ctx.set_ply_failure_params(rho)
         return Form(self.ctx, "ply_failure", subdomain=-1 if dx is None else int(dx))
 
+    def ply_strength_index(self, w, uhat, ply_table, dx=None, rho=100.0):
+        """KS aggregate of the load-proportional ply strength index r = 1 / (strength ratio) over the recovery points of the ply
+        table (include/femo_hip.h, "ply_strength_index"): the load may grow by 1 / r until the Tsai-Wu index of ``ply_failure``
+        reaches one.  ``dx`` as for ``ply_failure``; ``rho`` is the exponent the two aggregates share (femo_set_ply_failure_params)."""
+        self.ctx.set_ply_failure_params(rho)
+        return Form(self.ctx, "ply_strength_index", subdomain=-1 if dx is None else int(dx))
+
+    def ply_strength_index_field(self, w, uhat, ply_table):
+        """The (nel, npt) field of the strength index per cell and recovery point (its largest value over the cell's quadrature
+        points) as a field form, in reverse mode only: ``computeMatVecProductBwd(computePartials(form, f), cbar)`` and
+        ``FEA.field_gradients``."""
+        return FieldForm(self.ctx, "ply_strength_index_field")
+
     def ply_shear_failure(self, w, uhat, ply_shear_table, dx=None, rho=100.0):
         """KS aggregate of the interlaminar shear failure index over the recovery points of the shear table (include/femo_hip.h,
         femo_set_ply_shear_table; under a layup with shear strengths the table is the layup's: pass None); ``dx``: None for the whole

@@ -203,6 +203,38 @@ int femo_set_ply_shear_params(femo_ctx* ctx, double rho);
 int femo_ply_shear_failure_field(femo_ctx* ctx, double* out, int64_t n);
 int femo_set_layup_shear_strength(femo_ctx* ctx, int32_t nply, const double* S);
 
+/* Load-proportional ply strength index (femo_alpha_amd/csrc/ply_strength.h) -- new, since FEMO_VERSION 103; the project's own contract
+ * (pinned by tests/ply_strength_ref.py).  The Tsai-Wu index FI = a + b of "ply_failure" has a quadratic part a and a linear part b and
+ * is not proportional to the load; the strength ratio (reserve factor) R, the factor by which the load may grow until first-ply failure,
+ * is.  These outputs give its inverse r = 1/R, the positive root of a/r^2 + b/r = 1, on the ply table of femo_set_ply_table (or of the
+ * layup), unchanged.  At quadrature point q of the degree-4 stress measure and recovery point p, with sigma of "ply_failure":
+ *     b = F1 s1 + F2 s2,   a = F11 s1^2 + F22 s2^2 + F66 t12^2 + 2 F12 s1 s2,   D = sqrt(max(b^2 + 4a, 0)),
+ *     r = (b + D)/2 for b >= 0,   r = 2a/(D - b) for b < 0,   r = 0 where D = 0;   dr = (r db + da)/D, defined as 0 where D = 0.
+ *   r(s w) = s r(w) for s > 0; with F1 = F2 = 0, r = sqrt(FI); scaling the state by 1/r puts FI on 1;
+ *   - functional "ply_strength_index" (femo_functional, femo_dfunctional, femo_total_gradient(s) with the sub-domain list, femo_total_jvp,
+ *     femo_field_gradient_vec: wherever "ply_failure" appears), over the selected sub-domain:
+ *         K = 1/rho log( 1/(alpha npt) sum_e sum_q wj_eq sum_p exp(rho r_eqp) )
+ *     with the wj, alpha and rho of "ply_failure" (femo_set_ply_failure_params: both indices are of order one at failure).  With
+ *     uhat = 0: max r + 1/rho log(min wj / (alpha npt)) <= K <= max r; w = 0 gives K = 0 with the reference area, and exactly zero
+ *     gradients.  femo_dfunctional: wrt "disp_solid" and "ply_table" from the kernels; exact zeros for "laminate", "thickness", "E",
+ *     "nu", "density", "F_solid", "ply_shear_table"; "ply_thickness" / "ply_angle" through the layup's pull-back; "uhat" is refused: the
+ *     shape derivative of this output is not provided;
+ *   - field femo_ply_strength_index_field: (nel, npt), entry = max_q r_eqp, every cell whatever the selection; the first maximiser in
+ *     quadrature order wins and a NaN stays visible.  Differentiated in reverse at that maximiser under the name
+ *     "ply_strength_index_field" (femo_field_output_vjp, femo_field_total_gradients; the argument set of "ply_failure_field", cotangents
+ *     grouped four to a solve).  femo_field_output_jvp, femo_field_total_jvp and femo_field_output_jacobian(_nnz) refuse the name: not
+ *     provided.
+ * r needs a >= 0: the quadratic form of every recovery point must be positive semidefinite, F11, F22, F66 >= 0 and
+ * F12^2 <= F11 F22 (1 + 1e-12) (the slack covers the rounding of tsai_wu(f12 = +-1)).  The table is checked on the device at most once
+ * per upload or femo_set_layup, when one of these outputs is first asked for; a failing table is refused with an error that names the
+ * cell and the point, and "ply_failure" keeps working on it.  The outputs keep their own block slots and results: a call never
+ * disturbs the shift the gradients of "ply_failure" read.  No float atomics and fixed summation orders: two identical calls of
+ * femo_functional, femo_dfunctional, femo_ply_strength_index_field and femo_field_output_vjp return the same bits; the totals repeat to
+ * the solver's tolerance, as for the shear outputs above.
+ * Not provided: the shape derivative; forward mode and the sparse Jacobian of the field; a ratio for the shear index (it is
+ * sqrt(FI), the caller's one line); transient laminates; the multi-GPU driver. */
+int femo_ply_strength_index_field(femo_ctx* ctx, double* out, int64_t n);
+
 /* Layups: the laminate and the ply table built on the device from the design variables of a laminate, ply thicknesses and ply angles
  * (femo_alpha_amd/csrc/layup.h) -- new; the conventions are those of femo_alpha_amd/laminate.py (clt_from_plies, ply_table):
  *   - nply plies (1..32), listed bottom to top along the cell normal, the same materials in every cell: plies is nply x 12,
