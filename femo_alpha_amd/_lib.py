@@ -45,6 +45,8 @@ SIGNATURES = {
     "femo_ply_shear_failure_field": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
     "femo_set_layup_shear_strength": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p]),
     "femo_ply_strength_index_field": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
+    "femo_set_ply_hashin_table": (C.c_int, [C.c_void_p, _c_double_p, C.c_int32, C.c_int64]),
+    "femo_ply_hashin_field": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64]),
     "femo_set_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_get_state": (C.c_int, [C.c_void_p, _c_double_p]),
     "femo_apply_K": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),

@@ -167,7 +167,7 @@ class ShellContext:
     LAYUP_SURFACES = {"bot": 1, "mid": 2, "top": 4}
 
     def set_layup(self, plies, t=None, theta=None, surfaces=("bot", "top"), c_drill=None, density=None, shear_strength=None,
-                  reference=None, offset=None):
+                  reference=None, offset=None, hashin=None):
         """Layup mode (femo_set_layup): the laminate and the ply table are built on the device from ply thicknesses ``t`` and ply
         angles ``theta`` (degrees from E0), both (nel, nply) in solver cell order or (nply,) for the same layup in every cell; plies
         bottom to top.  ``plies``: one dict per ply, or one for all, with E1, E2, G12, nu12, G13, G23 and either the strengths
@@ -181,7 +181,12 @@ class ShellContext:
         strengths [S13, S23] of the outputs "ply_shear_failure" / "ply_shear_failure_field" (``set_layup_shear_strength``); None
         likewise leaves what the context holds.  ``reference`` / ``offset``: the reference surface of the layup
         (``set_layup_reference``), "mid", "bot", "top" or a number, and per-cell lengths in solver cell order; ``reference=None``
-        leaves the surface the mode holds -- the mid-surface when the mode is entered -- and ``offset`` then has to be None too."""
+        leaves the surface the mode holds -- the mid-surface when the mode is entered -- and ``offset`` then has to be None too.
+        ``hashin``: the strengths of the Hashin outputs (``set_ply_hashin_table``), per ply: (nply, 6) or (6,) values
+        [Xt, Xc, Yt, Yc, SL, ST], or ply dicts (one, or one per ply) with Xt, Xc, Yt, Yc, S and optionally ST (default Yc / 2), or True
+        to read them from the dicts of ``plies``.  They are expanded on the host to the table's point order (ply by ply from the
+        bottom, the layup's surfaces inside a ply): they do not depend on thickness or angle.  None leaves what the context holds
+        (a layup with another number of recovery points drops them)."""
         if plies is None:
             self._chk(self.lib.femo_set_layup(self._h, 0, None, 0, 0.0, None, None))
             return
@@ -216,6 +221,31 @@ class ShellContext:
             self.set_layup_density(density)
         if shear_strength is not None:
             self.set_layup_shear_strength(shear_strength)
+        if hashin is not None:
+            if not bits:
+                raise ValueError("set_layup: hashin needs recovery points (surfaces)")
+            per_ply = self._layup_hashin(plies if hashin is True else hashin, nply)
+            self.set_ply_hashin_table(np.repeat(per_ply, len(bits), axis=0))
+
+    @staticmethod
+    def _layup_hashin(strengths, nply):
+        """(nply, 6) Hashin strengths per ply from an array or from ply dicts."""
+        from .laminate import hashin_strengths
+        if isinstance(strengths, dict):
+            strengths = [strengths] * nply
+        if isinstance(strengths, (list, tuple)) and len(strengths) and isinstance(strengths[0], dict):
+            if len(strengths) != nply:
+                raise ValueError(f"set_layup: {len(strengths)} sets of Hashin strengths for {nply} plies")
+            missing = [k for p in strengths for k in ("Xt", "Xc", "Yt", "Yc", "S") if k not in p]
+            if missing:
+                raise ValueError(f"set_layup: hashin needs the strengths Xt, Xc, Yt, Yc, S of every ply (missing {missing[0]!r})")
+            strengths = [hashin_strengths(p["Xt"], p["Xc"], p["Yt"], p["Yc"], p["S"], p.get("ST")) for p in strengths]
+        a = np.asarray(strengths, dtype=np.float64)
+        if a.shape == (6,):
+            a = np.broadcast_to(a, (nply, 6))
+        if a.shape != (nply, 6):
+            raise ValueError(f"set_layup: hashin must give [Xt, Xc, Yt, Yc, SL, ST] for each of the {nply} plies, got shape {a.shape}")
+        return np.ascontiguousarray(a)
 
     def _layup_reference(self, reference, offset):
         """(r, offsets (nel,) or None) of a reference surface, checked as femo_set_layup_reference checks them."""
@@ -331,6 +361,41 @@ class ShellContext:
         out = np.empty(max(n, 0) // 16)
         self._chk(self.lib.femo_ply_strength_index_field(self._h, dptr(out), out.size))
         return out.reshape(self.mesh.nel, -1)
+
+    def set_ply_hashin_table(self, table=None, npt=None):
+        """Strengths of the Hashin outputs "ply_hashin_fibre" / "ply_hashin_matrix" and their fields (femo_set_ply_hashin_table;
+        laminate mode): ``table`` is (nel, npt, 6) values [Xt, Xc, Yt, Yc, SL, ST] in solver cell order, all finite and > 0 (the
+        array of ``laminate.hashin_table``), or (npt, 6) / (6,) for the same strengths in every cell (``npt`` then defaults to the ply
+        table's), or flat with ``npt`` given; ``None`` removes it.  The recovery points are those of the ply table, whose G and z
+        the outputs read.  The factor is kept."""
+        if table is None:
+            self._chk(self.lib.femo_set_ply_hashin_table(self._h, None, 0, 0))
+            return
+        a = np.asarray(table, dtype=np.float64)
+        nel = self.mesh.nel
+        if a.ndim == 1 and a.size == 6:
+            if npt is None:
+                npt = max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // (16 * nel)
+            if npt < 1:
+                raise ValueError("set_ply_hashin_table: (6,) strengths need a ply table to take npt from, or npt")
+            a = np.broadcast_to(a, (nel, int(npt), 6))
+        elif a.ndim == 2 and a.shape[1] == 6 and (npt is None or a.shape[0] == npt):
+            npt = a.shape[0]
+            a = np.broadcast_to(a, (nel, npt, 6))
+        elif npt is None:
+            if a.ndim != 3:
+                raise ValueError("set_ply_hashin_table: a (nel, npt, 6), (npt, 6) or (6,) array, or npt")
+            npt = a.shape[1]
+        v = self._vec(a)
+        self._chk(self.lib.femo_set_ply_hashin_table(self._h, dptr(v), int(npt), v.size))
+
+    def ply_hashin_field(self):
+        """(fibre, matrix), each (nel, npt): the Hashin fibre and matrix failure indices, the largest over the cell's quadrature points
+        per recovery point, from one pass (femo_ply_hashin_field)."""
+        n = max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // 16
+        ff, fm = np.empty(n), np.empty(n)
+        self._chk(self.lib.femo_ply_hashin_field(self._h, dptr(ff), dptr(fm), n))
+        return ff.reshape(self.mesh.nel, -1), fm.reshape(self.mesh.nel, -1)
 
     def set_ply_shear_table(self, table=None, npt=None):
         """Recovery points of the interlaminar shear outputs (femo_set_ply_shear_table; laminate mode): ``table`` is the
@@ -785,7 +850,8 @@ class ShellContext:
         ``field_size_of(name)`` entries (nvc * nel for the DG1 stress fields; nel * npt, cell-major like
         ``ply_failure_field().ravel()``, for 'ply_failure_field'), or several as rows of a 2-D array (the result has the same number
         of rows).  Points of zero stress contribute zero (a subgradient); an entry of the ply failure field is differentiated at
-        its first maximiser, the branch the forward mode takes.  'ply_failure_field' and 'ply_strength_index_field' also take wrt
+        its first maximiser, the branch the forward mode takes.  'ply_failure_field', 'ply_strength_index_field' and the Hashin
+        fields 'ply_hashin_fibre_field' / 'ply_hashin_matrix_field' also take wrt
         'ply_table' and, under an active layup, 'ply_thickness' / 'ply_angle'."""
         cb = np.ascontiguousarray(cbar, dtype=np.float64)
         one = cb.ndim == 1
@@ -813,7 +879,7 @@ class ShellContext:
     def field_total_gradients(self, name, cbars, arg):
         """Total derivatives d (cbar_k . field) / d arg through the solved state for the rows cbar_k of ``cbars`` -- one grouped
         adjoint solve (femo_field_total_gradients).  Returns (gradients (nbar, n), iterations, relative residuals).  A row has
-        ``field_size_of(name)`` entries.  'ply_failure_field' (and 'ply_strength_index_field' likewise) takes arg 'laminate', 'ply_table', 'F_solid', 'thickness', 'E', 'nu',
+        ``field_size_of(name)`` entries.  'ply_failure_field' (and 'ply_strength_index_field' and the Hashin fields likewise) takes arg 'laminate', 'ply_table', 'F_solid', 'thickness', 'E', 'nu',
         'density' (no solve runs where the residual does not depend on the argument: iterations 0) and, under an active layup,
         'ply_thickness' / 'ply_angle', composed on the device: k local failure constraints cost ceil(k / 4) grouped solves."""
         cb = self._cotangent_rows(name, np.ascontiguousarray(cbars, dtype=np.float64))
@@ -838,8 +904,9 @@ class ShellContext:
 
     def field_size_of(self, name):
         """Entries of the field output ``name``: nvc * nel for the DG1 stress fields, nel * npt for 'ply_failure_field',
-        'ply_strength_index_field' and 'ply_shear_failure_field' (the recovery points of their own tables)."""
-        if name in ("ply_failure_field", "ply_strength_index_field"):
+        'ply_strength_index_field', 'ply_hashin_fibre_field', 'ply_hashin_matrix_field' and 'ply_shear_failure_field' (the recovery
+        points of their own tables)."""
+        if name in ("ply_failure_field", "ply_strength_index_field", "ply_hashin_fibre_field", "ply_hashin_matrix_field"):
             return max(int(self.lib.femo_field_size(self._h, b"ply_table")), 0) // 16
         if name == "ply_shear_failure_field":
             return max(int(self.lib.femo_field_size(self._h, b"ply_shear_table")), 0) // 6

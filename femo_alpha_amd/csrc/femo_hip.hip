@@ -15,6 +15,7 @@
 #include "field_jvp.h"
 #include "ply_field_rev.h"
 #include "ply_strength.h"
+#include "ply_hashin.h"
 #include "layup.h"
 #include "layup_mass.h"
 #include "disp_aggregate.h"
@@ -41,7 +42,7 @@ constexpr int WIDE_NP_DEFAULT = 512;    // option "wide_np" overrides it for the
 constexpr int WIDE_CNT_DEFAULT = 512;   // option "wide_cnt": levels with at most this many fronts also take the wide (many workgroups per
                                         // front) solve kernels -- one workgroup per front cannot pull a level's factor out of HBM
 
-#define FEMO_VERSION 103
+#define FEMO_VERSION 104
 
 static std::string g_create_error;
 
@@ -152,6 +153,16 @@ struct femo_ctx {
         DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_strength_dtable")
         DevBuf<int> first;          // k_ply_psd_check: the first offending recovery point
     } pst;
+    // Hashin fibre and matrix indices (femo_set_ply_hashin_table; ply_hashin.h; laminate mode only): G and z are the ply table's, the
+    // six strengths per recovery point a table of their own; slots and results per index, so that a call never disturbs the others
+    struct PlyHashin {
+        int npt = 0;                // 0: no strengths table
+        DevBuf<double> tab;         // cell-major (nel, npt, 6), as the caller gave it
+        DevBuf<double> tabT;        // entry-major [6 p + k][nel]: what the kernels read
+        DevBuf<double> part[2], res[2];   // per index (fibre, matrix): block slots; { shift S, reference area, K, alpha } of k_ply_combine
+        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_hashin_*_dtable")
+        DevBuf<int> first;          // k_hashin_check: the first offending entry
+    } ph;
     // layup mode (femo_set_layup; layup.h): the laminate and the ply table are built on the device from ply thicknesses and angles
     struct Layup {
         bool active = false;
@@ -670,6 +681,13 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_PSI_FIELD , PSI_FIELD
 #define COMMA_PSI_DW , PSI_DW
 #define COMMA_PSI_DTABLE , PSI_DTABLE
+#define COMMA_PH_VALUE_F , PH_VALUE, PH_FIBRE
+#define COMMA_PH_VALUE_M , PH_VALUE, PH_MATRIX
+#define COMMA_PH_FIELD , PH_FIELD, PH_FIBRE
+#define COMMA_PH_DW_F , PH_DW, PH_FIBRE
+#define COMMA_PH_DW_M , PH_DW, PH_MATRIX
+#define COMMA_PH_DTABLE_F , PH_DTABLE, PH_FIBRE
+#define COMMA_PH_DTABLE_M , PH_DTABLE, PH_MATRIX
 
 static const int EB = 128;   // element kernels: threads per block (one element per thread)
 
@@ -2309,6 +2327,7 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
             c->clt_sym.reset();
             c->ply = femo_ctx::Ply();                          // the recovery points belong to the laminate
             c->pst.psd_ok = false;
+            c->ph = femo_ctx::PlyHashin();
             c->psh = femo_ctx::PlyShear();
             c->lay = femo_ctx::Layup();                        // ... and so does the layup
             operator_changed(c);
@@ -2479,6 +2498,57 @@ int femo_set_ply_shear_params(femo_ctx* c, double rho) {
     return 0;
 }
 
+// strengths of the Hashin outputs (ply_hashin.h): (nel, npt, 6) cell-major; they are checked on the device once, here
+int femo_set_ply_hashin_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!table && n == 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ph = femo_ctx::PlyHashin();
+        return 0;
+    }
+    char buf[280];
+    if (!c->laminate) return fail(c, "ply hashin table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
+    if (npt < 1 || npt > PLY_MAX) {
+        snprintf(buf, sizeof buf, "ply hashin table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
+        return fail(c, buf);
+    }
+    const int64_t len = (int64_t)HSH_W * npt * c->nel;
+    if (!table || n != len) {
+        snprintf(buf, sizeof buf, "ply hashin table: expected %d values per recovery point [Xt, Xc, Yt, Yc, SL, ST] x %d points x %d cells = %lld, "
+                                  "got %lld%s", HSH_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
+        return fail(c, buf);
+    }
+    if (len > INT32_MAX) return fail(c, "ply hashin table: more than 2^31 - 1 values");
+    // the candidate passes the device check before the table the context holds is touched
+    DevBuf<double> cand;
+    int first = INT32_MAX;
+    HIPCHK(c, cand.alloc((size_t)len));
+    HIPCHK(c, c->ph.first.grow(1));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(cand, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ph.first, &first, sizeof first, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_hashin_check, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)cand, (long long)len, c->ph.first.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&first, c->ph.first, sizeof first, hipMemcpyDeviceToHost));
+    if (first != INT32_MAX) {
+        static const char* const names[HSH_W] = {"Xt", "Xc", "Yt", "Yc", "SL", "ST"};
+        const int64_t per = (int64_t)HSH_W * npt, e = first / per, r = first - e * per;
+        snprintf(buf, sizeof buf, "ply hashin table: value %d (the strength %s) of recovery point %d of cell %lld is not finite and > 0", (int)(r % HSH_W),
+                 names[r % HSH_W], (int)(r / HSH_W), (long long)e);
+        return fail(c, buf);
+    }
+    HIPCHK(c, c->ph.tab.grow((size_t)len));
+    HIPCHK(c, c->ph.tabT.grow((size_t)len));
+    HIPCHK(c, hipMemcpy(c->ph.tab, cand, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice));
+    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ph.tab, c->ph.tabT.get(), c->nel,
+                       (int)(HSH_W * npt));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ph.npt = npt;
+    return 0;                                                  // the operator does not see the strengths: factor and Jacobi diagonal stay
+}
+
 // ---- layups (layup.h): the laminate and the ply table built on the device from ply thicknesses and angles
 // 0: not a layup argument (or no layup is active); 1: "ply_thickness"; 2: "ply_angle"
 static int layup_wrt(const femo_ctx* c, const std::string& s) {
@@ -2647,6 +2717,7 @@ int femo_set_layup(femo_ctx* c, int32_t nply, const double* plies, int32_t surfa
         c->psh = femo_ctx::PlyShear();
         c->psh.rho = rho;
     }
+    if (c->ph.npt && c->ph.npt != npt) c->ph = femo_ctx::PlyHashin();   // ... and the Hashin strengths, with the recovery points
     lay.nply = nply; lay.surfaces = surfaces; lay.npt = npt; lay.c_drill = c_drill;
     lay.active = true;
     c->pst.psd_ok = false;                                 // new strength coefficients: the strength index checks them when first asked for
@@ -3355,6 +3426,97 @@ static int strength_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, do
     return ply_gather_sum(c, out);
 }
 
+// ---- Hashin fibre and matrix indices (ply_hashin.h): G and z of the ply failure's table, strengths of their own; eslot and gather
+// are the ply failure's, the slots and the results their own per index
+// PH_FIBRE, PH_MATRIX, or -1
+static int hashin_name(const std::string& fn) { return fn == "ply_hashin_fibre" ? PH_FIBRE : fn == "ply_hashin_matrix" ? PH_MATRIX : -1; }
+static int hashin_field_name(const std::string& fn) {
+    return fn == "ply_hashin_fibre_field" ? PH_FIBRE : fn == "ply_hashin_matrix_field" ? PH_MATRIX : -1;
+}
+static const char* const HASHIN_NAMES[2] = {"ply_hashin_fibre", "ply_hashin_matrix"};
+static const char* const HASHIN_FIELD_NAMES[2] = {"ply_hashin_fibre_field", "ply_hashin_matrix_field"};
+
+// both tables, with the same recovery points
+static int hashin_need_table(femo_ctx* c, const char* who) {
+    if (ply_need_table(c, who)) return 2;
+    if (c->ph.npt < 1) return fail(c, std::string(who) + ": no Hashin strengths table is set (femo_set_ply_hashin_table, laminate mode)");
+    if (c->ph.npt != c->ply.npt) {
+        char buf[240];
+        snprintf(buf, sizeof buf, "%s: the Hashin strengths table has %d recovery points per cell, the ply table %d", who, c->ph.npt, c->ply.npt);
+        return fail(c, buf);
+    }
+    return 0;
+}
+
+// the refusals every derivative entry point makes for the aggregates before it does anything else
+static int hashin_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
+    const int idx = hashin_name(fn);
+    if (idx < 0) return 0;
+    if (int rc = hashin_need_table(c, HASHIN_NAMES[idx])) return rc;
+    if (arg == "uhat") return fail(c, fn + ": the shape derivative (uhat) of this output is not provided");
+    return 0;
+}
+
+// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
+static int hashin_value_launch(femo_ctx* c, int idx) {
+    auto& ph = c->ph;
+    const int g = nblk(c->nel, PLY_BLOCK);
+    HIPCHK(c, ph.part[idx].grow((size_t)3 * g));
+    HIPCHK(c, ph.res[idx].grow(4));
+#define HASHIN_VALUE_ARGS mesh_dev(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT, (const double*)ph.tabT, c->ply.npt, c->ply.rho, \
+                          (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ph.part[idx].get(), (double*)nullptr
+    if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_F, g, PLY_BLOCK, HASHIN_VALUE_ARGS);
+    else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_M, g, PLY_BLOCK, HASHIN_VALUE_ARGS);
+#undef HASHIN_VALUE_ARGS
+    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ph.part[idx], stress_alpha_ref(c), c->ply.npt, c->ply.rho,
+                       ph.res[idx].get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
+static int hashin_value_dev(femo_ctx* c, int idx, double out4[4]) {
+    if (int rc = hashin_need_table(c, HASHIN_NAMES[idx])) return rc;
+    if (hashin_value_launch(c, idx)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->ph.res[idx], 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
+    if (!std::isfinite(out4[2])) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a non-finite state or "
+                                  "failure index", HASHIN_NAMES[idx], out4[0], out4[3], c->ply.rho);
+        return fail(c, msg);
+    }
+    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
+    return 0;
+}
+
+// (d / d w) into out (ndof) or (d / d table) into out (16 npt nel, cell-major).  cbar null: of the aggregate K over the selected
+// sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
+static int hashin_grad_dev(femo_ctx* c, int idx, bool wrt_state, const double* cbar, double* out) {
+    auto& ph = c->ph;
+    if (!cbar && hashin_value_launch(c, idx)) return 1;
+    const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+#define HASHIN_GRAD_ARGS m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, (const double*)ph.tabT, c->ply.npt, c->ply.rho, \
+                         (const double*)c->w, (const double*)ph.res[idx], cbar, eslot, dst, (double*)nullptr
+    const int* eslot = nullptr;
+    double* dst = out;
+    if (!wrt_state) {
+        if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_F, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
+        else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_M, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    if (int rc = ply_eslot(c)) return rc;
+    eslot = c->ply.eslot;
+    dst = c->ybuf;
+    if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_F, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
+    else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_M, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
+#undef HASHIN_GRAD_ARGS
+    return ply_gather_sum(c, out);
+}
+
 // ---- mass and volume from the layup (layup_mass.h): outputs of the layup itself, not of the laminate, and independent of the state
 static bool layup_mass_name(const femo_ctx* c, const std::string& fn) {
     return c->lay.active && (fn == "layup_mass" || fn == "layup_volume");
@@ -3590,6 +3752,12 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         *value = v[2];
         return 0;
     }
+    if (const int idx = hashin_name(s); idx >= 0) {
+        double v[4];
+        if (int rc = hashin_value_dev(c, idx, v)) return rc;
+        *value = v[2];
+        return 0;
+    }
     if (const int slot = disp_agg_slot(s); slot >= 0) {
         double v[4];
         if (int rc = disp_agg_value_dev(c, s, slot, v)) return rc;
@@ -3698,6 +3866,12 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
     if (strength_name(fn)) {
         if (int rc = strength_gate(c, fn, wrt)) return rc;
         if (wrt == "disp_solid" || wrt == "ply_table") return strength_grad_dev(c, wrt == "disp_solid", nullptr, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;                                             // laminate, thickness, E, nu, density, F_solid, ply_shear_table: no explicit dependence
+    }
+    if (const int idx = hashin_name(fn); idx >= 0) {
+        if (int rc = hashin_gate(c, fn, wrt)) return rc;
+        if (wrt == "disp_solid" || wrt == "ply_table") return hashin_grad_dev(c, idx, wrt == "disp_solid", nullptr, out);
         HIPCHK(c, hipGetLastError());
         return 0;                                             // laminate, thickness, E, nu, density, F_solid, ply_shear_table: no explicit dependence
     }
@@ -3811,6 +3985,7 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
     }
     if (int rc = shear_gate(c, fn, a)) return rc;
     if (int rc = strength_gate(c, fn, a)) return rc;
+    if (int rc = hashin_gate(c, fn, a)) return rc;
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     if (layup_mass_name(c, fn)) {                                           // no state dependence: lambda = 0, the total is the partial
@@ -3932,6 +4107,8 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
         if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     for (int i = 0; i < nfun; ++i)
         if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = hashin_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
@@ -4170,6 +4347,8 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
         if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     for (int i = 0; i < nfun; ++i)
         if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    for (int i = 0; i < nfun; ++i)
+        if (int rc = hashin_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     const int keep_sel = c->csel;
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
@@ -5999,6 +6178,67 @@ int femo_ply_strength_index_field(femo_ctx* c, double* out, int64_t n) {
     return 0;
 }
 
+// ---- the Hashin fields (ply_hashin.h) and their reverse mode (the gradient modes with a cotangent in place of the KS weight, at the
+// first maximiser), under the names "ply_hashin_fibre_field" and "ply_hashin_matrix_field".  Forward mode and the sparse Jacobian are
+// not provided.
+static int hashin_field_not_provided(femo_ctx* c, int idx, const char* who) {
+    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of '" + HASHIN_FIELD_NAMES[idx] + "' are not provided "
+                                      "(femo_field_output_vjp, femo_field_total_gradients)");
+}
+
+static int hashin_fibre_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return hashin_grad_dev(c, PH_FIBRE, !table, cbar, out); }
+static int hashin_matrix_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return hashin_grad_dev(c, PH_MATRIX, !table, cbar, out); }
+
+// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
+// the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
+static int hashin_field_arg_vjp_dev(femo_ctx* c, int idx, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    if (wrt == "disp_solid" || wrt == "ply_table") return hashin_grad_dev(c, idx, wrt == "disp_solid", cbar, out);
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    HIPCHK(c, hipGetLastError());
+    if (!lw) return 0;
+    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
+    if (int rc = hashin_grad_dev(c, idx, false, cbar, c->lay.tbar)) return rc;
+    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
+}
+static int hashin_fibre_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    return hashin_field_arg_vjp_dev(c, PH_FIBRE, wrt, lw, cbar, out, n);
+}
+static int hashin_matrix_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    return hashin_field_arg_vjp_dev(c, PH_MATRIX, wrt, lw, cbar, out, n);
+}
+
+static int hashin_field_output_vjp(femo_ctx* c, int idx, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    return point_field_output_vjp(c, HASHIN_FIELD_NAMES[idx], hashin_need_table, &c->ply.npt,
+                                  idx == PH_FIBRE ? hashin_fibre_field_arg_vjp_dev : hashin_matrix_field_arg_vjp_dev, a, cbar, nbar, out, n);
+}
+
+static int hashin_field_total_gradients(femo_ctx* c, int idx, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n,
+                                        int32_t* iters, double* relres) {
+    return ply_table_field_total_gradients(c, HASHIN_FIELD_NAMES[idx], hashin_need_table,
+                                           idx == PH_FIBRE ? hashin_fibre_field_vjp_dev : hashin_matrix_field_vjp_dev,
+                                           idx == PH_FIBRE ? hashin_fibre_field_arg_vjp_dev : hashin_matrix_field_arg_vjp_dev, nbar, cbar, a,
+                                           out, n, iters, relres);
+}
+
+// both fields in one pass over the strains; either pointer may be null
+int femo_ply_hashin_field(femo_ctx* c, double* fibre, double* matrix, int64_t n) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = hashin_need_table(c, "femo_ply_hashin_field")) return rc;
+    const int64_t len = (int64_t)c->nel * c->ply.npt;
+    if (n != len) return fail(c, "femo_ply_hashin_field: the fields have nel * npt entries");
+    if (!fibre && !matrix) return 0;
+    DevBuf<double> d;
+    HIPCHK(c, d.alloc((size_t)2 * len));
+    ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
+                (const double*)c->ph.tabT, c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr,
+                (const int*)nullptr, fibre ? d.get() : (double*)nullptr, matrix ? d.get() + len : (double*)nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (fibre) HIPCHK(c, hipMemcpy(fibre, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    if (matrix) HIPCHK(c, hipMemcpy(matrix, d.get() + len, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- reverse mode of the interlaminar shear field (ply_shear.h: the gradient modes with a cotangent in place of the KS weight), under
 // the name "ply_shear_failure_field".  Forward mode and the sparse Jacobian are not provided.
 static int shear_field_not_provided(femo_ctx* c, const char* who) {
@@ -6084,6 +6324,7 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
     double zf;
     if (fname == "ply_shear_failure_field") return shear_field_output_vjp(c, a, cbar, nbar, out, n);
     if (fname == "ply_strength_index_field") return strength_field_output_vjp(c, a, cbar, nbar, out, n);
+    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_output_vjp(c, idx, a, cbar, nbar, out, n);
     if (fname == "ply_failure_field") return ply_field_output_vjp(c, a, cbar, nbar, out, n);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
@@ -6106,6 +6347,7 @@ int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wr
     if (fname == "ply_failure_field") return ply_field_jacobian_nnz(c, a, nnz);
     if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
     if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
+    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_not_provided(c, idx, "femo_field_output_jacobian");
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
@@ -6122,6 +6364,7 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     if (fname == "ply_failure_field") return ply_field_jacobian(c, a, rowptr, colidx, vals, nnz);
     if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
     if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
+    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_not_provided(c, idx, "femo_field_output_jacobian");
     if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
@@ -6160,6 +6403,7 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     if (fname == "ply_failure_field") return ply_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
     if (fname == "ply_shear_failure_field") return shear_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
     if (fname == "ply_strength_index_field") return strength_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
+    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_total_gradients(c, idx, nbar, cbar, a, out, n, iters, relres);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
@@ -6195,6 +6439,7 @@ static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
     if (field_zf(name, &zf)) return (int64_t)c->nvc * c->nel;
     if (name == "ply_shear_failure_field") { shear_field_not_provided(c, "forward mode"); return -1; }
     if (name == "ply_strength_index_field") { strength_field_not_provided(c, "forward mode"); return -1; }
+    if (const int idx = hashin_field_name(name); idx >= 0) { hashin_field_not_provided(c, idx, "forward mode"); return -1; }
     if (name != "ply_failure_field") { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
     if (ply_need_table(c, "ply_failure_field")) return -2;
     return (int64_t)c->nel * c->ply.npt;
@@ -6420,6 +6665,18 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             if (s == "ply_strength_dw") return strength_grad_dev(c, true, nullptr, c->tmp);
             HIPCHK(c, c->pst.gtab.grow((size_t)PLY_W * c->ply.npt * c->nel));
             return s == "ply_dtable" ? ply_grad_dev(c, false, c->pst.gtab) : strength_grad_dev(c, false, nullptr, c->pst.gtab);
+        }
+        // Hashin indices: the passes of the strength index above, per index ("ply_hashin_fibre_value", "ply_hashin_matrix_dw", ...)
+        for (int idx = 0; idx < 2; ++idx) {
+            const std::string base = HASHIN_NAMES[idx];
+            if (s.rfind(base + "_", 0) != 0) continue;
+            const std::string pass = s.substr(base.size() + 1);
+            if (pass != "value" && pass != "dw" && pass != "dtable") continue;
+            if (int rc = hashin_need_table(c, "femo_bench_kernel")) return rc;
+            if (pass == "value") return hashin_value_launch(c, idx);
+            if (pass == "dw") return hashin_grad_dev(c, idx, true, nullptr, c->tmp);
+            HIPCHK(c, c->ph.gtab.grow((size_t)PLY_W * c->ply.npt * c->nel));
+            return hashin_grad_dev(c, idx, false, nullptr, c->ph.gtab);
         }
         return fail(c, "unknown kernel '" + s + "'");
     };

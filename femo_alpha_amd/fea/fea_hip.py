@@ -111,7 +111,7 @@ class _SubFunction:
 
 class Form:
     """Scalar output known to the backend: 'compliance', 'mass', 'elastic_energy', 'pnorm_stress', 'volume', 'ply_failure',
-    'ply_strength_index', 'ply_shear_failure', and in layup mode 'layup_mass' and 'layup_volume', and the max-displacement aggregates 'max_disp', 'max_disp1', 'max_disp2', 'max_disp3'.
+    'ply_strength_index', 'ply_hashin_fibre', 'ply_hashin_matrix', 'ply_shear_failure', and in layup mode 'layup_mass' and 'layup_volume', and the max-displacement aggregates 'max_disp', 'max_disp1', 'max_disp2', 'max_disp3'.
     ``subdomain`` restricts the stress aggregate to one tagged set of cells (the reference's ``dxx(i)`` measure)."""
 
     def __init__(self, ctx, name, subdomain=-1, stress_params=None, disp_params=None):
@@ -145,7 +145,8 @@ class Form:
 
 class FieldForm:
     """Field output known to the backend: 'stress' (top-surface von Mises, projected onto DG1), 'stress_mid', 'stress_bot', and in
-    laminate mode with a ply table 'ply_failure_field' ((nel, npt) flattened), 'ply_strength_index_field' and with a shear table 'ply_shear_failure_field' (likewise; reverse
+    laminate mode with a ply table 'ply_failure_field' ((nel, npt) flattened), 'ply_strength_index_field', with Hashin strengths
+    'ply_hashin_fibre_field' / 'ply_hashin_matrix_field', and with a shear table 'ply_shear_failure_field' (likewise; reverse
     mode only: ``computeMatVecProductBwd`` and ``FEA.field_gradients``).  ``assemble(computePartials(field_form, f), dim=2)``
     is the sparse partial Jacobian of any of them (for the ply failure field with respect to the state and the ply table);
     ``computeMatVecProductFwd(computePartials(field_form, f), v)`` is the matrix-free tangent and
@@ -405,7 +406,8 @@ class FEA:
         ``field_tangents``: row k is d (cbars[k] . field) / d arg through the solved state, ceil(k / 4) grouped adjoint solves for k
         cotangents (femo_field_total_gradients on the context of the state's residual).  Nothing is pushed: the inputs and the state
         are the ones the context holds.  ``name``: a registered field output or one of the backend's own names ('stress',
-        'stress_mid', 'stress_bot', 'ply_failure_field', 'ply_strength_index_field', 'ply_shear_failure_field').  ``cbars`` (one cotangent, or several as rows; cell-major like the field)
+        'stress_mid', 'stress_bot', 'ply_failure_field', 'ply_strength_index_field', 'ply_hashin_fibre_field',
+        'ply_hashin_matrix_field', 'ply_shear_failure_field').  ``cbars`` (one cotangent, or several as rows; cell-major like the field)
         and the gradients are in caller order when the model was renumbered."""
         ctx = self.states_dict[state]["residual_form"].ctx
         fn = self.outputs_field_dict[name]["form"].name if name in self.outputs_field_dict else name

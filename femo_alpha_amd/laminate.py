@@ -28,6 +28,7 @@ K_SHEAR = 0.833          # linear_shell_model.py:146
 LAM_W = 32               # [A (9), B (9), D (9), A_s (4), c_drill] per cell
 PLY_W = 16               # [G (9), z, F1, F2, F11, F22, F66, F12] per recovery point (femo_set_ply_table)
 PSH_W = 6                # [Gs (4), F55, F44] per recovery point (femo_set_ply_shear_table)
+HSH_W = 6                # [Xt, Xc, Yt, Yc, SL, ST] per recovery point (femo_set_ply_hashin_table)
 
 
 def _t_eps(theta_deg):
@@ -225,6 +226,37 @@ def ply_table(E1, E2, G12, nu12, t, theta, strengths, surfaces=("bot", "top"), j
         dz[:, s, :] = a * dzi[:-1] + b * dzi[1:]
     out = out.reshape(nel, nply * ns, PLY_W)
     return (out, dz.reshape(nply * ns, nply)) if jacobian else out
+
+
+def hashin_strengths(Xt, Xc, Yt, Yc, SL, ST=None):
+    """The six strengths [Xt, Xc, Yt, Yc, SL, ST] of the Hashin fibre and matrix failure indices (femo_set_ply_hashin_table), all
+    positive: tension / compression along and across the fibres, the longitudinal (in-plane) and the transverse shear strength.
+    ``ST=None`` takes Yc / 2, for which the matrix index has no kink at s2 = 0.  Arguments broadcast; the strengths are the last
+    axis.
+        fibre   (s1/Xt)^2 for s1 >= 0, (s1/Xc)^2 for s1 < 0
+        matrix  (s2/Yt)^2 + (t12/SL)^2 for s2 >= 0, (s2/(2 ST))^2 + ((Yc/(2 ST))^2 - 1) s2/Yc + (t12/SL)^2 for s2 < 0"""
+    Yc = np.asarray(Yc, dtype=np.float64)
+    vals = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (Xt, Xc, Yt, Yc, SL, 0.5 * Yc if ST is None else ST)))
+    out = np.stack(vals, axis=-1)
+    if not (np.all(np.isfinite(out)) and np.all(out > 0)):
+        raise ValueError("hashin_strengths: the strengths must be finite and > 0")
+    return out
+
+
+def hashin_table(strengths, nel, nply=None, surfaces=("bot", "top")):
+    """The strengths table of femo_set_ply_hashin_table, (nel, npt, 6), in the point order of ``ply_table``: ply by ply from the
+    bottom, inside a ply the ``surfaces`` as listed.  ``strengths``: the array of ``hashin_strengths``, (6,), (nply, 6) or
+    (nel, nply, 6); ``nply`` is needed with (6,) alone.  The strengths depend on neither thickness nor angle."""
+    s = np.asarray(strengths, dtype=np.float64)
+    if s.shape[-1] != HSH_W:
+        raise ValueError(f"hashin_table: [Xt, Xc, Yt, Yc, SL, ST] on the last axis, got shape {s.shape}")
+    if s.ndim == 1:
+        if nply is None:
+            raise ValueError("hashin_table: (6,) strengths need nply")
+        s = s[None, :]
+    nply = s.shape[-2] if nply is None else int(nply)
+    s = np.broadcast_to(s, (int(nel), nply, HSH_W))
+    return np.ascontiguousarray(np.repeat(s, len(surfaces), axis=1))
 
 
 def shear_strength(S13, S23):

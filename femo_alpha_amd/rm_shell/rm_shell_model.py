@@ -68,7 +68,7 @@ class RMShellModel:
     def __init__(self, mesh: ShellMesh, shell_bc_func: callable = None, element_wise_material=False, rho=100,
                  PENALTY_BC=True, additional_outputs=None, mesh_tags=None, record=True, elementwise_pressure=False,
                  device=0, renumber=False, nquad=None, laminate=False, ply_failure=None, layup=None, max_disp=None,
-                 ply_strength=False):
+                 ply_strength=False, hashin=False):
         # caller order <-> solver order.  dolfinx reorders every mesh it is given and the reference carries the maps
         # (rm_shell_model.py:116, 396-438, 505-527); with renumber=True this build does the same with a Morton order of
         # the cells (ShellMesh.renumbered): inputs are gathered into solver order, nodal displacements come back in
@@ -138,6 +138,23 @@ class RMShellModel:
             raise ValueError("ply_strength needs a ply table: ply_failure=npt or a layup")
         if self.ply_strength and layup is not None and not len(tuple(layup.get("surfaces", ("bot", "top")))):
             raise ValueError("ply_strength needs a ply table: this layup has no recovery points (surfaces)")
+        # hashin (opt-in; with laminate=True and a ply table): the outputs "ply_hashin_fibre" and "ply_hashin_matrix", the KS
+        # aggregates of the Hashin fibre and matrix failure indices, beside "ply_failure" and with its arguments.  The strengths
+        # [Xt, Xc, Yt, Yc, SL, ST] are the same in every cell: with a layup hashin=True reads them from the layup's "hashin" key or
+        # from its ply dicts (Xt, Xc, Yt, Yc, S, optionally ST), and hashin=(nply, 6) | (6,) | ply dicts gives them here; with
+        # ply_failure=npt hashin=(npt, 6) | (6,).  Strengths that vary over the cells go to ShellContext.set_ply_hashin_table.
+        self.hashin = None if hashin is None or hashin is False else hashin
+        if self.hashin is not None:
+            if not self.laminate:
+                raise ValueError("hashin needs laminate=True")
+            if self.ply_failure is None and layup is None:
+                raise ValueError("hashin needs a ply table: ply_failure=npt or a layup")
+            if layup is not None and not len(tuple(layup.get("surfaces", ("bot", "top")))):
+                raise ValueError("hashin needs a ply table: this layup has no recovery points (surfaces)")
+            if self.hashin is not True and np.ndim(self.hashin) > 2:
+                raise ValueError("hashin: strengths per ply or per recovery point, the same in every cell")
+            if self.hashin is True and layup is None:
+                raise ValueError("hashin=True reads the strengths of a layup; with ply_failure=npt give hashin=[Xt, Xc, Yt, Yc, SL, ST]")
         self.max_disp = None
         if max_disp is not None:
             specs = [dict(max_disp)] if isinstance(max_disp, dict) else [dict(d) for d in max_disp]
@@ -200,7 +217,7 @@ class RMShellModel:
         shell_pde = self.shell_pde = RMShellPDE(mesh, element_wise_material=self.element_wise_material,
                                                 elementwise_pressure=self.elementwise_pressure, device=self.device,
                                                 nquad=self._nquad_arg, laminate=self.laminate, ply_failure=self.ply_failure,
-                                                layup=self.layup)
+                                                layup=self.layup, hashin=self.hashin)
         fea = FEA(mesh)
         if self.caller_mesh is not mesh:                 # renumbered: FEA.field_tangents answers in caller order
             fea.vertex_of_new, fea.cell_of_new = self.vertex_of_new, self.cell_of_new
@@ -253,6 +270,10 @@ class RMShellModel:
         if self.layup is not None and shell_pde.ply_npt and self.ply_strength:
             fea.add_output(name="ply_strength_index", form=shell_pde.ply_strength_index(w, uhat, None, rho=self.rho),
                            arguments=["disp_solid"] + lam_args)
+        if self.layup is not None and shell_pde.ply_npt and self.hashin is not None:
+            for mode in ("fibre", "matrix"):
+                fea.add_output(name="ply_hashin_" + mode, form=shell_pde.ply_hashin(w, uhat, None, mode, rho=self.rho),
+                               arguments=["disp_solid"] + lam_args)
         if self.layup is not None and shell_pde.layup_shear:
             # shear_strength=[...] in the layup: the interlaminar shear aggregate, with the arguments ply_failure has on this route
             fea.add_output(name="ply_shear_failure", form=shell_pde.ply_shear_failure(w, uhat, None, rho=self.rho),
@@ -268,6 +289,10 @@ class RMShellModel:
             if self.ply_strength:
                 fea.add_output(name="ply_strength_index", form=shell_pde.ply_strength_index(w, uhat, ply, rho=self.rho),
                                arguments=["disp_solid", "ply_table"])
+            if self.hashin is not None:
+                for mode in ("fibre", "matrix"):
+                    fea.add_output(name="ply_hashin_" + mode, form=shell_pde.ply_hashin(w, uhat, ply, mode, rho=self.rho),
+                                   arguments=["disp_solid", "ply_table"])
         if self.mesh_tags is not None:
             self.set_up_subdomains(self.mesh_tags)
             for tag, i in self.association_table.items():
@@ -294,6 +319,9 @@ class RMShellModel:
             self.ply_failure_field_form = shell_pde.ply_failure_field(w, uhat, ply)
         if self.ply_strength and (self.ply_failure is not None or shell_pde.ply_npt):
             self.ply_strength_index_field_form = shell_pde.ply_strength_index_field(w, uhat, None)
+        if self.hashin is not None:
+            self.ply_hashin_fibre_field_form = shell_pde.ply_hashin_field(w, uhat, None, "fibre")
+            self.ply_hashin_matrix_field_form = shell_pde.ply_hashin_field(w, uhat, None, "matrix")
         self.fea = fea
 
     def evaluate(self, force_vector, thickness, E, nu, density, node_disp=None, debug_mode=False, is_pressure=True, laminate=None,

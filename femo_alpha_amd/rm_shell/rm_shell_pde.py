@@ -23,7 +23,7 @@ class FacetSet:
 
 class RMShellPDE:
     def __init__(self, mesh, element_wise_material=False, elementwise_pressure=False, nquad=None, device=0, solver="direct",
-                 element_type=None, laminate=False, ply_failure=None, layup=None):
+                 element_type=None, laminate=False, ply_failure=None, layup=None, hashin=None):
         # element_type: 'CG2CG1' (what the reference's RMShellPDE hard-codes, rm_shell_pde.py:27) or 'CG1CG1' (the other quadrilateral /
         # triangle choice of ShellElement.setUpFunctionSpace, linear_shell_model.py:74-79); None: the element the mesh object carries
         if element_type is not None and element_type != mesh.element:
@@ -52,6 +52,13 @@ class RMShellPDE:
         # laminate and the ply table are built on the device from ply thicknesses and angles, two DG0 spaces of nply values per cell; the
         # recovery points, hence "ply_failure", follow from the layup's surfaces, "layup_mass" from its (nply,) ply densities, and
         # "ply_shear_failure" from its (nply, 2) transverse shear strengths [S13, S23]
+        # hashin: the strengths [Xt, Xc, Yt, Yc, SL, ST] of the Hashin outputs "ply_hashin_fibre" / "ply_hashin_matrix".  With a layup:
+        # per ply, (nply, 6), (6,), ply dicts, or True for the dicts of the layup's plies (the layup's own "hashin" key does the
+        # same); with ply_failure=npt: (npt, 6) or (6,) for every cell, or (nel, npt, 6) in solver cell order
+        self.hashin = False
+        given = hashin is not None and hashin is not False
+        if given and not self.laminate:
+            raise ValueError("hashin needs laminate=True")
         self.layup = layup
         self.VY = None
         if layup is not None:
@@ -60,9 +67,15 @@ class RMShellPDE:
             t = np.asarray(layup["t"], dtype=np.float64)
             nply = t.shape[-1] if t.ndim else 1
             surfaces = tuple(layup.get("surfaces", ("bot", "top")))
+            strengths = layup.get("hashin")
+            if given and not (hashin is True and strengths is not None):
+                strengths = hashin
+            if strengths is not None and not len(surfaces):
+                raise ValueError("hashin needs a ply table: this layup has no recovery points (surfaces)")
             self.ctx.set_layup(layup["plies"], t, layup["theta"], surfaces, layup.get("c_drill"), density=layup.get("density"),
                                shear_strength=layup.get("shear_strength"), reference=layup.get("reference"),
-                               offset=layup.get("offset"))
+                               offset=layup.get("offset"), hashin=strengths)
+            self.hashin = strengths is not None
             self.layup_density = layup.get("density") is not None
             self.layup_shear = layup.get("shear_strength") is not None
             self.VY = FunctionSpace(self.ctx, "VY", width=nply)
@@ -86,6 +99,11 @@ class RMShellPDE:
             self.VP = FunctionSpace(self.ctx, "VP", width=16 * self.ply_npt)
             self.ply_table_init = np.zeros(self.VP.dim)
             self.ctx.set_ply_table(self.ply_table_init, self.ply_npt)
+        if given:
+            if self.ply_npt is None or hashin is True:
+                raise ValueError("hashin needs a ply table and strengths: a layup, or ply_failure=npt with hashin=[Xt, Xc, Yt, Yc, SL, ST]")
+            self.ctx.set_ply_hashin_table(hashin, npt=None if np.ndim(hashin) < 3 else self.ply_npt)
+            self.hashin = True
 
     # ------------------------------------------------------------------ residual
     def pdeRes(self, h, w, uhat, f, E, nu, penalty=False, dss=None, dSS=None, g=None):
@@ -165,6 +183,24 @@ class RMShellPDE:
         points) as a field form, in reverse mode only: ``computeMatVecProductBwd(computePartials(form, f), cbar)`` and
         ``FEA.field_gradients``."""
         return FieldForm(self.ctx, "ply_strength_index_field")
+
+    def ply_hashin(self, w, uhat, ply_table, mode, dx=None, rho=100.0):
+        """KS aggregate of the Hashin failure index of one ``mode``, "fibre" or "matrix", over the recovery points of the ply table
+        (include/femo_hip.h, "ply_hashin_fibre" / "ply_hashin_matrix"; strengths: ``ShellContext.set_ply_hashin_table`` or the
+        layup's ``hashin``).  ``dx`` as for ``ply_failure``; ``rho`` is the exponent the ply aggregates share
+        (femo_set_ply_failure_params)."""
+        if mode not in ("fibre", "matrix"):
+            raise ValueError(f"ply_hashin: mode 'fibre' or 'matrix', got {mode!r}")
+        self.ctx.set_ply_failure_params(rho)
+        return Form(self.ctx, "ply_hashin_" + mode, subdomain=-1 if dx is None else int(dx))
+
+    def ply_hashin_field(self, w, uhat, ply_table, mode):
+        """The (nel, npt) field of the Hashin index of one ``mode`` per cell and recovery point (its largest value over the cell's
+        quadrature points) as a field form, in reverse mode only: ``computeMatVecProductBwd(computePartials(form, f), cbar)`` and
+        ``FEA.field_gradients``."""
+        if mode not in ("fibre", "matrix"):
+            raise ValueError(f"ply_hashin_field: mode 'fibre' or 'matrix', got {mode!r}")
+        return FieldForm(self.ctx, "ply_hashin_" + mode + "_field")
 
     def ply_shear_failure(self, w, uhat, ply_shear_table, dx=None, rho=100.0):
         """KS aggregate of the interlaminar shear failure index over the recovery points of the shear table (include/femo_hip.h,

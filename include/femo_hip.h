@@ -235,6 +235,42 @@ int femo_set_layup_shear_strength(femo_ctx* ctx, int32_t nply, const double* S);
  * sqrt(FI), the caller's one line); transient laminates; the multi-GPU driver. */
 int femo_ply_strength_index_field(femo_ctx* ctx, double* out, int64_t n);
 
+/* Hashin fibre and matrix failure indices (femo_alpha_amd/csrc/ply_hashin.h) -- new, since FEMO_VERSION 104; the project's own contract
+ * (pinned by tests/ply_hashin_ref.py).  The criteria above are single polynomials on the ply table and cannot tell which mode is
+ * critical; Hashin's (1980) separates fibre from matrix failure and switches its formula on the sign of a stress component, which no
+ * table of quadratic forms can express.  With sigma = (s1, s2, t12) = G (eps - z kappa) of "ply_failure" (entries 0..9 of the ply
+ * table of femo_set_ply_table or of the layup; entries 10..15 are not read) and six strengths [Xt, Xc, Yt, Yc, SL, ST] per (cell,
+ * recovery point), all finite and > 0:
+ *     fibre   FI_f = (s1/Xt)^2                              s1 >= 0        FI_f = (s1/Xc)^2                          s1 < 0
+ *     matrix  FI_m = (s2/Yt)^2 + (t12/SL)^2                 s2 >= 0        FI_m = (s2/(2 ST))^2 + c1 s2 + (t12/SL)^2   s2 < 0,
+ *     c1 = ((Yc/(2 ST))^2 - 1)/Yc.
+ * Hashin's shear term in fibre tension (his alpha) is taken as 0: FI_f is C1 and sqrt(FI_f) is proportional to the load.  FI_m is
+ * continuous with a derivative kink at s2 = 0 unless ST = Yc/2, may be negative, and is differentiated on the branch of the sign;
+ * s1 = 0 and s2 = 0 take the tension branch; a NaN passes through.
+ *   - femo_set_ply_hashin_table: table is (nel, npt, 6) cell-major in solver cell order; NULL with n = 0 removes it.  Laminate mode
+ *     only; the factor is kept.  The strengths are checked on the device once per upload; a refusal names the entry, the recovery
+ *     point and the cell, and the table the context held stays.  npt must equal the ply table's when an output is asked for.  Leaving
+ *     laminate mode, and a femo_set_layup with another number of recovery points, drop the table.
+ *   - functionals "ply_hashin_fibre" and "ply_hashin_matrix" (femo_functional, femo_dfunctional, femo_total_gradient(s) with the
+ *     sub-domain list, femo_total_jvp), over the selected sub-domain:
+ *         K = 1/rho log( 1/(alpha npt) sum_e sum_q wj_eq sum_p exp(rho FI_eqp) )
+ *     with the wj, alpha and rho of "ply_failure" (femo_set_ply_failure_params).  femo_dfunctional: wrt "disp_solid" and "ply_table"
+ *     from the kernels (columns 10..15 of the table gradient are exact zeros; zeros outside the selection); exact zeros for
+ *     "laminate", "thickness", "E", "nu", "density", "F_solid", "ply_shear_table"; "ply_thickness" / "ply_angle" through the layup's
+ *     pull-back; "uhat" is refused: the shape derivative of these outputs is not provided;
+ *   - fields femo_ply_hashin_field: (nel, npt) each, entry = max_q FI_eqp, every cell whatever the selection, both computed in one
+ *     pass; either pointer may be NULL.  The first maximiser in quadrature order wins and a NaN stays visible.  Differentiated in
+ *     reverse at that maximiser under the names "ply_hashin_fibre_field" and "ply_hashin_matrix_field" (femo_field_output_vjp,
+ *     femo_field_total_gradients; the argument set of "ply_strength_index_field").  femo_field_output_jvp, femo_field_total_jvp and
+ *     femo_field_output_jacobian(_nnz) refuse the names: not provided.
+ * The outputs keep block slots and results of their own per index: a call never disturbs the other ply outputs.  No float atomics and
+ * fixed summation orders: two identical calls return the same bits; the totals repeat to the solver's tolerance.
+ * Not provided: Hashin's alpha > 0; derivatives with respect to the strengths; the shape derivative; forward mode and the sparse
+ * Jacobian of the fields; a combined index over both modes (take the max, or constrain both); transient laminates; the multi-GPU
+ * driver. */
+int femo_set_ply_hashin_table(femo_ctx* ctx, const double* table, int32_t npt, int64_t n);
+int femo_ply_hashin_field(femo_ctx* ctx, double* fibre, double* matrix, int64_t n);
+
 /* Layups: the laminate and the ply table built on the device from the design variables of a laminate, ply thicknesses and ply angles
  * (femo_alpha_amd/csrc/layup.h) -- new; the conventions are those of femo_alpha_amd/laminate.py (clt_from_plies, ply_table):
  *   - nply plies (1..32), listed bottom to top along the cell normal, the same materials in every cell: plies is nply x 12,
