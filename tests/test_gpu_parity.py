@@ -325,7 +325,8 @@ def test_shape_sensitivities_vs_oracle_finite_differences(kind, bc):
 
 
 def _shape_sensitivities(kind, bc, vertices=(), nrandom=3):
-    """``vertices``: checked in addition to the ``nrandom`` drawn at random."""
+    """``vertices``: checked in addition to the ``nrandom`` drawn at random.  Every entry, at beta = 1e15 and against an
+    extended-precision reference under a per-vertex scale: tests/test_gpu_shape_parity.py."""
     m, o, c, rng = _pair(kind, uhat=True, bc=bc, beta=1e6)
     w = rng.uniform(-1, 1, m.ndof) * 1e-3
     lam = rng.uniform(-1, 1, m.ndof)
