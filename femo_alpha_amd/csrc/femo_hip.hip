@@ -127,42 +127,44 @@ struct femo_ctx {
     DevBuf<double> clt;             // as the caller gave them (femo_get_field, the stale_factor snapshot)
     DevBuf<double> clt_sym;         // every block replaced by its symmetric part: what the kernels read (FieldsDev.clt)
     bool laminate = false;
-    // ply failure outputs (femo_set_ply_table; laminate mode only): npt recovery points of PLY_W doubles per cell
+    // the five ply criteria (PLY_CRITERIA) share three tables.  Every criterion has block slots and results of its own, so that a call of one
+    // never disturbs the shift another one's gradients read
+    struct PlySlots {
+        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
+    };
+    // ply table (femo_set_ply_table; laminate mode only): npt recovery points of PLY_W doubles per cell
     struct Ply {
         int npt = 0;                // 0: no table
         double rho = 100.0;         // femo_set_ply_failure_params
         DevBuf<double> tab;         // cell-major, as the caller gave it (femo_get_field, the layout of d K / d table)
         DevBuf<double> tabT;        // entry-major [16 p + k][nel]: what the kernels read
-        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
-        DevBuf<int> eslot;          // slot of every cell in ybuf (the inverse of eorder), built at first use
+        PlySlots slots;             // "ply_failure"
+        DevBuf<int> eslot;          // slot of every cell in ybuf (the inverse of eorder), built at first use; serves every criterion
     } ply;
-    // interlaminar shear outputs (femo_set_ply_shear_table; ply_shear.h; laminate mode only): npt recovery points of PSH_W doubles per cell
+    // interlaminar shear table (femo_set_ply_shear_table; ply_shear.h; laminate mode only): npt recovery points of PSH_W doubles per cell
     struct PlyShear {
         int npt = 0;                // 0: no table
         double rho = 100.0;         // femo_set_ply_shear_params
         DevBuf<double> tab;         // cell-major (femo_get_field, the layout of d K / d table)
         DevBuf<double> tabT;        // entry-major [6 p + k][nel]: what the kernels read
-        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
-        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_shear_dtable")
+        PlySlots slots;             // "ply_shear_failure"
     } psh;
-    // load-proportional ply strength index (ply_strength.h): the table is ply's; slots and results are its own, so that a call never
-    // disturbs the shift ply_failure's gradients read
+    // load-proportional ply strength index (ply_strength.h): the table is ply's
     struct PlyStrength {
         bool psd_ok = false;        // the table has passed k_ply_psd_check since it was last uploaded or built by femo_set_layup
-        DevBuf<double> part, res;   // block slots of the value pass; { shift S, reference area, K, alpha } of k_ply_combine
-        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_strength_dtable")
+        PlySlots slots;             // "ply_strength_index"
         DevBuf<int> first;          // k_ply_psd_check: the first offending recovery point
     } pst;
     // Hashin fibre and matrix indices (femo_set_ply_hashin_table; ply_hashin.h; laminate mode only): G and z are the ply table's, the
-    // six strengths per recovery point a table of their own; slots and results per index, so that a call never disturbs the others
+    // six strengths per recovery point a table of their own
     struct PlyHashin {
         int npt = 0;                // 0: no strengths table
         DevBuf<double> tab;         // cell-major (nel, npt, 6), as the caller gave it
         DevBuf<double> tabT;        // entry-major [6 p + k][nel]: what the kernels read
-        DevBuf<double> part[2], res[2];   // per index (fibre, matrix): block slots; { shift S, reference area, K, alpha } of k_ply_combine
-        DevBuf<double> gtab;        // room for one table gradient (femo_bench_kernel "ply_hashin_*_dtable")
+        PlySlots slots[2];          // "ply_hashin_fibre", "ply_hashin_matrix"
         DevBuf<int> first;          // k_hashin_check: the first offending entry
     } ph;
+    DevBuf<double> ply_gtab;        // room for one table gradient of any criterion (femo_bench_kernel "*_dtable")
     // layup mode (femo_set_layup; layup.h): the laminate and the ply table are built on the device from ply thicknesses and angles
     struct Layup {
         bool active = false;
@@ -610,7 +612,6 @@ static FieldsDev fields_dev(const femo_ctx* c) {
     return f;
 }
 static MeshDev mesh_dev_all(const femo_ctx* c);
-static int ply_need_table(femo_ctx* c, const char* who);
 static FacetDev facet_dev(const femo_ctx* c) {
     FacetDev fd;
     fd.nf = c->nf; fd.cell = c->fa.cell; fd.ledge = c->fa.ledge; fd.unode = c->fa.unode; fd.vnode = c->fa.vnode;
@@ -669,6 +670,8 @@ static FacetDev facet_dev(const femo_ctx* c) {
 #define COMMA_NU , DERIV_NU
 #define COMMA_LAM , true
 #define COMMA_FALSE_LAM , false, true
+#define COMMA_PFR_STATE , false
+#define COMMA_PFR_TABLE , true
 #define COMMA_PF_VALUE , PF_VALUE
 #define COMMA_PF_FIELD , PF_FIELD
 #define COMMA_PF_DW , PF_DW
@@ -2399,6 +2402,73 @@ int femo_set_laminate(femo_ctx* c, const double* clt, int64_t n) {
     return 0;
 }
 
+// ---- the three table setters on one helper.  check comes between the shape checks and the adoption: it refuses bad values, and may
+// leave a device copy in cand, which the table is then adopted from (the held table is not touched before it has passed)
+typedef int (*ply_table_check)(femo_ctx* c, const char* label, int width, const double* table, int npt, int64_t len, DevBuf<double>& cand);
+
+static int ply_table_finite(femo_ctx* c, const char* label, int width, const double* table, int npt, int64_t len, DevBuf<double>&) {
+    const int64_t per = (int64_t)width * npt;
+    for (int64_t i = 0; i < len; ++i)
+        if (!std::isfinite(table[i])) {
+            char buf[280];
+            const int64_t e = i / per, r = i - e * per;
+            snprintf(buf, sizeof buf, "%s: value %d of recovery point %d of cell %lld is not finite", label, (int)(r % width), (int)(r / width), (long long)e);
+            return fail(c, buf);
+        }
+    return 0;
+}
+
+// the Hashin strengths are checked on the device (k_hashin_check)
+static int hashin_table_positive(femo_ctx* c, const char* label, int width, const double* table, int npt, int64_t len, DevBuf<double>& cand) {
+    if (len > INT32_MAX) return fail(c, std::string(label) + ": more than 2^31 - 1 values");
+    int first = INT32_MAX;
+    HIPCHK(c, cand.alloc((size_t)len));
+    HIPCHK(c, c->ph.first.grow(1));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(cand, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ph.first, &first, sizeof first, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_hashin_check, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)cand, (long long)len, c->ph.first.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&first, c->ph.first, sizeof first, hipMemcpyDeviceToHost));
+    if (first == INT32_MAX) return 0;
+    static const char* const names[HSH_W] = {"Xt", "Xc", "Yt", "Yc", "SL", "ST"};
+    char buf[280];
+    const int64_t per = (int64_t)width * npt, e = first / per, r = first - e * per;
+    snprintf(buf, sizeof buf, "%s: value %d (the strength %s) of recovery point %d of cell %lld is not finite and > 0", label, (int)(r % width),
+             names[r % width], (int)(r / width), (long long)e);
+    return fail(c, buf);
+}
+
+// label: "ply table", ...; layout: the entries of a recovery point as the length message spells them; tab / tabT: the cell-major and the
+// entry-major device copies.  The caller sets npt on success
+static int ply_table_upload(femo_ctx* c, const char* label, const char* layout, int width, ply_table_check check, const double* table, int32_t npt,
+                            int64_t n, DevBuf<double>& tab, DevBuf<double>& tabT) {
+    char buf[280];
+    if (!c->laminate) return fail(c, std::string(label) + ": recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
+    if (npt < 1 || npt > PLY_MAX) {
+        snprintf(buf, sizeof buf, "%s: npt must be 1..%d recovery points per cell, got %d", label, PLY_MAX, (int)npt);
+        return fail(c, buf);
+    }
+    const int64_t len = (int64_t)width * npt * c->nel;
+    if (!table || n != len) {
+        snprintf(buf, sizeof buf, "%s: expected %d values per recovery point %s x %d points x %d cells = %lld, got %lld%s", label, width, layout,
+                 (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
+        return fail(c, buf);
+    }
+    DevBuf<double> cand;
+    if (int rc = check(c, label, width, table, npt, len, cand)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, tab.grow((size_t)len));
+    HIPCHK(c, tabT.grow((size_t)len));
+    if (cand) HIPCHK(c, hipMemcpy(tab, cand, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice));
+    else HIPCHK(c, hipMemcpy(tab, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)tab, tabT.get(), c->nel, width * npt);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
+}
+
 int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->lay.active) return fail(c, std::string("femo_set_ply_table") + LAYUP_OWNS);
@@ -2408,37 +2478,11 @@ int femo_set_ply_table(femo_ctx* c, const double* table, int32_t npt, int64_t n)
         c->pst.psd_ok = false;
         return 0;
     }
-    char buf[240];
-    if (!c->laminate) return fail(c, "ply table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
-    if (npt < 1 || npt > PLY_MAX) {
-        snprintf(buf, sizeof buf, "ply table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
-        return fail(c, buf);
-    }
-    const int64_t len = (int64_t)PLY_W * npt * c->nel;
-    if (!table || n != len) {
-        snprintf(buf, sizeof buf, "ply table: expected %d values per recovery point [G (3x3), z, F1, F2, F11, F22, F66, F12] x %d points x %d cells "
-                                  "= %lld, got %lld%s", PLY_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
-        return fail(c, buf);
-    }
-    const int64_t per = (int64_t)PLY_W * npt;
-    for (int64_t i = 0; i < len; ++i)
-        if (!std::isfinite(table[i])) {
-            const int64_t e = i / per, r = i - e * per;
-            snprintf(buf, sizeof buf, "ply table: value %d of recovery point %d of cell %lld is not finite", (int)(r % PLY_W), (int)(r / PLY_W), (long long)e);
-            return fail(c, buf);
-        }
-    const double rho = c->ply.rho;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->ply.tab.grow((size_t)len));
-    HIPCHK(c, c->ply.tabT.grow((size_t)len));
-    HIPCHK(c, hipMemcpy(c->ply.tab, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ply.tab, c->ply.tabT.get(), c->nel,
-                       (int)per);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->ply.npt = npt; c->ply.rho = rho;
+    if (int rc = ply_table_upload(c, "ply table", "[G (3x3), z, F1, F2, F11, F22, F66, F12]", PLY_W, ply_table_finite, table, npt, n, c->ply.tab,
+                                  c->ply.tabT)) return rc;
+    c->ply.npt = npt;
     c->pst.psd_ok = false;                                     // a new table: the strength index checks it when first asked for
-    return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
+    return 0;
 }
 
 int femo_set_ply_failure_params(femo_ctx* c, double rho) {
@@ -2453,43 +2497,16 @@ static const char* const LAYUP_OWNS_SHEAR = ": the shear table belongs to the ac
 int femo_set_ply_shear_table(femo_ctx* c, const double* table, int32_t npt, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->lay.active && c->lay.has_shear) return fail(c, std::string("femo_set_ply_shear_table") + LAYUP_OWNS_SHEAR);
-    const double rho = c->psh.rho;
     if (!table && n == 0) {
+        const double rho = c->psh.rho;                         // the parameter outlives the table
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->psh = femo_ctx::PlyShear();
         c->psh.rho = rho;
         return 0;
     }
-    char buf[240];
-    if (!c->laminate) return fail(c, "ply shear table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
-    if (npt < 1 || npt > PLY_MAX) {
-        snprintf(buf, sizeof buf, "ply shear table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
-        return fail(c, buf);
-    }
-    const int64_t len = (int64_t)PSH_W * npt * c->nel;
-    if (!table || n != len) {
-        snprintf(buf, sizeof buf, "ply shear table: expected %d values per recovery point [Gs (2x2), F55, F44] x %d points x %d cells = %lld, got %lld%s",
-                 PSH_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
-        return fail(c, buf);
-    }
-    const int64_t per = (int64_t)PSH_W * npt;
-    for (int64_t i = 0; i < len; ++i)
-        if (!std::isfinite(table[i])) {
-            const int64_t e = i / per, r = i - e * per;
-            snprintf(buf, sizeof buf, "ply shear table: value %d of recovery point %d of cell %lld is not finite", (int)(r % PSH_W), (int)(r / PSH_W),
-                     (long long)e);
-            return fail(c, buf);
-        }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->psh.tab.grow((size_t)len));
-    HIPCHK(c, c->psh.tabT.grow((size_t)len));
-    HIPCHK(c, hipMemcpy(c->psh.tab, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->psh.tab, c->psh.tabT.get(), c->nel,
-                       (int)per);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = ply_table_upload(c, "ply shear table", "[Gs (2x2), F55, F44]", PSH_W, ply_table_finite, table, npt, n, c->psh.tab, c->psh.tabT)) return rc;
     c->psh.npt = npt;
-    return 0;                                                  // the operator does not see the table: factor and Jacobi diagonal stay
+    return 0;
 }
 
 int femo_set_ply_shear_params(femo_ctx* c, double rho) {
@@ -2506,47 +2523,10 @@ int femo_set_ply_hashin_table(femo_ctx* c, const double* table, int32_t npt, int
         c->ph = femo_ctx::PlyHashin();
         return 0;
     }
-    char buf[280];
-    if (!c->laminate) return fail(c, "ply hashin table: recovery points belong to a laminate -- enter laminate mode first (femo_set_laminate)");
-    if (npt < 1 || npt > PLY_MAX) {
-        snprintf(buf, sizeof buf, "ply hashin table: npt must be 1..%d recovery points per cell, got %d", PLY_MAX, (int)npt);
-        return fail(c, buf);
-    }
-    const int64_t len = (int64_t)HSH_W * npt * c->nel;
-    if (!table || n != len) {
-        snprintf(buf, sizeof buf, "ply hashin table: expected %d values per recovery point [Xt, Xc, Yt, Yc, SL, ST] x %d points x %d cells = %lld, "
-                                  "got %lld%s", HSH_W, (int)npt, c->nel, (long long)len, (long long)n, table ? "" : " (null values)");
-        return fail(c, buf);
-    }
-    if (len > INT32_MAX) return fail(c, "ply hashin table: more than 2^31 - 1 values");
-    // the candidate passes the device check before the table the context holds is touched
-    DevBuf<double> cand;
-    int first = INT32_MAX;
-    HIPCHK(c, cand.alloc((size_t)len));
-    HIPCHK(c, c->ph.first.grow(1));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(cand, table, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->ph.first, &first, sizeof first, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_hashin_check, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)cand, (long long)len, c->ph.first.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(&first, c->ph.first, sizeof first, hipMemcpyDeviceToHost));
-    if (first != INT32_MAX) {
-        static const char* const names[HSH_W] = {"Xt", "Xc", "Yt", "Yc", "SL", "ST"};
-        const int64_t per = (int64_t)HSH_W * npt, e = first / per, r = first - e * per;
-        snprintf(buf, sizeof buf, "ply hashin table: value %d (the strength %s) of recovery point %d of cell %lld is not finite and > 0", (int)(r % HSH_W),
-                 names[r % HSH_W], (int)(r / HSH_W), (long long)e);
-        return fail(c, buf);
-    }
-    HIPCHK(c, c->ph.tab.grow((size_t)len));
-    HIPCHK(c, c->ph.tabT.grow((size_t)len));
-    HIPCHK(c, hipMemcpy(c->ph.tab, cand, (size_t)len * sizeof(double), hipMemcpyDeviceToDevice));
-    hipLaunchKernelGGL(k_ply_transpose, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ph.tab, c->ph.tabT.get(), c->nel,
-                       (int)(HSH_W * npt));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = ply_table_upload(c, "ply hashin table", "[Xt, Xc, Yt, Yc, SL, ST]", HSH_W, hashin_table_positive, table, npt, n, c->ph.tab, c->ph.tabT))
+        return rc;
     c->ph.npt = npt;
-    return 0;                                                  // the operator does not see the strengths: factor and Jacobi diagonal stay
+    return 0;
 }
 
 // ---- layups (layup.h): the laminate and the ply table built on the device from ply thicknesses and angles
@@ -2927,21 +2907,6 @@ int femo_layup_vjp(femo_ctx* c, const char* wrt, const double* laminate_bar, con
     return 0;
 }
 
-int femo_ply_failure_field(femo_ctx* c, double* out, int64_t n) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (ply_need_table(c, "femo_ply_failure_field")) return 2;
-    const int64_t len = (int64_t)c->nel * c->ply.npt;
-    if (!out || n != len) return fail(c, "femo_ply_failure_field: the field has nel * npt entries");
-    DevBuf<double> d;
-    HIPCHK(c, d.alloc((size_t)len));
-    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
-                c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const int*)nullptr, d.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
 int femo_set_state(femo_ctx* c, const double* w) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy(c->w, w, (size_t)c->ndof * sizeof(double), hipMemcpyHostToDevice));
@@ -3200,150 +3165,48 @@ static int pnorm_dev(femo_ctx* c, double out2[2]) {
     return 0;
 }
 
-// ---- ply failure aggregate and field (ply_failure.h)
+// ---- the ply criteria of laminated shells: five aggregates with a field each, driven from ONE table (PLY_CRITERIA).  A row holds what
+// differs between them; the value pass, the read-back, the gradients, the gate of the derivative entry points and the fields' reverse mode
+// below are written once on top of it.
+struct PlyCriterion;
+enum { PLY_PASS_VALUE = 0, PLY_PASS_FIELD = 1, PLY_PASS_DW = 2, PLY_PASS_DTABLE = 3 };      // the MODE numbers of all four kernels
+// One pass of a family's kernel over the mesh view m, enqueued.  res: the shift of the gradient passes; cbar (nel npt, device) or null:
+// a cotangent of the field in place of the KS weight; eslot: slot of every cell in ybuf (PLY_PASS_DW); out: block slots, the field, ybuf
+// or the table gradient; out2: the second field of a family that forms two in one pass (Hashin: out fibre, out2 matrix; either may be null)
+typedef int (*ply_launch_fn)(femo_ctx*, const PlyCriterion&, int pass, const MeshDev& m, const double* res, const double* cbar, const int* eslot,
+                             double* out, double* out2);
+// out (nel nply, device) = (d table / d layup)^T [d (cbar . field) / d table]  - (dR / d layup)^T lam: the way this criterion's table
+// cotangent reaches the layup argument wrt.  cbar null: of the aggregate; lam null: the partial alone
+typedef int (*ply_layup_fn)(femo_ctx*, const PlyCriterion&, const std::string& wrt, const double* lam, const double* cbar, double* out, int64_t n);
+
+struct PlyCriterion {
+    const char* name;               // the aggregate
+    const char* field;              // its field of nel * npt entries
+    const char* bench;              // femo_bench_kernel: "<bench>_value", "<bench>_dw", "<bench>_dtable"
+    const char* index_word;         // what the not-finite message calls the pointwise number
+    const char* table_arg;          // the argument its table gradient belongs to
+    int width;                      // ... and that table's doubles per recovery point
+    int idx;                        // Hashin: PH_FIBRE or PH_MATRIX; else 0
+    const int& (*npt)(const femo_ctx*);
+    const double& (*rho)(const femo_ctx*);
+    femo_ctx::PlySlots& (*slots)(femo_ctx*);
+    int (*need_table)(femo_ctx*, const char* who);
+    bool jac_and_jvp;               // the sparse Jacobian and the forward mode of the field are provided
+    bool layup_by_ply_table;        // the layup reaches it through the laminate and the ply table, the general composition of
+                                    // dfunctional_dev; false: through a table of its own, by layup_vjp alone
+    ply_layup_fn layup_vjp;
+    ply_launch_fn launch;           // the only place that names the family's kernel
+};
+
 static int ply_need_table(femo_ctx* c, const char* who) {
     if (c->ply.npt > 0) return 0;
     return fail(c, std::string(who) + ": no ply table is set (femo_set_ply_table, laminate mode)");
 }
 
-// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
-static int ply_value_launch(femo_ctx* c) {
-    auto& pl = c->ply;
-    const int g = nblk(c->nel, PLY_BLOCK);
-    HIPCHK(c, pl.part.grow((size_t)3 * g));
-    HIPCHK(c, pl.res.grow(4));
-    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
-                (const double*)c->w, (const double*)nullptr, (const int*)nullptr, pl.part.get());
-    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)pl.part, stress_alpha_ref(c), pl.npt, pl.rho, pl.res.get());
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like pnorm_stress's
-static int ply_value_dev(femo_ctx* c, double out4[4]) {
-    if (ply_need_table(c, "ply_failure")) return 2;
-    if (ply_value_launch(c)) return 1;
-    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->ply.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
-    if (!std::isfinite(out4[2])) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "ply_failure: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
-                                  "non-finite state or failure index", out4[0], out4[3], c->ply.rho);
-        return fail(c, msg);
-    }
-    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
-    return 0;
-}
-
-// slot of every cell in ybuf (the inverse of eorder), for the one-thread-per-cell kernels that end in k_gather_sum
-static int ply_eslot(femo_ctx* c) {
-    auto& pl = c->ply;
-    if (pl.eslot) return 0;
-    std::vector<int> eo((size_t)c->nel), inv((size_t)c->nel);
-    HIPCHK(c, hipMemcpy(eo.data(), c->eorder, eo.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int slot = 0; slot < c->nel; ++slot) inv[eo[slot]] = slot;
-    HIPCHK(c, pl.eslot.alloc(inv.size()));
-    HIPCHK(c, hipMemcpy(pl.eslot, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// out (ndof) = the element vectors of ybuf added per node in fixed order
-static int ply_gather_sum(femo_ctx* c, double* out) {
-    const int nthreads = c->nP2 + c->nghost;
-#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
-                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
-    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
-    else if (c->quad) GATHER_SUM(9, 4);
-    else GATHER_SUM(6, 3);
-#undef GATHER_SUM
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// d K / d w into out (ndof) or d K / d table into out (16 npt nel, cell-major); the shift stays on the device
-static int ply_grad_dev(femo_ctx* c, bool wrt_state, double* out) {
-    auto& pl = c->ply;
-    if (ply_value_launch(c)) return 1;
-    const int g = nblk(c->nel, PLY_BLOCK);
-    if (!wrt_state) {
-        ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_DTABLE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
-                    (const double*)c->w, (const double*)pl.res, (const int*)nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;
-    }
-    if (int rc = ply_eslot(c)) return rc;
-    ELEM_LAUNCH(c, k_ply_failure, COMMA_PF_DW, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, pl.rho,
-                (const double*)c->w, (const double*)pl.res, (const int*)pl.eslot, c->ybuf.get());
-    return ply_gather_sum(c, out);
-}
-
-// ---- interlaminar shear failure aggregate and field (ply_shear.h); slots, combine, eslot and gather are the ply failure's
 static int shear_need_table(femo_ctx* c, const char* who) {
     if (c->psh.npt > 0) return 0;
     return fail(c, std::string(who) + ": no ply shear table is set (femo_set_ply_shear_table, laminate mode)");
 }
-
-// the refusals every derivative entry point makes for the aggregate before it does anything else
-static int shear_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
-    if (fn != "ply_shear_failure") return 0;
-    if (shear_need_table(c, "ply_shear_failure")) return 2;
-    if (arg == "uhat") return fail(c, "ply_shear_failure: the shape derivative (uhat) of this output is not provided");
-    return 0;
-}
-
-// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
-static int shear_value_launch(femo_ctx* c) {
-    auto& ps = c->psh;
-    const int g = nblk(c->nel, PLY_BLOCK);
-    HIPCHK(c, ps.part.grow((size_t)3 * g));
-    HIPCHK(c, ps.res.grow(4));
-    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
-                (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ps.part.get());
-    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ps.part, stress_alpha_ref(c), ps.npt, ps.rho, ps.res.get());
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
-static int shear_value_dev(femo_ctx* c, double out4[4]) {
-    if (shear_need_table(c, "ply_shear_failure")) return 2;
-    if (shear_value_launch(c)) return 1;
-    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->psh.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
-    if (!std::isfinite(out4[2])) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "ply_shear_failure: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
-                                  "non-finite state or failure index", out4[0], out4[3], c->psh.rho);
-        return fail(c, msg);
-    }
-    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
-    return 0;
-}
-
-// (d / d w) into out (ndof) or (d / d table) into out (6 npt nel, cell-major).  cbar null: of the aggregate K over the selected
-// sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
-static int shear_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, double* out) {
-    auto& ps = c->psh;
-    if (!cbar && shear_value_launch(c)) return 1;
-    const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
-    const int g = nblk(c->nel, PLY_BLOCK);
-    if (!wrt_state) {
-        ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_DTABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
-                    (const double*)c->w, (const double*)ps.res, cbar, (const int*)nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;
-    }
-    if (int rc = ply_eslot(c)) return rc;
-    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_DW, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)ps.tabT, ps.npt, ps.rho,
-                (const double*)c->w, (const double*)ps.res, cbar, (const int*)c->ply.eslot, c->ybuf.get());
-    return ply_gather_sum(c, out);
-}
-
-// ---- load-proportional ply strength index (ply_strength.h) on the ply failure's table; eslot and gather are the ply failure's, the
-// slots and the results its own
-static bool strength_name(const std::string& fn) { return fn == "ply_strength_index"; }
 
 // a table, and one whose quadratic form is positive semidefinite: checked on the device once per upload or femo_set_layup, when one
 // of these outputs is first asked for; the error names the first offending cell and point
@@ -3369,73 +3232,6 @@ static int strength_need_table(femo_ctx* c, const char* who) {
     return fail(c, buf);
 }
 
-// the refusals every derivative entry point makes for the aggregate before it does anything else
-static int strength_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
-    if (!strength_name(fn)) return 0;
-    if (int rc = strength_need_table(c, "ply_strength_index")) return rc;
-    if (arg == "uhat") return fail(c, "ply_strength_index: the shape derivative (uhat) of this output is not provided");
-    return 0;
-}
-
-// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
-static int strength_value_launch(femo_ctx* c) {
-    auto& ps = c->pst;
-    const int g = nblk(c->nel, PLY_BLOCK);
-    HIPCHK(c, ps.part.grow((size_t)3 * g));
-    HIPCHK(c, ps.res.grow(4));
-    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_VALUE, g, PLY_BLOCK, mesh_dev(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
-                (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ps.part.get());
-    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ps.part, stress_alpha_ref(c), c->ply.npt, c->ply.rho, ps.res.get());
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
-static int strength_value_dev(femo_ctx* c, double out4[4]) {
-    if (int rc = strength_need_table(c, "ply_strength_index")) return rc;
-    if (strength_value_launch(c)) return 1;
-    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->pst.res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
-    if (!std::isfinite(out4[2])) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "ply_strength_index: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
-                                  "non-finite state or strength index", out4[0], out4[3], c->ply.rho);
-        return fail(c, msg);
-    }
-    if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
-    return 0;
-}
-
-// (d / d w) into out (ndof) or (d / d table) into out (16 npt nel, cell-major).  cbar null: of the aggregate K over the selected
-// sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
-static int strength_grad_dev(femo_ctx* c, bool wrt_state, const double* cbar, double* out) {
-    auto& ps = c->pst;
-    if (!cbar && strength_value_launch(c)) return 1;
-    const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
-    const int g = nblk(c->nel, PLY_BLOCK);
-    if (!wrt_state) {
-        ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_DTABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
-                    (const double*)c->w, (const double*)ps.res, cbar, (const int*)nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;
-    }
-    if (int rc = ply_eslot(c)) return rc;
-    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_DW, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho,
-                (const double*)c->w, (const double*)ps.res, cbar, (const int*)c->ply.eslot, c->ybuf.get());
-    return ply_gather_sum(c, out);
-}
-
-// ---- Hashin fibre and matrix indices (ply_hashin.h): G and z of the ply failure's table, strengths of their own; eslot and gather
-// are the ply failure's, the slots and the results their own per index
-// PH_FIBRE, PH_MATRIX, or -1
-static int hashin_name(const std::string& fn) { return fn == "ply_hashin_fibre" ? PH_FIBRE : fn == "ply_hashin_matrix" ? PH_MATRIX : -1; }
-static int hashin_field_name(const std::string& fn) {
-    return fn == "ply_hashin_fibre_field" ? PH_FIBRE : fn == "ply_hashin_matrix_field" ? PH_MATRIX : -1;
-}
-static const char* const HASHIN_NAMES[2] = {"ply_hashin_fibre", "ply_hashin_matrix"};
-static const char* const HASHIN_FIELD_NAMES[2] = {"ply_hashin_fibre_field", "ply_hashin_matrix_field"};
-
 // both tables, with the same recovery points
 static int hashin_need_table(femo_ctx* c, const char* who) {
     if (ply_need_table(c, who)) return 2;
@@ -3448,72 +3244,188 @@ static int hashin_need_table(femo_ctx* c, const char* who) {
     return 0;
 }
 
-// the refusals every derivative entry point makes for the aggregates before it does anything else
-static int hashin_gate(femo_ctx* c, const std::string& fn, const std::string& arg) {
-    const int idx = hashin_name(fn);
-    if (idx < 0) return 0;
-    if (int rc = hashin_need_table(c, HASHIN_NAMES[idx])) return rc;
-    if (arg == "uhat") return fail(c, fn + ": the shape derivative (uhat) of this output is not provided");
-    return 0;
-}
+// ---- the four launch functions: nothing else names these kernels or their template arguments
+#define PLY_PASS_LAUNCH(KERNEL, PREFIX, ...)                                                              \
+    switch (pass) {                                                                                       \
+    case PLY_PASS_VALUE: ELEM_LAUNCH(c, KERNEL, COMMA_##PREFIX##_VALUE, g, PLY_BLOCK, __VA_ARGS__); break; \
+    case PLY_PASS_FIELD: ELEM_LAUNCH(c, KERNEL, COMMA_##PREFIX##_FIELD, g, PLY_BLOCK, __VA_ARGS__); break; \
+    case PLY_PASS_DW: ELEM_LAUNCH(c, KERNEL, COMMA_##PREFIX##_DW, g, PLY_BLOCK, __VA_ARGS__); break;       \
+    default: ELEM_LAUNCH(c, KERNEL, COMMA_##PREFIX##_DTABLE, g, PLY_BLOCK, __VA_ARGS__); break;            \
+    }
 
-// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
-static int hashin_value_launch(femo_ctx* c, int idx) {
-    auto& ph = c->ph;
+// ply failure (ply_failure.h); with a cotangent, the reverse mode of its field, which has kernels of its own (ply_field_rev.h)
+static int failure_launch(femo_ctx* c, const PlyCriterion&, int pass, const MeshDev& m, const double* res, const double* cbar, const int* eslot,
+                          double* out, double*) {
     const int g = nblk(c->nel, PLY_BLOCK);
-    HIPCHK(c, ph.part[idx].grow((size_t)3 * g));
-    HIPCHK(c, ph.res[idx].grow(4));
-#define HASHIN_VALUE_ARGS mesh_dev(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT, (const double*)ph.tabT, c->ply.npt, c->ply.rho, \
-                          (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, ph.part[idx].get(), (double*)nullptr
-    if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_F, g, PLY_BLOCK, HASHIN_VALUE_ARGS);
-    else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_M, g, PLY_BLOCK, HASHIN_VALUE_ARGS);
-#undef HASHIN_VALUE_ARGS
-    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)ph.part[idx], stress_alpha_ref(c), c->ply.npt, c->ply.rho,
-                       ph.res[idx].get());
+    const double* tabT = c->ply.tabT;
+    if (cbar && pass == PLY_PASS_DTABLE)
+        ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_TABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, tabT, c->ply.npt, (const double*)c->w, cbar, eslot, out);
+    else if (cbar)
+        ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_STATE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, tabT, c->ply.npt, (const double*)c->w, cbar, eslot, out);
+    else
+        PLY_PASS_LAUNCH(k_ply_failure, PF, m, fields_dev(c), c->tab_s, tabT, c->ply.npt, c->ply.rho, (const double*)c->w, res, eslot, out)
     HIPCHK(c, hipGetLastError());
     return 0;
 }
 
-// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like ply_failure's
-static int hashin_value_dev(femo_ctx* c, int idx, double out4[4]) {
-    if (int rc = hashin_need_table(c, HASHIN_NAMES[idx])) return rc;
-    if (hashin_value_launch(c, idx)) return 1;
-    HIPCHK(c, hipMemcpyAsync(c->scal_host, c->ph.res[idx], 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+// interlaminar shear (ply_shear.h)
+static int shear_launch(femo_ctx* c, const PlyCriterion&, int pass, const MeshDev& m, const double* res, const double* cbar, const int* eslot,
+                        double* out, double*) {
+    const int g = nblk(c->nel, PLY_BLOCK);
+    PLY_PASS_LAUNCH(k_ply_shear, PS, m, fields_dev(c), c->tab_s, (const double*)c->psh.tabT, c->psh.npt, c->psh.rho, (const double*)c->w, res, cbar,
+                    eslot, out)
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// load-proportional strength index (ply_strength.h), on the ply table
+static int strength_launch(femo_ctx* c, const PlyCriterion&, int pass, const MeshDev& m, const double* res, const double* cbar, const int* eslot,
+                           double* out, double*) {
+    const int g = nblk(c->nel, PLY_BLOCK);
+    PLY_PASS_LAUNCH(k_ply_strength, PSI, m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, c->ply.npt, c->ply.rho, (const double*)c->w, res, cbar,
+                    eslot, out)
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// Hashin fibre and matrix indices (ply_hashin.h): G and z of the ply table, strengths of their own; the row's idx picks the instantiation.
+// The field pass forms both fields at once
+static int hashin_launch(femo_ctx* c, const PlyCriterion& k, int pass, const MeshDev& m, const double* res, const double* cbar, const int* eslot,
+                         double* out, double* out2) {
+    const int g = nblk(c->nel, PLY_BLOCK);
+#define HASHIN_ARGS m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, (const double*)c->ph.tabT, c->ply.npt, c->ply.rho, (const double*)c->w, \
+                    res, cbar, eslot, out, out2
+    const bool fibre = k.idx == PH_FIBRE;
+    switch (pass) {
+    case PLY_PASS_VALUE: if (fibre) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_F, g, PLY_BLOCK, HASHIN_ARGS);
+                         else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_VALUE_M, g, PLY_BLOCK, HASHIN_ARGS);
+                         break;
+    case PLY_PASS_FIELD: ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_FIELD, g, PLY_BLOCK, HASHIN_ARGS); break;
+    case PLY_PASS_DW: if (fibre) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_F, g, PLY_BLOCK, HASHIN_ARGS);
+                      else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_M, g, PLY_BLOCK, HASHIN_ARGS);
+                      break;
+    default: if (fibre) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_F, g, PLY_BLOCK, HASHIN_ARGS);
+             else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_M, g, PLY_BLOCK, HASHIN_ARGS);
+             break;
+    }
+#undef HASHIN_ARGS
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+#undef PLY_PASS_LAUNCH
+
+static int ply_table_layup_vjp(femo_ctx* c, const PlyCriterion& k, const std::string& wrt, const double* lam, const double* cbar, double* out, int64_t n);
+static int shear_layup_vjp(femo_ctx* c, const PlyCriterion& k, const std::string& wrt, const double* lam, const double* cbar, double* out, int64_t n);
+
+enum { PLY_FAILURE = 0, PLY_SHEAR = 1, PLY_STRENGTH = 2, PLY_HASHIN_FIBRE = 3, PLY_HASHIN_MATRIX = 4 };
+#define PLY_NPT(T) [](const femo_ctx* c) -> const int& { return c->T.npt; }
+#define PLY_RHO(T) [](const femo_ctx* c) -> const double& { return c->T.rho; }
+#define PLY_SLOTS(S) [](femo_ctx* c) -> femo_ctx::PlySlots& { return c->S; }
+static const PlyCriterion PLY_CRITERIA[5] = {
+    {"ply_failure", "ply_failure_field", "ply", "failure index", "ply_table", PLY_W, 0, PLY_NPT(ply), PLY_RHO(ply), PLY_SLOTS(ply.slots),
+     ply_need_table, true, true, ply_table_layup_vjp, failure_launch},
+    {"ply_shear_failure", "ply_shear_failure_field", "ply_shear", "failure index", "ply_shear_table", PSH_W, 0, PLY_NPT(psh), PLY_RHO(psh),
+     PLY_SLOTS(psh.slots), shear_need_table, false, false, shear_layup_vjp, shear_launch},
+    {"ply_strength_index", "ply_strength_index_field", "ply_strength", "strength index", "ply_table", PLY_W, 0, PLY_NPT(ply), PLY_RHO(ply),
+     PLY_SLOTS(pst.slots), strength_need_table, false, true, ply_table_layup_vjp, strength_launch},
+    {"ply_hashin_fibre", "ply_hashin_fibre_field", "ply_hashin_fibre", "failure index", "ply_table", PLY_W, PH_FIBRE, PLY_NPT(ply), PLY_RHO(ply),
+     PLY_SLOTS(ph.slots[PH_FIBRE]), hashin_need_table, false, true, ply_table_layup_vjp, hashin_launch},
+    {"ply_hashin_matrix", "ply_hashin_matrix_field", "ply_hashin_matrix", "failure index", "ply_table", PLY_W, PH_MATRIX, PLY_NPT(ply), PLY_RHO(ply),
+     PLY_SLOTS(ph.slots[PH_MATRIX]), hashin_need_table, false, true, ply_table_layup_vjp, hashin_launch},
+};
+#undef PLY_NPT
+#undef PLY_RHO
+#undef PLY_SLOTS
+
+// the row of an aggregate / of a field by name, or null
+static const PlyCriterion* ply_criterion(const std::string& fn) {
+    for (const PlyCriterion& k : PLY_CRITERIA) if (fn == k.name) return &k;
+    return nullptr;
+}
+static const PlyCriterion* ply_field_criterion(const std::string& fn) {
+    for (const PlyCriterion& k : PLY_CRITERIA) if (fn == k.field) return &k;
+    return nullptr;
+}
+
+// the refusals every derivative entry point makes for an aggregate before it does anything else
+static int ply_gate(femo_ctx* c, const PlyCriterion& k, const std::string& arg) {
+    if (int rc = k.need_table(c, k.name)) return rc;
+    if (arg == "uhat") return fail(c, std::string(k.name) + ": the shape derivative (uhat) of this output is not provided");
+    return 0;
+}
+
+// ... for a list of names that may be null: the rows in the table's order, the names in list order under each
+static int ply_gate_all(femo_ctx* c, int nfun, const char* const* functionals, const std::string& arg) {
+    for (const PlyCriterion& k : PLY_CRITERIA)
+        for (int i = 0; i < nfun; ++i)
+            if (functionals[i] && std::string(functionals[i]) == k.name)
+                if (int rc = ply_gate(c, k, arg)) return rc;
+    return 0;
+}
+
+// value pass over the selected sub-domain, enqueued only: block slots, then res = { S, reference area, K, alpha } on the device
+static int ply_value_launch(femo_ctx* c, const PlyCriterion& k) {
+    femo_ctx::PlySlots& sl = k.slots(c);
+    const int g = nblk(c->nel, PLY_BLOCK);
+    HIPCHK(c, sl.part.grow((size_t)3 * g));
+    HIPCHK(c, sl.res.grow(4));
+    if (int rc = k.launch(c, k, PLY_PASS_VALUE, mesh_dev(c), nullptr, nullptr, nullptr, sl.part, nullptr)) return rc;
+    hipLaunchKernelGGL(k_ply_combine, dim3(1), dim3(256), 0, c->stream, g, (const double*)sl.part, stress_alpha_ref(c), k.npt(c), k.rho(c), sl.res.get());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// ... and read back: out4 = { S, reference area, K, alpha }.  The reference area is frozen at first use like pnorm_stress's
+static int ply_value_dev(femo_ctx* c, const PlyCriterion& k, double out4[4]) {
+    if (int rc = k.need_table(c, k.name)) return rc;
+    if (ply_value_launch(c, k)) return 1;
+    HIPCHK(c, hipMemcpyAsync(c->scal_host, k.slots(c).res, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < 4; ++i) out4[i] = c->scal_host[i];
     if (!std::isfinite(out4[2])) {
         char msg[256];
-        snprintf(msg, sizeof msg, "%s: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a non-finite state or "
-                                  "failure index", HASHIN_NAMES[idx], out4[0], out4[3], c->ply.rho);
+        snprintf(msg, sizeof msg, "%s: the aggregate is not finite (S = %g, alpha = %g, rho = %g): an empty sub-domain, or a "
+                                  "non-finite state or %s", k.name, out4[0], out4[3], k.rho(c), k.index_word);
         return fail(c, msg);
     }
     if (stress_alpha_ref(c) < 0) stress_alpha_ref(c) = out4[1];
     return 0;
 }
 
-// (d / d w) into out (ndof) or (d / d table) into out (16 npt nel, cell-major).  cbar null: of the aggregate K over the selected
+// slot of every cell in ybuf (the inverse of eorder), for the one-thread-per-cell kernels of all criteria that end in k_gather_sum
+static int ply_eslot(femo_ctx* c) {
+    auto& pl = c->ply;
+    if (pl.eslot) return 0;
+    std::vector<int> eo((size_t)c->nel), inv((size_t)c->nel);
+    HIPCHK(c, hipMemcpy(eo.data(), c->eorder, eo.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int slot = 0; slot < c->nel; ++slot) inv[eo[slot]] = slot;
+    HIPCHK(c, pl.eslot.alloc(inv.size()));
+    HIPCHK(c, hipMemcpy(pl.eslot, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// out (ndof) = the element vectors of ybuf added per node in fixed order (all criteria)
+static int ply_gather_sum(femo_ctx* c, double* out) {
+    const int nthreads = c->nP2 + c->nghost;
+#define GATHER_SUM(NPC_, NVC_) hipLaunchKernelGGL((k_gather_sum<NPC_, NVC_>), dim3(nblk(nthreads, 256)), dim3(256), 0, c->stream, c->nP2, c->nn, \
+                                                  c->ndof_u, c->ndof, c->n2e_off, c->n2e_ent, c->ybuf, out, c->cr ? 1 : 0, c->nrot)
+    if (c->cg1) { if (c->quad) GATHER_SUM(4, 4); else GATHER_SUM(3, 3); }
+    else if (c->quad) GATHER_SUM(9, 4);
+    else GATHER_SUM(6, 3);
+#undef GATHER_SUM
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// (d / d w) into out (ndof) or (d / d table) into out (width npt nel, cell-major).  cbar null: of the aggregate K over the selected
 // sub-domain (the value pass runs first, the shift stays on the device); cbar (nel npt, device): of cbar . field over every cell
-static int hashin_grad_dev(femo_ctx* c, int idx, bool wrt_state, const double* cbar, double* out) {
-    auto& ph = c->ph;
-    if (!cbar && hashin_value_launch(c, idx)) return 1;
+static int ply_grad_dev(femo_ctx* c, const PlyCriterion& k, bool wrt_state, const double* cbar, double* out) {
+    if (!cbar && ply_value_launch(c, k)) return 1;
     const MeshDev m = cbar ? mesh_dev_all(c) : mesh_dev(c);
-    const int g = nblk(c->nel, PLY_BLOCK);
-#define HASHIN_GRAD_ARGS m, fields_dev(c), c->tab_s, (const double*)c->ply.tabT, (const double*)ph.tabT, c->ply.npt, c->ply.rho, \
-                         (const double*)c->w, (const double*)ph.res[idx], cbar, eslot, dst, (double*)nullptr
-    const int* eslot = nullptr;
-    double* dst = out;
-    if (!wrt_state) {
-        if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_F, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
-        else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DTABLE_M, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
-        HIPCHK(c, hipGetLastError());
-        return 0;
-    }
+    const double* res = k.slots(c).res;
+    if (!wrt_state) return k.launch(c, k, PLY_PASS_DTABLE, m, res, cbar, nullptr, out, nullptr);
     if (int rc = ply_eslot(c)) return rc;
-    eslot = c->ply.eslot;
-    dst = c->ybuf;
-    if (idx == PH_FIBRE) ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_F, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
-    else ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_DW_M, g, PLY_BLOCK, HASHIN_GRAD_ARGS);
-#undef HASHIN_GRAD_ARGS
+    if (int rc = k.launch(c, k, PLY_PASS_DW, m, res, cbar, c->ply.eslot, c->ybuf, nullptr)) return rc;
     return ply_gather_sum(c, out);
 }
 
@@ -3734,27 +3646,9 @@ int femo_functional(femo_ctx* c, const char* name, double* value) {
         *value = v[0] / stress_alpha_ref(c);
         return 0;
     }
-    if (s == "ply_failure") {
+    if (const PlyCriterion* k = ply_criterion(s)) {
         double v[4];
-        if (int rc = ply_value_dev(c, v)) return rc;
-        *value = v[2];
-        return 0;
-    }
-    if (s == "ply_shear_failure") {
-        double v[4];
-        if (int rc = shear_value_dev(c, v)) return rc;
-        *value = v[2];
-        return 0;
-    }
-    if (strength_name(s)) {
-        double v[4];
-        if (int rc = strength_value_dev(c, v)) return rc;
-        *value = v[2];
-        return 0;
-    }
-    if (const int idx = hashin_name(s); idx >= 0) {
-        double v[4];
-        if (int rc = hashin_value_dev(c, idx, v)) return rc;
+        if (int rc = ply_value_dev(c, *k, v)) return rc;
         *value = v[2];
         return 0;
     }
@@ -3818,17 +3712,11 @@ static int shape_gradient_dev(femo_ctx* c, int mode, const double* w, const doub
 static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string& wrt, double* out, int64_t n) {
     // the layup's own outputs first: the composition below reaches the layup through the laminate and the table, which these never see
     if (layup_mass_name(c, fn)) return layup_mass_grad_dev(c, fn, wrt, out, n);
-    if (const int lw = layup_wrt(c, wrt); lw && fn == "ply_shear_failure") {
-        // the shear table of a layup sees the ply angles alone: d/d ply_angle = (d shear table / d ply_angle)^T [d/d ply_shear_table];
-        // the ply_thickness partial is exact zeros (its total comes through the laminate and the adjoint)
-        if (shear_need_table(c, "ply_shear_failure")) return 2;
+    const PlyCriterion* const k = ply_criterion(fn);
+    if (layup_wrt(c, wrt) && k && !k->layup_by_ply_table) {      // a table of its own: the composition below never sees it
+        if (int rc = k->need_table(c, k->name)) return rc;
         if (n != (int64_t)c->nel * c->lay.nply) return fail(c, "gradient buffer has the wrong length for '" + wrt + "'");
-        hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
-        HIPCHK(c, hipGetLastError());
-        if (lw == 1 || !c->lay.has_shear) return 0;
-        HIPCHK(c, c->lay.sbar.grow((size_t)PSH_W * c->psh.npt * c->nel));
-        if (int rc = shear_grad_dev(c, false, nullptr, c->lay.sbar)) return rc;
-        return layup_shear_vjp_dev(c, c->lay.sbar, out);
+        return k->layup_vjp(c, *k, wrt, nullptr, nullptr, out, n);
     }
     if (const int lw = layup_wrt(c, wrt)) {
         // the composition d/dx = (d laminate / dx)^T [d/d laminate] + (d table / dx)^T [d/d ply_table], on device buffers
@@ -3850,30 +3738,11 @@ static int dfunctional_dev(femo_ctx* c, const std::string& fn, const std::string
     const MeshDev m = mesh_dev(c);
     const FieldsDev f = fields_dev(c);
     const int g = nblk(c->nel, EB);
-    if (fn == "ply_failure") {
-        if (ply_need_table(c, "ply_failure")) return 2;
-        if (wrt == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
-        if (wrt == "disp_solid" || wrt == "ply_table") return ply_grad_dev(c, wrt == "disp_solid", out);
+    if (k) {
+        if (int rc = ply_gate(c, *k, wrt)) return rc;
+        if (wrt == "disp_solid" || wrt == k->table_arg) return ply_grad_dev(c, *k, wrt == "disp_solid", nullptr, out);
         HIPCHK(c, hipGetLastError());
-        return 0;                                             // laminate, thickness, E, nu, density, F_solid: no explicit dependence
-    }
-    if (fn == "ply_shear_failure") {
-        if (int rc = shear_gate(c, fn, wrt)) return rc;
-        if (wrt == "disp_solid" || wrt == "ply_shear_table") return shear_grad_dev(c, wrt == "disp_solid", nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;                                             // laminate, ply_table, thickness, E, nu, density, F_solid: no explicit dependence
-    }
-    if (strength_name(fn)) {
-        if (int rc = strength_gate(c, fn, wrt)) return rc;
-        if (wrt == "disp_solid" || wrt == "ply_table") return strength_grad_dev(c, wrt == "disp_solid", nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;                                             // laminate, thickness, E, nu, density, F_solid, ply_shear_table: no explicit dependence
-    }
-    if (const int idx = hashin_name(fn); idx >= 0) {
-        if (int rc = hashin_gate(c, fn, wrt)) return rc;
-        if (wrt == "disp_solid" || wrt == "ply_table") return hashin_grad_dev(c, idx, wrt == "disp_solid", nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;                                             // laminate, thickness, E, nu, density, F_solid, ply_shear_table: no explicit dependence
+        return 0;                                             // the other table, laminate, thickness, E, nu, density, F_solid: no explicit dependence
     }
     if (const int slot = disp_agg_slot(fn); slot >= 0) {      // nodal values, not integrals: the state is the only argument they see
         if (wrt == "disp_solid") return disp_agg_grad_dev(c, fn, slot, out);
@@ -3979,13 +3848,8 @@ int femo_total_gradient(femo_ctx* c, const char* functional, const char* arg, do
                         double* relres) {
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fn(functional ? functional : ""), a(arg ? arg : "");
-    if (fn == "ply_failure") {
-        if (ply_need_table(c, "ply_failure")) return 2;
-        if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
-    }
-    if (int rc = shear_gate(c, fn, a)) return rc;
-    if (int rc = strength_gate(c, fn, a)) return rc;
-    if (int rc = hashin_gate(c, fn, a)) return rc;
+    if (const PlyCriterion* k = ply_criterion(fn))
+        if (int rc = ply_gate(c, *k, a)) return rc;
     DevBuf<double> d;
     HIPCHK(c, d.alloc(std::max<int64_t>(n, 1)));
     if (layup_mass_name(c, fn)) {                                           // no state dependence: lambda = 0, the total is the partial
@@ -4098,17 +3962,7 @@ int femo_total_gradients(femo_ctx* c, int32_t nfun, const char* const* functiona
     const int keep_sel = c->csel;
     for (int i = 0; i < nfun; ++i)
         if (subdomains && (subdomains[i] < -1 || subdomains[i] >= c->ntags)) return fail(c, "unknown sub-domain");
-    for (int i = 0; i < nfun; ++i)
-        if (functionals[i] && std::string(functionals[i]) == "ply_failure") {
-            if (ply_need_table(c, "ply_failure")) return 2;
-            if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
-        }
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = hashin_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    if (int rc = ply_gate_all(c, nfun, functionals, a)) return rc;
     HIPCHK(c, c->mr_io.grow((size_t)nfun * (2 * nd + (size_t)std::max<int64_t>(n, 1))));
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nfun * nd, *Gd = Xd + (size_t)nfun * nd;
@@ -4338,17 +4192,7 @@ int femo_total_jvp(femo_ctx* c, const char* arg, int32_t ndir, const double* V, 
     if (int rc = jvp_check_arg(c, a, n)) return rc;
     for (int i = 0; i < nfun; ++i)
         if (subdomains && (subdomains[i] < -1 || subdomains[i] >= c->ntags)) return fail(c, "unknown sub-domain");
-    for (int i = 0; i < nfun; ++i)
-        if (functionals[i] && std::string(functionals[i]) == "ply_failure") {
-            if (ply_need_table(c, "ply_failure")) return 2;
-            if (a == "uhat") return fail(c, "ply_failure: the shape derivative (uhat) of this output is not provided");
-        }
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = shear_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = strength_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
-    for (int i = 0; i < nfun; ++i)
-        if (int rc = hashin_gate(c, functionals[i] ? functionals[i] : "", a)) return rc;
+    if (int rc = ply_gate_all(c, nfun, functionals, a)) return rc;
     const size_t nd = (size_t)c->ndof, nv = (size_t)std::max<int64_t>(n, 1);
     const int keep_sel = c->csel;
     HIPCHK(c, c->jv.scal.grow(2 * (size_t)std::max(nfun, 1) * ndir));
@@ -5949,11 +5793,9 @@ static int field_vjp_dev(femo_ctx* c, double zf, const std::string& wrt, const d
     return 0;
 }
 
-// ---- reverse mode of the ply failure field (ply_field_rev.h): the same three entry points under the name "ply_failure_field"
-#define COMMA_PFR_STATE , false
-#define COMMA_PFR_TABLE , true
+// ---- reverse mode of the fields of the ply criteria: the same three entry points under the criteria's field names
 
-// wrt is an argument the ply failure field is differentiated by in reverse, and n its length (n < 0: not checked).  *lw: layup_wrt's
+// wrt is an argument a field of recovery points is differentiated by in reverse, and n its length (n < 0: not checked).  *lw: layup_wrt's
 // 1 or 2; the products and the totals reach the layup through the table (layup_ok), the sparse Jacobian refuses it as the stress
 // fields do.  The shape derivative is refused like the aggregate's and the forward mode's.
 static int point_field_rev_arg(femo_ctx* c, const char* field, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
@@ -5966,82 +5808,88 @@ static int point_field_rev_arg(femo_ctx* c, const char* field, const std::string
     if (n >= 0 && len != n) return fail(c, "buffer has the wrong length for '" + wrt + "'");
     return 0;
 }
-static int ply_field_rev_arg(femo_ctx* c, const std::string& wrt, int64_t n, bool layup_ok, int* lw) {
-    return point_field_rev_arg(c, "ply_failure_field", wrt, n, layup_ok, lw);
-}
 
-// entries per row of the partial Jacobian of the ply failure field (0: the field does not depend on wrt)
-static int ply_field_jac_width(const femo_ctx* c, const std::string& wrt) {
-    return wrt == "disp_solid" ? c->ld : wrt == "ply_table" ? PLY_W : 0;
-}
-
-// out (device) = (d field / d w)^T cbar (ndof) or (d field / d table)^T cbar (16 npt nel, cell-major) for one device cotangent of
-// nel npt entries; every entry of out is written
-static int ply_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) {
-    auto& pl = c->ply;
-    const MeshDev m = mesh_dev_all(c);
-    const int g = nblk(c->nel, PLY_BLOCK);
-    if (table) {
-        ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_TABLE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, (const double*)c->w,
-                    cbar, (const int*)nullptr, out);
-        HIPCHK(c, hipGetLastError());
-        return 0;
+// the layup hook of the criteria on the ply table: lbar = -(dR / d laminate)^T lam (where there is an adjoint) and the table cotangent
+// go through ONE pull-back, the composition of dfunctional_dev / dRdarg_T_dev.  The stream orders the reuse of lbar and tbar
+static int ply_table_layup_vjp(femo_ctx* c, const PlyCriterion& k, const std::string& wrt, const double* lam, const double* cbar, double* out, int64_t n) {
+    const int64_t nl = (int64_t)LAM_W * c->nel;
+    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
+    if (lam) {
+        HIPCHK(c, c->lay.lbar.grow((size_t)nl));
+        hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 0.0, nl);
+        if (int rc = dRdarg_T_dev(c, "laminate", lam, -1.0, c->lay.lbar, nl)) return rc;
     }
-    if (int rc = ply_eslot(c)) return rc;
-    ELEM_LAUNCH(c, k_ply_field_vjp, COMMA_PFR_STATE, g, PLY_BLOCK, m, fields_dev(c), c->tab_s, (const double*)pl.tabT, pl.npt, (const double*)c->w, cbar,
-                (const int*)pl.eslot, c->ybuf.get());
-    return ply_gather_sum(c, out);
+    if (int rc = ply_grad_dev(c, k, false, cbar, c->lay.tbar)) return rc;
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    return layup_vjp_dev(c, layup_wrt(c, wrt), lam ? c->lay.lbar.get() : nullptr, c->lay.tbar, out);
 }
 
-// out (device, n) = (d field / d wrt)^T cbar for an argument ply_field_rev_arg admitted (lw from there): the kernels for the state
-// and the table, the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
-static int ply_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    if (wrt == "disp_solid" || wrt == "ply_table") return ply_field_vjp_dev(c, wrt == "ply_table", cbar, out);
+// the layup hook of the shear criterion: the shear table of a layup sees the ply angles alone, through a pull-back of its own (the
+// ply_thickness partial is exact zeros); the adjoint term then comes through the laminate as for any other output
+static int shear_layup_vjp(femo_ctx* c, const PlyCriterion& k, const std::string& wrt, const double* lam, const double* cbar, double* out, int64_t n) {
     if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
     HIPCHK(c, hipGetLastError());
-    if (!lw) return 0;
-    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
-    if (int rc = ply_field_vjp_dev(c, true, cbar, c->lay.tbar)) return rc;
-    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
+    if (layup_wrt(c, wrt) == 2 && c->lay.has_shear) {
+        HIPCHK(c, c->lay.sbar.grow((size_t)PSH_W * c->psh.npt * c->nel));
+        if (int rc = ply_grad_dev(c, k, false, cbar, c->lay.sbar)) return rc;
+        if (int rc = layup_shear_vjp_dev(c, c->lay.sbar, out)) return rc;
+    }
+    return lam ? dRdarg_T_dev(c, wrt, lam, -1.0, out, n) : 0;
 }
 
-// The products of a (nel, npt) field of recovery points with nbar cotangents: shared by "ply_failure_field" and
-// "ply_shear_failure_field".  need_table refuses without a table, arg_vjp is the field's own product for one device cotangent.
-typedef int (*point_field_arg_vjp)(femo_ctx*, const std::string&, int, const double*, double*, int64_t);
-static int point_field_output_vjp(femo_ctx* c, const char* field, int (*need_table)(femo_ctx*, const char*), const int* npt,
-                                  point_field_arg_vjp arg_vjp, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    if (need_table(c, field)) return 2;
+// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted (lw from there): the kernels for the state
+// and the table, the table cotangent through the criterion's layup hook for the layup, exact zeros for every other argument
+static int ply_field_arg_vjp_dev(femo_ctx* c, const PlyCriterion& k, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
+    if (wrt == "disp_solid" || wrt == k.table_arg) return ply_grad_dev(c, k, wrt == "disp_solid", cbar, out);
+    if (lw) return k.layup_vjp(c, k, wrt, nullptr, cbar, out, n);
+    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// the products of a criterion's (nel, npt) field with nbar cotangents
+static int ply_field_output_vjp(femo_ctx* c, const PlyCriterion& k, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
+    if (k.need_table(c, k.field)) return 2;
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nel * npt entries");
     int lw;
-    if (int rc = point_field_rev_arg(c, field, a, n, true, &lw)) return rc;
-    const size_t nc = (size_t)c->nel * *npt;
+    if (int rc = point_field_rev_arg(c, k.field, a, n, true, &lw)) return rc;
+    const size_t nc = (size_t)c->nel * k.npt(c);
     DevBuf<double> d;
     HIPCHK(c, d.alloc((size_t)nbar * nc + (size_t)nbar * std::max<int64_t>(n, 1)));
     double* o = d + (size_t)nbar * nc;
     if (hipMemcpy(d, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(c, "copy of the cotangents failed");
-    for (int64_t k = 0; k < nbar; ++k)                   // one cotangent at a time: row k is the single call on cbar[k] bit for bit
-        if (int rc = arg_vjp(c, a, lw, d + k * nc, o + k * n, n)) return rc;
+    for (int64_t j = 0; j < nbar; ++j)                   // one cotangent at a time: row j is the single call on cbar[j] bit for bit
+        if (int rc = ply_field_arg_vjp_dev(c, k, a, lw, d + j * nc, o + j * n, n)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, o, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
-static int ply_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    return point_field_output_vjp(c, "ply_failure_field", ply_need_table, &c->ply.npt, ply_field_arg_vjp_dev, a, cbar, nbar, out, n);
+// the refusal of the criteria whose field has neither forward mode nor a sparse Jacobian
+static int ply_field_not_provided(femo_ctx* c, const PlyCriterion& k, const char* who) {
+    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of '" + k.field + "' are not provided "
+                                      "(femo_field_output_vjp, femo_field_total_gradients)");
 }
 
-static int ply_field_jacobian_nnz(femo_ctx* c, const std::string& a, int64_t* nnz) {
-    if (ply_need_table(c, "ply_failure_field")) return 2;
+// ---- the sparse Jacobian of the ply failure field (ply_field_rev.h), the one field that has it (PlyCriterion::jac_and_jvp)
+// entries per row of the partial Jacobian (0: the field does not depend on wrt)
+static int ply_field_jac_width(const femo_ctx* c, const std::string& wrt) {
+    return wrt == "disp_solid" ? c->ld : wrt == "ply_table" ? PLY_W : 0;
+}
+
+static int ply_field_jacobian_nnz(femo_ctx* c, const PlyCriterion& k, const std::string& a, int64_t* nnz) {
+    if (!k.jac_and_jvp) return ply_field_not_provided(c, k, "femo_field_output_jacobian");
+    if (k.need_table(c, k.field)) return 2;
     int lw;
-    if (int rc = ply_field_rev_arg(c, a, -1, false, &lw)) return rc;
+    if (int rc = point_field_rev_arg(c, k.field, a, -1, false, &lw)) return rc;
     if (!nnz) return fail(c, "null nnz");
     *nnz = (int64_t)ply_field_jac_width(c, a) * c->nel * c->ply.npt;
     return 0;
 }
 
-static int ply_field_jacobian(femo_ctx* c, const std::string& a, int64_t* rowptr, int32_t* colidx, double* vals, int64_t nnz) {
+static int ply_field_jacobian(femo_ctx* c, const PlyCriterion& k, const std::string& a, int64_t* rowptr, int32_t* colidx, double* vals, int64_t nnz) {
     int64_t want;
-    if (int rc = ply_field_jacobian_nnz(c, a, &want)) return rc;
+    if (int rc = ply_field_jacobian_nnz(c, k, a, &want)) return rc;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
     if (nnz > INT32_MAX) return fail(c, "femo_field_output_jacobian: the columns of this Jacobian do not fit 32-bit indices");
@@ -6068,54 +5916,40 @@ static int ply_field_jacobian(femo_ctx* c, const std::string& a, int64_t* rowptr
     return 0;
 }
 
-// out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k for the ply failure field.  R sees the laminate and the load alone in
-// laminate mode: for every other argument no solve runs (iterations 0, residuals 0).  The layup: lbar_k = -(dR / d laminate)^T lambda_k
-// and tbar_k = (d field / d table)^T cbar_k go through ONE pull-back, the composition of dfunctional_dev / dRdarg_T_dev.
-// Shared by the fields on the ply table, "ply_failure_field" and "ply_strength_index_field": vjp is the field's own product with one
-// device cotangent (table = false: the state, true: the table), arg_vjp its product for any admitted argument.
-typedef int (*ply_table_field_vjp)(femo_ctx*, bool, const double*, double*);
-static int ply_table_field_total_gradients(femo_ctx* c, const char* field, int (*need_table)(femo_ctx*, const char*), ply_table_field_vjp vjp,
-                                           point_field_arg_vjp arg_vjp, int32_t nbar, const double* cbar, const std::string& a, double* out,
-                                           int64_t n, int32_t* iters, double* relres) {
-    if (int rc = need_table(c, field)) return rc;
+// out_j = (d field / d arg)^T cbar_j - (dR / d arg)^T lambda_j for a criterion's field.  R sees the laminate and the load alone in
+// laminate mode: for every other argument no solve runs (iterations 0, residuals 0).  The layup goes through the criterion's hook.
+static int ply_field_total_gradients(femo_ctx* c, const PlyCriterion& k, int32_t nbar, const double* cbar, const std::string& a, double* out,
+                                     int64_t n, int32_t* iters, double* relres) {
+    if (int rc = k.need_table(c, k.field)) return rc;
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nel * npt entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
     int lw;
-    if (int rc = point_field_rev_arg(c, field, a, n, true, &lw)) return rc;
+    if (int rc = point_field_rev_arg(c, k.field, a, n, true, &lw)) return rc;
     const bool solve = lw || a == "laminate" || a == "F_solid";
-    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * c->ply.npt, ng = (size_t)std::max<int64_t>(n, 1);
-    const int64_t nl = (int64_t)LAM_W * c->nel;
+    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * k.npt(c), ng = (size_t)std::max<int64_t>(n, 1);
     HIPCHK(c, c->mr_io.grow((size_t)nbar * (2 * nd + ng + nc)));
-    if (lw) {
-        HIPCHK(c, c->lay.lbar.grow((size_t)nl));
-        HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
-    }
     double* Bd = c->mr_io;
     double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * ng;
     std::vector<double*> B(nbar), X(nbar);
-    for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
+    for (int j = 0; j < nbar; ++j) { B[j] = Bd + j * nd; X[j] = Xd + j * nd; }
     int rc = 0;
     if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
     if (solve) {
-        for (int k = 0; k < nbar && !rc; ++k) rc = vjp(c, false, Cd + k * nc, B[k]);                             // (d field / d w)^T cbar_k
-        if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_k
+        for (int j = 0; j < nbar && !rc; ++j) rc = ply_grad_dev(c, k, true, Cd + j * nc, B[j]);                  // (d field / d w)^T cbar_j
+        if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_j
     } else {
-        for (int k = 0; k < nbar; ++k) {
-            if (iters) iters[k] = 0;
-            if (relres) relres[k] = 0.0;
+        for (int j = 0; j < nbar; ++j) {
+            if (iters) iters[j] = 0;
+            if (relres) relres[j] = 0.0;
         }
     }
-    for (int k = 0; k < nbar && !rc; ++k) {
-        double* g = Gd + (size_t)k * n;
-        if (lw) {                                         // the stream orders the reuse of lbar and tbar
-            hipLaunchKernelGGL(k_fill, dim3(vec_grid(nl)), dim3(256), 0, c->stream, c->lay.lbar.get(), 0.0, nl);
-            rc = dRdarg_T_dev(c, "laminate", X[k], -1.0, c->lay.lbar, nl);
-            if (!rc) rc = vjp(c, true, Cd + k * nc, c->lay.tbar);
-            if (!rc) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, g, 0.0, n);
-            if (!rc) rc = layup_vjp_dev(c, lw, c->lay.lbar, c->lay.tbar, g);
+    for (int j = 0; j < nbar && !rc; ++j) {
+        double* g = Gd + (size_t)j * n;
+        if (lw) {
+            rc = k.layup_vjp(c, k, a, X[j], Cd + j * nc, g, n);
         } else {
-            rc = arg_vjp(c, a, 0, Cd + k * nc, g, n);                                                            // (d field / d arg)^T cbar_k
-            if (!rc && solve) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                         // - (dR/d arg)^T lambda_k
+            rc = ply_field_arg_vjp_dev(c, k, a, 0, Cd + j * nc, g, n);                                           // (d field / d arg)^T cbar_j
+            if (!rc && solve) rc = dRdarg_T_dev(c, a, X[j], -1.0, g, n);                                         // - (dR/d arg)^T lambda_j
         }
     }
     if (!rc) {
@@ -6126,195 +5960,43 @@ static int ply_table_field_total_gradients(femo_ctx* c, const char* field, int (
     return rc;
 }
 
-static int ply_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
-                                     double* relres) {
-    return ply_table_field_total_gradients(c, "ply_failure_field", ply_need_table, ply_field_vjp_dev, ply_field_arg_vjp_dev, nbar, cbar, a, out, n,
-                                           iters, relres);
-}
-
-// ---- reverse mode of the ply strength index field (ply_strength.h: the gradient modes with a cotangent in place of the KS weight,
-// at the maximiser), under the name "ply_strength_index_field".  Forward mode and the sparse Jacobian are not provided.
-static int strength_field_not_provided(femo_ctx* c, const char* who) {
-    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of 'ply_strength_index_field' are not provided "
-                                      "(femo_field_output_vjp, femo_field_total_gradients)");
-}
-
-static int strength_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return strength_grad_dev(c, !table, cbar, out); }
-
-// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
-// the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
-static int strength_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    if (wrt == "disp_solid" || wrt == "ply_table") return strength_grad_dev(c, wrt == "disp_solid", cbar, out);
-    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
-    HIPCHK(c, hipGetLastError());
-    if (!lw) return 0;
-    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
-    if (int rc = strength_grad_dev(c, false, cbar, c->lay.tbar)) return rc;
-    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
-}
-
-static int strength_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    return point_field_output_vjp(c, "ply_strength_index_field", strength_need_table, &c->ply.npt, strength_field_arg_vjp_dev, a, cbar, nbar, out, n);
-}
-
-static int strength_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n,
-                                          int32_t* iters, double* relres) {
-    return ply_table_field_total_gradients(c, "ply_strength_index_field", strength_need_table, strength_field_vjp_dev, strength_field_arg_vjp_dev,
-                                           nbar, cbar, a, out, n, iters, relres);
-}
-
-int femo_ply_strength_index_field(femo_ctx* c, double* out, int64_t n) {
+// ---- the field getters: every cell, whatever the selected sub-domain
+static int ply_field_get(femo_ctx* c, const PlyCriterion& k, const char* who, double* out, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = strength_need_table(c, "femo_ply_strength_index_field")) return rc;
-    const int64_t len = (int64_t)c->nel * c->ply.npt;
-    if (!out || n != len) return fail(c, "femo_ply_strength_index_field: the field has nel * npt entries");
+    if (int rc = k.need_table(c, who)) return rc;
+    const int64_t len = (int64_t)c->nel * k.npt(c);
+    if (!out || n != len) return fail(c, std::string(who) + ": the field has nel * npt entries");
     DevBuf<double> d;
     HIPCHK(c, d.alloc((size_t)len));
-    ELEM_LAUNCH(c, k_ply_strength, COMMA_PSI_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
-                c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, d.get());
-    HIPCHK(c, hipGetLastError());
+    if (int rc = k.launch(c, k, PLY_PASS_FIELD, mesh_dev_all(c), nullptr, nullptr, nullptr, d, nullptr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
-// ---- the Hashin fields (ply_hashin.h) and their reverse mode (the gradient modes with a cotangent in place of the KS weight, at the
-// first maximiser), under the names "ply_hashin_fibre_field" and "ply_hashin_matrix_field".  Forward mode and the sparse Jacobian are
-// not provided.
-static int hashin_field_not_provided(femo_ctx* c, int idx, const char* who) {
-    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of '" + HASHIN_FIELD_NAMES[idx] + "' are not provided "
-                                      "(femo_field_output_vjp, femo_field_total_gradients)");
+int femo_ply_failure_field(femo_ctx* c, double* out, int64_t n) { return ply_field_get(c, PLY_CRITERIA[PLY_FAILURE], "femo_ply_failure_field", out, n); }
+int femo_ply_shear_failure_field(femo_ctx* c, double* out, int64_t n) {
+    return ply_field_get(c, PLY_CRITERIA[PLY_SHEAR], "femo_ply_shear_failure_field", out, n);
+}
+int femo_ply_strength_index_field(femo_ctx* c, double* out, int64_t n) {
+    return ply_field_get(c, PLY_CRITERIA[PLY_STRENGTH], "femo_ply_strength_index_field", out, n);
 }
 
-static int hashin_fibre_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return hashin_grad_dev(c, PH_FIBRE, !table, cbar, out); }
-static int hashin_matrix_field_vjp_dev(femo_ctx* c, bool table, const double* cbar, double* out) { return hashin_grad_dev(c, PH_MATRIX, !table, cbar, out); }
-
-// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
-// the table cotangent through the layup's pull-back for the layup, exact zeros for every other argument
-static int hashin_field_arg_vjp_dev(femo_ctx* c, int idx, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    if (wrt == "disp_solid" || wrt == "ply_table") return hashin_grad_dev(c, idx, wrt == "disp_solid", cbar, out);
-    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
-    HIPCHK(c, hipGetLastError());
-    if (!lw) return 0;
-    HIPCHK(c, c->lay.tbar.grow((size_t)PLY_W * c->ply.npt * c->nel));
-    if (int rc = hashin_grad_dev(c, idx, false, cbar, c->lay.tbar)) return rc;
-    return layup_vjp_dev(c, lw, nullptr, c->lay.tbar, out);
-}
-static int hashin_fibre_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    return hashin_field_arg_vjp_dev(c, PH_FIBRE, wrt, lw, cbar, out, n);
-}
-static int hashin_matrix_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    return hashin_field_arg_vjp_dev(c, PH_MATRIX, wrt, lw, cbar, out, n);
-}
-
-static int hashin_field_output_vjp(femo_ctx* c, int idx, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    return point_field_output_vjp(c, HASHIN_FIELD_NAMES[idx], hashin_need_table, &c->ply.npt,
-                                  idx == PH_FIBRE ? hashin_fibre_field_arg_vjp_dev : hashin_matrix_field_arg_vjp_dev, a, cbar, nbar, out, n);
-}
-
-static int hashin_field_total_gradients(femo_ctx* c, int idx, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n,
-                                        int32_t* iters, double* relres) {
-    return ply_table_field_total_gradients(c, HASHIN_FIELD_NAMES[idx], hashin_need_table,
-                                           idx == PH_FIBRE ? hashin_fibre_field_vjp_dev : hashin_matrix_field_vjp_dev,
-                                           idx == PH_FIBRE ? hashin_fibre_field_arg_vjp_dev : hashin_matrix_field_arg_vjp_dev, nbar, cbar, a,
-                                           out, n, iters, relres);
-}
-
-// both fields in one pass over the strains; either pointer may be null
+// both Hashin fields in one pass over the strains; either pointer may be null
 int femo_ply_hashin_field(femo_ctx* c, double* fibre, double* matrix, int64_t n) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = hashin_need_table(c, "femo_ply_hashin_field")) return rc;
+    const PlyCriterion& k = PLY_CRITERIA[PLY_HASHIN_FIBRE];
+    if (int rc = k.need_table(c, "femo_ply_hashin_field")) return rc;
     const int64_t len = (int64_t)c->nel * c->ply.npt;
     if (n != len) return fail(c, "femo_ply_hashin_field: the fields have nel * npt entries");
     if (!fibre && !matrix) return 0;
     DevBuf<double> d;
     HIPCHK(c, d.alloc((size_t)2 * len));
-    ELEM_LAUNCH(c, k_ply_hashin, COMMA_PH_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->ply.tabT,
-                (const double*)c->ph.tabT, c->ply.npt, c->ply.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr,
-                (const int*)nullptr, fibre ? d.get() : (double*)nullptr, matrix ? d.get() + len : (double*)nullptr);
-    HIPCHK(c, hipGetLastError());
+    if (int rc = k.launch(c, k, PLY_PASS_FIELD, mesh_dev_all(c), nullptr, nullptr, nullptr, fibre ? d.get() : (double*)nullptr,
+                          matrix ? d.get() + len : (double*)nullptr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (fibre) HIPCHK(c, hipMemcpy(fibre, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
     if (matrix) HIPCHK(c, hipMemcpy(matrix, d.get() + len, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---- reverse mode of the interlaminar shear field (ply_shear.h: the gradient modes with a cotangent in place of the KS weight), under
-// the name "ply_shear_failure_field".  Forward mode and the sparse Jacobian are not provided.
-static int shear_field_not_provided(femo_ctx* c, const char* who) {
-    return fail(c, std::string(who) + ": forward mode and the sparse Jacobian of 'ply_shear_failure_field' are not provided "
-                                      "(femo_field_output_vjp, femo_field_total_gradients)");
-}
-
-// out (device, n) = (d field / d wrt)^T cbar for an argument point_field_rev_arg admitted: the kernels for the state and the table,
-// the table cotangent through the layup's pull-back for the ply angles, exact zeros for every other argument
-static int shear_field_arg_vjp_dev(femo_ctx* c, const std::string& wrt, int lw, const double* cbar, double* out, int64_t n) {
-    if (wrt == "disp_solid" || wrt == "ply_shear_table") return shear_grad_dev(c, wrt == "disp_solid", cbar, out);
-    if (n > 0) hipLaunchKernelGGL(k_fill, dim3(vec_grid(n)), dim3(256), 0, c->stream, out, 0.0, n);
-    HIPCHK(c, hipGetLastError());
-    if (lw != 2 || !c->lay.has_shear) return 0;
-    HIPCHK(c, c->lay.sbar.grow((size_t)PSH_W * c->psh.npt * c->nel));
-    if (int rc = shear_grad_dev(c, false, cbar, c->lay.sbar)) return rc;
-    return layup_shear_vjp_dev(c, c->lay.sbar, out);
-}
-
-static int shear_field_output_vjp(femo_ctx* c, const std::string& a, const double* cbar, int64_t nbar, double* out, int64_t n) {
-    return point_field_output_vjp(c, "ply_shear_failure_field", shear_need_table, &c->psh.npt, shear_field_arg_vjp_dev, a, cbar, nbar, out, n);
-}
-
-// out_k = (d field / d arg)^T cbar_k - (dR / d arg)^T lambda_k for the shear field, as ply_field_total_gradients: a solve runs for the
-// laminate, the load and the layup only; for the layup lbar_k = -(dR / d laminate)^T lambda_k goes through the layup's pull-back and the
-// shear table cotangent through its own (ply angles).
-static int shear_field_total_gradients(femo_ctx* c, int32_t nbar, const double* cbar, const std::string& a, double* out, int64_t n, int32_t* iters,
-                                       double* relres) {
-    if (shear_need_table(c, "ply_shear_failure_field")) return 2;
-    if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nel * npt entries");
-    if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
-    int lw;
-    if (int rc = point_field_rev_arg(c, "ply_shear_failure_field", a, n, true, &lw)) return rc;
-    const bool solve = lw || a == "laminate" || a == "F_solid";
-    const size_t nd = (size_t)c->ndof, nc = (size_t)c->nel * c->psh.npt, ng = (size_t)std::max<int64_t>(n, 1);
-    HIPCHK(c, c->mr_io.grow((size_t)nbar * (2 * nd + ng + nc)));
-    double* Bd = c->mr_io;
-    double *Xd = Bd + (size_t)nbar * nd, *Gd = Xd + (size_t)nbar * nd, *Cd = Gd + (size_t)nbar * ng;
-    std::vector<double*> B(nbar), X(nbar);
-    for (int k = 0; k < nbar; ++k) { B[k] = Bd + k * nd; X[k] = Xd + k * nd; }
-    int rc = 0;
-    if (hipMemcpy(Cd, cbar, (size_t)nbar * nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, "copy of the cotangents failed");
-    if (solve) {
-        for (int k = 0; k < nbar && !rc; ++k) rc = shear_grad_dev(c, true, Cd + k * nc, B[k]);                   // (d field / d w)^T cbar_k
-        if (!rc) rc = solve_multi_dev(c, nbar, B.data(), X.data(), iters, relres);                               // lambda_k
-    } else {
-        for (int k = 0; k < nbar; ++k) {
-            if (iters) iters[k] = 0;
-            if (relres) relres[k] = 0.0;
-        }
-    }
-    for (int k = 0; k < nbar && !rc; ++k) {
-        double* g = Gd + (size_t)k * n;
-        rc = shear_field_arg_vjp_dev(c, a, lw, Cd + k * nc, g, n);                                               // (d field / d arg)^T cbar_k
-        if (!rc && solve) rc = dRdarg_T_dev(c, a, X[k], -1.0, g, n);                                             // - (dR/d arg)^T lambda_k
-    }
-    if (!rc) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, Gd, (size_t)nbar * n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { c->err = hipGetErrorString(e); rc = 1; }
-    }
-    return rc;
-}
-
-int femo_ply_shear_failure_field(femo_ctx* c, double* out, int64_t n) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (shear_need_table(c, "femo_ply_shear_failure_field")) return 2;
-    const int64_t len = (int64_t)c->nel * c->psh.npt;
-    if (!out || n != len) return fail(c, "femo_ply_shear_failure_field: the field has nel * npt entries");
-    DevBuf<double> d;
-    HIPCHK(c, d.alloc((size_t)len));
-    ELEM_LAUNCH(c, k_ply_shear, COMMA_PS_FIELD, nblk(c->nel, PLY_BLOCK), PLY_BLOCK, mesh_dev_all(c), fields_dev(c), c->tab_s, (const double*)c->psh.tabT,
-                c->psh.npt, c->psh.rho, (const double*)c->w, (const double*)nullptr, (const double*)nullptr, (const int*)nullptr, d.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, d, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -6322,10 +6004,7 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
-    if (fname == "ply_shear_failure_field") return shear_field_output_vjp(c, a, cbar, nbar, out, n);
-    if (fname == "ply_strength_index_field") return strength_field_output_vjp(c, a, cbar, nbar, out, n);
-    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_output_vjp(c, idx, a, cbar, nbar, out, n);
-    if (fname == "ply_failure_field") return ply_field_output_vjp(c, a, cbar, nbar, out, n);
+    if (const PlyCriterion* k = ply_field_criterion(fname)) return ply_field_output_vjp(c, *k, a, cbar, nbar, out, n);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_output_vjp: nbar >= 1 cotangents of nvc * nel entries");
     if (field_arg_len(c, a, n)) return 1;
@@ -6344,10 +6023,7 @@ int femo_field_output_vjp(femo_ctx* c, const char* name, const char* wrt, const 
 int femo_field_output_jacobian_nnz(femo_ctx* c, const char* name, const char* wrt, int64_t* nnz) {
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     double zf;
-    if (fname == "ply_failure_field") return ply_field_jacobian_nnz(c, a, nnz);
-    if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
-    if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
-    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_not_provided(c, idx, "femo_field_output_jacobian");
+    if (const PlyCriterion* k = ply_field_criterion(fname)) return ply_field_jacobian_nnz(c, *k, a, nnz);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (int rc = layup_field_refused(c, a)) return rc;
     const int wd = field_jac_width(c, a);
@@ -6361,10 +6037,7 @@ int femo_field_output_jacobian(femo_ctx* c, const char* name, const char* wrt, i
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(wrt ? wrt : "");
     int64_t want;
-    if (fname == "ply_failure_field") return ply_field_jacobian(c, a, rowptr, colidx, vals, nnz);
-    if (fname == "ply_shear_failure_field") return shear_field_not_provided(c, "femo_field_output_jacobian");
-    if (fname == "ply_strength_index_field") return strength_field_not_provided(c, "femo_field_output_jacobian");
-    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_not_provided(c, idx, "femo_field_output_jacobian");
+    if (const PlyCriterion* k = ply_field_criterion(fname)) return ply_field_jacobian(c, *k, a, rowptr, colidx, vals, nnz);
     if (femo_field_output_jacobian_nnz(c, name, wrt, &want)) return 1;
     if (nnz != want) return fail(c, "femo_field_output_jacobian: nnz must be femo_field_output_jacobian_nnz's count");
     if (!rowptr || (nnz > 0 && (!colidx || !vals))) return fail(c, "null output array");
@@ -6400,10 +6073,7 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
     HIPCHK(c, hipSetDevice(c->device));
     const std::string fname(name ? name : ""), a(arg ? arg : "");
     double zf;
-    if (fname == "ply_failure_field") return ply_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
-    if (fname == "ply_shear_failure_field") return shear_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
-    if (fname == "ply_strength_index_field") return strength_field_total_gradients(c, nbar, cbar, a, out, n, iters, relres);
-    if (const int idx = hashin_field_name(fname); idx >= 0) return hashin_field_total_gradients(c, idx, nbar, cbar, a, out, n, iters, relres);
+    if (const PlyCriterion* k = ply_field_criterion(fname)) return ply_field_total_gradients(c, *k, nbar, cbar, a, out, n, iters, relres);
     if (!field_zf(fname, &zf)) return field_unknown(c, fname);
     if (nbar < 1 || !cbar || !out) return fail(c, "femo_field_total_gradients: nbar >= 1 cotangents of nvc * nel entries");
     if (a == "disp_solid") return fail(c, "femo_field_total_gradients: the state is not an argument of the total derivative");
@@ -6437,12 +6107,11 @@ int femo_field_total_gradients(femo_ctx* c, const char* name, int32_t nbar, cons
 static int64_t field_jvp_size(femo_ctx* c, const std::string& name) {
     double zf;
     if (field_zf(name, &zf)) return (int64_t)c->nvc * c->nel;
-    if (name == "ply_shear_failure_field") { shear_field_not_provided(c, "forward mode"); return -1; }
-    if (name == "ply_strength_index_field") { strength_field_not_provided(c, "forward mode"); return -1; }
-    if (const int idx = hashin_field_name(name); idx >= 0) { hashin_field_not_provided(c, idx, "forward mode"); return -1; }
-    if (name != "ply_failure_field") { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
-    if (ply_need_table(c, "ply_failure_field")) return -2;
-    return (int64_t)c->nel * c->ply.npt;
+    const PlyCriterion* const k = ply_field_criterion(name);
+    if (!k) { fail(c, "unknown field output '" + name + "' (" + FIELD_NAMES_JVP + ")"); return -1; }
+    if (!k->jac_and_jvp) { ply_field_not_provided(c, *k, "forward mode"); return -1; }
+    if (k->need_table(c, k->field)) return -2;
+    return (int64_t)c->nel * k->npt(c);
 }
 
 // wrt is an argument the field `name` can be differentiated by, and n its length.  Every input of the model is accepted (zeros
@@ -6634,49 +6303,28 @@ int femo_bench_kernel(femo_ctx* c, const char* name, int32_t reps, double* avg_m
             hipLaunchKernelGGL(k_fill, dim3(vec_grid(n * nr)), dim3(256), 0, c->stream, c->mr_v, 1.0, n * nr);
             return nr == 2 ? frontal_solve_multi<2>(c, c->mr_v, c->mr_y) : frontal_solve_multi<4>(c, c->mr_v, c->mr_y);
         }
-        // ply failure: the aggregate's value pass, its whole state gradient on the device (value pass, PF_DW, gather: what
-        // femo_dfunctional enqueues), and the reverse products of the field for a cotangent of ones (state: kernel and gather; table)
-        if (s == "ply_value" || s == "ply_dw" || s == "ply_field_vjp" || s == "ply_field_vjp_table") {
-            if (ply_need_table(c, "femo_bench_kernel")) return 2;
-            if (s == "ply_value") return ply_value_launch(c);
-            if (s == "ply_dw") return ply_grad_dev(c, true, c->tmp);
+        // the reverse products of the ply failure field for a cotangent of ones (state: kernel and gather; table)
+        if (s == "ply_field_vjp" || s == "ply_field_vjp_table") {
+            const PlyCriterion& k = PLY_CRITERIA[PLY_FAILURE];
+            if (int rc = k.need_table(c, "femo_bench_kernel")) return rc;
             const size_t nc = (size_t)c->nel * c->ply.npt, nt = nc * PLY_W;
             if (!cbar_set) {                                // once per call: the timed launches are the products alone
                 HIPCHK(c, c->mr_io.grow(nc + nt));
                 hipLaunchKernelGGL(k_fill, dim3(vec_grid((int64_t)nc)), dim3(256), 0, c->stream, c->mr_io.get(), 1.0, (int64_t)nc);
                 cbar_set = true;
             }
-            return s == "ply_field_vjp" ? ply_field_vjp_dev(c, false, c->mr_io, c->tmp) : ply_field_vjp_dev(c, true, c->mr_io, c->mr_io.get() + nc);
+            return s == "ply_field_vjp" ? ply_grad_dev(c, k, true, c->mr_io, c->tmp) : ply_grad_dev(c, k, false, c->mr_io, c->mr_io.get() + nc);
         }
-        // interlaminar shear: the value pass with its combine, the state gradient as femo_dfunctional enqueues it (value pass,
-        // PS_DW, gather) and the table product (value pass, PS_DTABLE)
-        if (s == "ply_shear_value" || s == "ply_shear_dw" || s == "ply_shear_dtable") {
-            if (shear_need_table(c, "femo_bench_kernel")) return 2;
-            if (s == "ply_shear_value") return shear_value_launch(c);
-            if (s == "ply_shear_dw") return shear_grad_dev(c, true, nullptr, c->tmp);
-            HIPCHK(c, c->psh.gtab.grow((size_t)PSH_W * c->psh.npt * c->nel));
-            return shear_grad_dev(c, false, nullptr, c->psh.gtab);
-        }
-        // ply strength index: the passes of the shear outputs above, on the ply table; "ply_dtable" is the table product of
-        // "ply_failure" (value pass, PF_DTABLE), the counterpart to measure "ply_strength_dtable" against
-        if (s == "ply_strength_value" || s == "ply_strength_dw" || s == "ply_strength_dtable" || s == "ply_dtable") {
-            if (int rc = s == "ply_dtable" ? ply_need_table(c, "femo_bench_kernel") : strength_need_table(c, "femo_bench_kernel")) return rc;
-            if (s == "ply_strength_value") return strength_value_launch(c);
-            if (s == "ply_strength_dw") return strength_grad_dev(c, true, nullptr, c->tmp);
-            HIPCHK(c, c->pst.gtab.grow((size_t)PLY_W * c->ply.npt * c->nel));
-            return s == "ply_dtable" ? ply_grad_dev(c, false, c->pst.gtab) : strength_grad_dev(c, false, nullptr, c->pst.gtab);
-        }
-        // Hashin indices: the passes of the strength index above, per index ("ply_hashin_fibre_value", "ply_hashin_matrix_dw", ...)
-        for (int idx = 0; idx < 2; ++idx) {
-            const std::string base = HASHIN_NAMES[idx];
-            if (s.rfind(base + "_", 0) != 0) continue;
-            const std::string pass = s.substr(base.size() + 1);
-            if (pass != "value" && pass != "dw" && pass != "dtable") continue;
-            if (int rc = hashin_need_table(c, "femo_bench_kernel")) return rc;
-            if (pass == "value") return hashin_value_launch(c, idx);
-            if (pass == "dw") return hashin_grad_dev(c, idx, true, nullptr, c->tmp);
-            HIPCHK(c, c->ph.gtab.grow((size_t)PLY_W * c->ply.npt * c->nel));
-            return hashin_grad_dev(c, idx, false, nullptr, c->ph.gtab);
+        // the ply criteria, "<short name>_<pass>": the value pass with its combine ("value"), the state gradient as femo_dfunctional
+        // enqueues it (value pass, DW pass, gather: "dw") and the table gradient (value pass, DTABLE pass: "dtable")
+        for (const PlyCriterion& k : PLY_CRITERIA) {
+            const std::string base = std::string(k.bench) + "_";
+            if (s != base + "value" && s != base + "dw" && s != base + "dtable") continue;
+            if (int rc = k.need_table(c, "femo_bench_kernel")) return rc;
+            if (s == base + "value") return ply_value_launch(c, k);
+            if (s == base + "dw") return ply_grad_dev(c, k, true, nullptr, c->tmp);
+            HIPCHK(c, c->ply_gtab.grow((size_t)k.width * k.npt(c) * c->nel));
+            return ply_grad_dev(c, k, false, nullptr, c->ply_gtab);
         }
         return fail(c, "unknown kernel '" + s + "'");
     };

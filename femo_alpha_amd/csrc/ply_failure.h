@@ -74,6 +74,114 @@ __device__ __forceinline__ void ks_push_w(double& m, double& z, double u, double
     m = d > 0.0 ? u : m;
 }
 
+// ---- device code shared by the kernels of all ply criteria (ply_failure.h, ply_shear.h, ply_strength.h, ply_hashin.h, ply_field_rev.h)
+
+// the six strains of every degree-4 point of the state w, through the thread's column of LDS into registers
+template <int NPC, int NVC, bool QUAD, bool UHAT, int NQ>
+__device__ __forceinline__ void ply_point_strains(const MeshDev& m, const Tables* __restrict__ tab, const Elem<NPC, NVC>& el,
+                                                  const double* __restrict__ w, double (*s_q)[PLY_BLOCK], int tid, double (&s)[NQ][6]) {
+    constexpr int LD = 3 * NPC + 3 * NVC;
+    {
+        double xe[LD];
+        load_state<NPC, NVC>(m, el, w, xe);
+        for (int q = 0; q < NQ; ++q) {
+            QPG g;
+            qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
+            const Gen sq = strains_q<NPC, NVC>(*tab, q, g, xe);
+            s_q[6 * q + 0][tid] = sq.e00; s_q[6 * q + 1][tid] = sq.e11; s_q[6 * q + 2][tid] = sq.g01;
+            s_q[6 * q + 3][tid] = sq.k00; s_q[6 * q + 4][tid] = sq.k11; s_q[6 * q + 5][tid] = sq.k01;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[q][k] = s_q[6 * q + k][tid];
+}
+
+// ply_point_strains with the weights: the six strains and wj_q = w_q det_q Ju_q of every degree-4 point through the thread's column
+// of LDS (7 rows per point) into registers; returns the reference area sum_q w_q det_q
+template <int NPC, int NVC, bool QUAD, bool UHAT, int NQ>
+__device__ __forceinline__ double ply_point_strains_w(const MeshDev& m, const Tables* __restrict__ tab, const Elem<NPC, NVC>& el,
+                                                      const double* __restrict__ w, double (*s_q)[PLY_BLOCK], int tid, double (&s)[NQ][6],
+                                                      double (&wj)[NQ]) {
+    constexpr int LD = 3 * NPC + 3 * NVC;
+    double area = 0.0;
+    {
+        double xe[LD];
+        load_state<NPC, NVC>(m, el, w, xe);
+        for (int q = 0; q < NQ; ++q) {
+            QPG g;
+            qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
+            const Gen sq = strains_q<NPC, NVC>(*tab, q, g, xe);
+            s_q[7 * q + 0][tid] = sq.e00; s_q[7 * q + 1][tid] = sq.e11; s_q[7 * q + 2][tid] = sq.g01;
+            s_q[7 * q + 3][tid] = sq.k00; s_q[7 * q + 4][tid] = sq.k11; s_q[7 * q + 5][tid] = sq.k01;
+            const double wd = tab->w[q] * g.det;
+            s_q[7 * q + 6][tid] = wd * g.Ju;
+            area += wd;                                  // alpha: area of the reference configuration, as for pnorm_stress
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[q][k] = s_q[7 * q + k][tid];
+        wj[q] = s_q[7 * q + 6][tid];
+    }
+    return area;
+}
+
+// The strain cotangents of every quadrature point, parked in the thread's column of LDS (7 rows per point, the first six: ebar,
+// kbar), go through ONE strains_T_q each (geometry again, once per point); the cell's element vector goes to its slot of ybuf for
+// k_gather_sum (fixed order, no atomics)
+template <int NPC, int NVC, bool QUAD, bool UHAT, int NQ>
+__device__ __forceinline__ void ply_strain_cotangents_to_ybuf(const Tables* __restrict__ tab, const Elem<NPC, NVC>& el, double (*s_q)[PLY_BLOCK],
+                                                              int tid, const int* __restrict__ eslot, int e, double* __restrict__ out) {
+    constexpr int LD = 3 * NPC + 3 * NVC;
+    double ye[LD];
+#pragma unroll
+    for (int i = 0; i < LD; ++i) ye[i] = 0.0;
+    for (int q = 0; q < NQ; ++q) {
+        QPG g;
+        qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
+        Gen tt;
+        tt.e00 = s_q[7 * q + 0][tid]; tt.e11 = s_q[7 * q + 1][tid]; tt.g01 = s_q[7 * q + 2][tid];
+        tt.k00 = s_q[7 * q + 3][tid]; tt.k11 = s_q[7 * q + 4][tid]; tt.k01 = s_q[7 * q + 5][tid];
+        tt.ga0 = tt.ga1 = tt.om = 0.0;
+        strains_T_q<NPC, NVC>(*tab, q, g, tt, ye);
+    }
+    double* dst = out + (size_t)eslot[e] * YSTRIDE;
+#pragma unroll
+    for (int i = 0; i < LD; ++i) dst[i] = ye[i];
+}
+
+// a cell outside the selected sub-domain: zeros in its slot of ybuf (the state gradients) ...
+template <int LD>
+__device__ __forceinline__ void ply_zero_ybuf_slot(const int* __restrict__ eslot, int e, double* __restrict__ out) {
+    double* dst = out + (size_t)eslot[e] * YSTRIDE;
+    for (int i = 0; i < LD; ++i) dst[i] = 0.0;
+}
+
+// ... and in its W npt row of the table gradient
+template <int W>
+__device__ __forceinline__ void ply_zero_table_row(int e, int npt, double* __restrict__ out) {
+    double* o = out + (size_t)e * npt * W;
+    for (int k = 0; k < npt * W; ++k) o[k] = 0.0;
+}
+
+// end of a value pass: the running pairs of the wave merged by a butterfly, the reference areas summed; lane 0 writes the block's slot
+// (m, z, reference area) for k_ply_combine
+__device__ __forceinline__ void ply_block_slot(double km, double kz, double area, int tid, double* __restrict__ out) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double m2 = shfl_xor_d(km, off), z2 = shfl_xor_d(kz, off);
+        ks_merge(km, kz, m2, z2);
+    }
+    area = wave_sum(area);
+    if (tid == 0) {
+        double* p = out + (size_t)blockIdx.x * 3;
+        p[0] = km; p[1] = kz; p[2] = area;
+    }
+}
+
 // res: shift S of the gradient kernels (PF_DW, PF_DTABLE), read from device memory; eslot: slot of every cell in ybuf (PF_DW);
 // out: part (PF_VALUE, 3 doubles per block), the field (PF_FIELD), ybuf (PF_DW), d K / d table (PF_DTABLE)
 template <int NPC, int NVC, bool QUAD, bool UHAT, int MODE>
@@ -88,27 +196,8 @@ k_ply_failure(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doub
     if (live) {
         Elem<NPC, NVC> el;
         load_elem<NPC, NVC, UHAT>(m, f, e, el);
-        {
-            double xe[LD];
-            load_state<NPC, NVC>(m, el, w, xe);
-            for (int q = 0; q < NQ; ++q) {
-                QPG g;
-                qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-                const Gen s = strains_q<NPC, NVC>(*tab, q, g, xe);
-                s_q[7 * q + 0][tid] = s.e00; s_q[7 * q + 1][tid] = s.e11; s_q[7 * q + 2][tid] = s.g01;
-                s_q[7 * q + 3][tid] = s.k00; s_q[7 * q + 4][tid] = s.k11; s_q[7 * q + 5][tid] = s.k01;
-                const double wd = tab->w[q] * g.det;
-                s_q[7 * q + 6][tid] = wd * g.Ju;
-                area += wd;                                  // alpha: area of the reference configuration, as for pnorm_stress
-            }
-        }
         double s[NQ][6], wj[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) s[q][k] = s_q[7 * q + k][tid];
-            wj[q] = s_q[7 * q + 6][tid];
-        }
+        area = ply_point_strains_w<NPC, NVC, QUAD, UHAT, NQ>(m, tab, el, w, s_q, tid, s, wj);
         if constexpr (MODE == PF_VALUE) {
             for (int p = 0; p < npt; ++p) {
                 PlyPoint P;
@@ -159,21 +248,7 @@ k_ply_failure(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doub
             for (int q = 0; q < NQ; ++q)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) { s_q[7 * q + j][tid] = eb[q][j]; s_q[7 * q + 3 + j][tid] = kb[q][j]; }
-            double ye[LD];
-#pragma unroll
-            for (int i = 0; i < LD; ++i) ye[i] = 0.0;
-            for (int q = 0; q < NQ; ++q) {
-                QPG g;
-                qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-                Gen tt;
-                tt.e00 = s_q[7 * q + 0][tid]; tt.e11 = s_q[7 * q + 1][tid]; tt.g01 = s_q[7 * q + 2][tid];
-                tt.k00 = s_q[7 * q + 3][tid]; tt.k11 = s_q[7 * q + 4][tid]; tt.k01 = s_q[7 * q + 5][tid];
-                tt.ga0 = tt.ga1 = tt.om = 0.0;
-                strains_T_q<NPC, NVC>(*tab, q, g, tt, ye);
-            }
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-#pragma unroll
-            for (int i = 0; i < LD; ++i) dst[i] = ye[i];
+            ply_strain_cotangents_to_ybuf<NPC, NVC, QUAD, UHAT, NQ>(tab, el, s_q, tid, eslot, e, out);
         } else {
             const double sh = res[0];
             for (int p = 0; p < npt; ++p) {
@@ -207,26 +282,10 @@ k_ply_failure(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doub
             }
         }
     } else if (e < m.nel) {                      // outside the selected sub-domain
-        if constexpr (MODE == PF_DW) {
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-            for (int i = 0; i < LD; ++i) dst[i] = 0.0;
-        } else if constexpr (MODE == PF_DTABLE) {
-            double* o = out + (size_t)e * npt * PLY_W;
-            for (int k = 0; k < npt * PLY_W; ++k) o[k] = 0.0;
-        }
+        if constexpr (MODE == PF_DW) ply_zero_ybuf_slot<LD>(eslot, e, out);
+        else if constexpr (MODE == PF_DTABLE) ply_zero_table_row<PLY_W>(e, npt, out);
     }
-    if constexpr (MODE == PF_VALUE) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double m2 = shfl_xor_d(km, off), z2 = shfl_xor_d(kz, off);
-            ks_merge(km, kz, m2, z2);
-        }
-        area = wave_sum(area);
-        if (tid == 0) {
-            double* p = out + (size_t)blockIdx.x * 3;
-            p[0] = km; p[1] = kz; p[2] = area;
-        }
-    }
+    if constexpr (MODE == PF_VALUE) ply_block_slot(km, kz, area, tid, out);
 }
 
 // res[0] = S = log sum wj exp(rho FI) (the shift of the gradient kernels), res[1] = reference area of the selection,

@@ -29,28 +29,6 @@
 
 namespace femo {
 
-// the six strains of every degree-4 point of the state w, through the thread's column of LDS into registers
-template <int NPC, int NVC, bool QUAD, bool UHAT, int NQ>
-__device__ __forceinline__ void ply_point_strains(const MeshDev& m, const Tables* __restrict__ tab, const Elem<NPC, NVC>& el,
-                                                  const double* __restrict__ w, double (*s_q)[PLY_BLOCK], int tid, double (&s)[NQ][6]) {
-    constexpr int LD = 3 * NPC + 3 * NVC;
-    {
-        double xe[LD];
-        load_state<NPC, NVC>(m, el, w, xe);
-        for (int q = 0; q < NQ; ++q) {
-            QPG g;
-            qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-            const Gen sq = strains_q<NPC, NVC>(*tab, q, g, xe);
-            s_q[6 * q + 0][tid] = sq.e00; s_q[6 * q + 1][tid] = sq.e11; s_q[6 * q + 2][tid] = sq.g01;
-            s_q[6 * q + 3][tid] = sq.k00; s_q[6 * q + 4][tid] = sq.k11; s_q[6 * q + 5][tid] = sq.k01;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s[q][k] = s_q[6 * q + k][tid];
-}
-
 // the maximiser q* of recovery point P over the points' strains s, with sigma, x = eps - z kappa and kappa at q*
 template <int NQ>
 __device__ __forceinline__ int ply_maximiser(const PlyPoint& P, const double (&s)[NQ][6], double* sigm, double* xm, double* km) {
@@ -136,6 +114,8 @@ k_ply_field_vjp(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const do
                 s_q[6 * qs + 3 + j][tid] -= P.z * t;
             }
         }
+        // ply_strain_cotangents_to_ybuf (ply_failure.h) written out: through the helper two instantiations of this kernel change their
+        // register count
         double ye[LD];
 #pragma unroll
         for (int i = 0; i < LD; ++i) ye[i] = 0.0;

@@ -264,21 +264,7 @@ k_ply_hashin(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doubl
 #pragma unroll
                     for (int j = 0; j < 3; ++j) { s_q[7 * q + j][tid] = eb[q][j]; s_q[7 * q + 3 + j][tid] = kb[q][j]; }
             }
-            double ye[LD];
-#pragma unroll
-            for (int i = 0; i < LD; ++i) ye[i] = 0.0;
-            for (int q = 0; q < NQ; ++q) {
-                QPG g;
-                qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-                Gen tt;
-                tt.e00 = s_q[7 * q + 0][tid]; tt.e11 = s_q[7 * q + 1][tid]; tt.g01 = s_q[7 * q + 2][tid];
-                tt.k00 = s_q[7 * q + 3][tid]; tt.k11 = s_q[7 * q + 4][tid]; tt.k01 = s_q[7 * q + 5][tid];
-                tt.ga0 = tt.ga1 = tt.om = 0.0;
-                strains_T_q<NPC, NVC>(*tab, q, g, tt, ye);
-            }
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-#pragma unroll
-            for (int i = 0; i < LD; ++i) dst[i] = ye[i];
+            ply_strain_cotangents_to_ybuf<NPC, NVC, QUAD, UHAT, NQ>(tab, el, s_q, tid, eslot, e, out);
         } else {
             const double sh = cbar ? 0.0 : res[0];
             for (int p = 0; p < npt; ++p) {
@@ -305,26 +291,10 @@ k_ply_hashin(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const doubl
             }
         }
     } else if (e < m.nel) {                      // outside the selected sub-domain
-        if constexpr (MODE == PH_DW) {
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-            for (int i = 0; i < LD; ++i) dst[i] = 0.0;
-        } else if constexpr (MODE == PH_DTABLE) {
-            double* o = out + (size_t)e * npt * PLY_W;
-            for (int k = 0; k < npt * PLY_W; ++k) o[k] = 0.0;
-        }
+        if constexpr (MODE == PH_DW) ply_zero_ybuf_slot<LD>(eslot, e, out);
+        else if constexpr (MODE == PH_DTABLE) ply_zero_table_row<PLY_W>(e, npt, out);
     }
-    if constexpr (MODE == PH_VALUE) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double m2 = shfl_xor_d(km, off), z2 = shfl_xor_d(kz, off);
-            ks_merge(km, kz, m2, z2);
-        }
-        area = wave_sum(area);
-        if (tid == 0) {
-            double* p = out + (size_t)blockIdx.x * 3;
-            p[0] = km; p[1] = kz; p[2] = area;
-        }
-    }
+    if constexpr (MODE == PH_VALUE) ply_block_slot(km, kz, area, tid, out);
 }
 
 // Every strength finite and > 0.  tab: the cell-major strengths table, n its entries.  *first (set to INT_MAX by the caller) receives

@@ -177,26 +177,10 @@ k_ply_shear(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const double
             }
         }
     } else if (e < m.nel) {                      // outside the selected sub-domain
-        if constexpr (MODE == PS_DW) {
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-            for (int i = 0; i < LD; ++i) dst[i] = 0.0;
-        } else if constexpr (MODE == PS_DTABLE) {
-            double* o = out + (size_t)e * npt * PSH_W;
-            for (int k = 0; k < npt * PSH_W; ++k) o[k] = 0.0;
-        }
+        if constexpr (MODE == PS_DW) ply_zero_ybuf_slot<LD>(eslot, e, out);
+        else if constexpr (MODE == PS_DTABLE) ply_zero_table_row<PSH_W>(e, npt, out);
     }
-    if constexpr (MODE == PS_VALUE) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double m2 = shfl_xor_d(km, off), z2 = shfl_xor_d(kz, off);
-            ks_merge(km, kz, m2, z2);
-        }
-        area = wave_sum(area);
-        if (tid == 0) {
-            double* p = out + (size_t)blockIdx.x * 3;
-            p[0] = km; p[1] = kz; p[2] = area;
-        }
-    }
+    if constexpr (MODE == PS_VALUE) ply_block_slot(km, kz, area, tid, out);
 }
 
 }  // namespace femo

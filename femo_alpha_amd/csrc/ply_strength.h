@@ -110,37 +110,6 @@ __device__ __forceinline__ int ply_sri_maximiser(const PlyPoint& P, const double
     return qs;
 }
 
-// ply_point_strains with the weights: the six strains and wj_q = w_q det_q Ju_q of every degree-4 point through the thread's column
-// of LDS (7 rows per point, the layout of k_ply_failure) into registers; returns the reference area sum_q w_q det_q
-template <int NPC, int NVC, bool QUAD, bool UHAT, int NQ>
-__device__ __forceinline__ double ply_point_strains_w(const MeshDev& m, const Tables* __restrict__ tab, const Elem<NPC, NVC>& el,
-                                                      const double* __restrict__ w, double (*s_q)[PLY_BLOCK], int tid, double (&s)[NQ][6],
-                                                      double (&wj)[NQ]) {
-    constexpr int LD = 3 * NPC + 3 * NVC;
-    double area = 0.0;
-    {
-        double xe[LD];
-        load_state<NPC, NVC>(m, el, w, xe);
-        for (int q = 0; q < NQ; ++q) {
-            QPG g;
-            qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-            const Gen sq = strains_q<NPC, NVC>(*tab, q, g, xe);
-            s_q[7 * q + 0][tid] = sq.e00; s_q[7 * q + 1][tid] = sq.e11; s_q[7 * q + 2][tid] = sq.g01;
-            s_q[7 * q + 3][tid] = sq.k00; s_q[7 * q + 4][tid] = sq.k11; s_q[7 * q + 5][tid] = sq.k01;
-            const double wd = tab->w[q] * g.det;
-            s_q[7 * q + 6][tid] = wd * g.Ju;
-            area += wd;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s[q][k] = s_q[7 * q + k][tid];
-        wj[q] = s_q[7 * q + 6][tid];
-    }
-    return area;
-}
-
 // res: shift S of the aggregate's gradient modes (read when cbar is null); cbar: cotangent of the field (nel npt) or null; eslot: slot
 // of every cell in ybuf (PSI_DW); out: part (PSI_VALUE, 3 doubles per block), the field (PSI_FIELD), ybuf (PSI_DW), d / d table
 // (PSI_DTABLE).  m selects the sub-domain: the caller passes every cell with a cotangent.
@@ -230,21 +199,7 @@ k_ply_strength(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const dou
 #pragma unroll
                     for (int j = 0; j < 3; ++j) { s_q[7 * q + j][tid] = eb[q][j]; s_q[7 * q + 3 + j][tid] = kb[q][j]; }
             }
-            double ye[LD];
-#pragma unroll
-            for (int i = 0; i < LD; ++i) ye[i] = 0.0;
-            for (int q = 0; q < NQ; ++q) {
-                QPG g;
-                qp_geometry<NVC, QUAD, UHAT>(el.X, el.Uh, tab->N1[q], tab->dN1[q], g);
-                Gen tt;
-                tt.e00 = s_q[7 * q + 0][tid]; tt.e11 = s_q[7 * q + 1][tid]; tt.g01 = s_q[7 * q + 2][tid];
-                tt.k00 = s_q[7 * q + 3][tid]; tt.k11 = s_q[7 * q + 4][tid]; tt.k01 = s_q[7 * q + 5][tid];
-                tt.ga0 = tt.ga1 = tt.om = 0.0;
-                strains_T_q<NPC, NVC>(*tab, q, g, tt, ye);
-            }
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-#pragma unroll
-            for (int i = 0; i < LD; ++i) dst[i] = ye[i];
+            ply_strain_cotangents_to_ybuf<NPC, NVC, QUAD, UHAT, NQ>(tab, el, s_q, tid, eslot, e, out);
         } else {
             const double sh = cbar ? 0.0 : res[0];
             for (int p = 0; p < npt; ++p) {
@@ -271,26 +226,10 @@ k_ply_strength(MeshDev m, FieldsDev f, const Tables* __restrict__ tab, const dou
             }
         }
     } else if (e < m.nel) {                      // outside the selected sub-domain
-        if constexpr (MODE == PSI_DW) {
-            double* dst = out + (size_t)eslot[e] * YSTRIDE;
-            for (int i = 0; i < LD; ++i) dst[i] = 0.0;
-        } else if constexpr (MODE == PSI_DTABLE) {
-            double* o = out + (size_t)e * npt * PLY_W;
-            for (int k = 0; k < npt * PLY_W; ++k) o[k] = 0.0;
-        }
+        if constexpr (MODE == PSI_DW) ply_zero_ybuf_slot<LD>(eslot, e, out);
+        else if constexpr (MODE == PSI_DTABLE) ply_zero_table_row<PLY_W>(e, npt, out);
     }
-    if constexpr (MODE == PSI_VALUE) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double m2 = shfl_xor_d(km, off), z2 = shfl_xor_d(kz, off);
-            ks_merge(km, kz, m2, z2);
-        }
-        area = wave_sum(area);
-        if (tid == 0) {
-            double* p = out + (size_t)blockIdx.x * 3;
-            p[0] = km; p[1] = kz; p[2] = area;
-        }
-    }
+    if constexpr (MODE == PSI_VALUE) ply_block_slot(km, kz, area, tid, out);
 }
 
 // The quadratic form of every recovery point must be positive semidefinite for r to exist: F11, F22, F66 >= 0 and

@@ -261,6 +261,58 @@ def test_ply_failure_is_bit_identical_after_calls_of_the_new_outputs():
     c.close()
 
 
+TABLE_OF = {"ply_failure": "ply_table", "ply_shear_failure": "ply_shear_table", "ply_strength_index": "ply_table",
+            "ply_hashin_fibre": "ply_table", "ply_hashin_matrix": "ply_table"}
+
+
+@pytest.fixture(scope="module")
+def five_criteria_context():
+    """80 quadrilaterals (two blocks of 64 cells), four recovery points in every table, a random state, and a selected
+    sub-domain that lies inside the second block: the first block's slot of every value pass is the empty pair."""
+    from test_gpu_ply_hashin import _context
+    from test_ply_hashin_cpu import case_inputs
+    from test_gpu_laminate import PLY
+    m = plate_mesh(2.0, 10.0, 4, 20)
+    assert m.nel == 80
+    inp = case_inputs(m, 11, 4)
+    c = _context(m, inp)
+    mat = [np.full((m.nel, 4), PLY[k]) for k in ("G13", "G23")]
+    c.set_ply_shear_table(lm.ply_shear_table(*mat, inp["rng"].uniform(-90, 90, (m.nel, 4)), lm.shear_strength(3e4, 2e4)))
+    c.set_state(inp["w"])
+    c.set_ply_failure_params(5.0 / max(np.abs(c.ply_failure_field()).max(), c.ply_strength_index_field().max(),
+                                       *(f.max() for f in c.ply_hashin_field())))
+    c.set_ply_shear_params(5.0 / c.ply_shear_failure_field().max())
+    tags = (np.arange(m.nel) >= 68).astype(np.int32)
+    c.set_cell_tags(tags, 2)
+    c.select_subdomain(1)
+    c.set_stress_alpha(2.5, 1)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("first", list(TABLE_OF))
+def test_every_criterion_is_bit_identical_after_calls_of_the_other_four(five_criteria_context, first):
+    """The criteria share tables, kernels' plumbing and one table of descriptors, but each has block slots and a shift of its
+    own: the value and the state gradient of one are the same bits after the value, the state gradient and the table gradient
+    of every other one."""
+    c = five_criteria_context
+    take = lambda: (c.functional(first), c.dfunctional(first, "disp_solid"))
+    v0, g0 = take()
+    assert np.isfinite(v0) and np.all(np.isfinite(g0)) and np.any(g0)
+    for other, table in TABLE_OF.items():
+        if other != first:
+            assert np.isfinite(c.functional(other))
+            assert np.any(c.dfunctional(other, "disp_solid")) and np.any(c.dfunctional(other, table))
+    v1, g1 = take()
+    assert v1 == v0 and np.array_equal(g1, g0)
+    # a value pass of every other criterion between the value pass and the gradient of this one: each reads its own shift
+    v2 = c.functional(first)
+    for other in TABLE_OF:
+        if other != first:
+            c.functional(other)
+    assert v2 == v0 and np.array_equal(c.dfunctional(first, "disp_solid"), g0)
+
+
 def _table_ctx(m, rng):
     """Laminate and recovery points of the same two plies, clamped, refined to the rounding floor."""
     from femo_alpha_amd.backend import ShellContext
